@@ -33,6 +33,10 @@ launches of the timed region (every 8th step) and of an untimed repeat of the sa
 `hbm_control_*` fields: the same kernel, same layout, same proposals over a list whose row array (480 MB) cannot stay in the
 256 MiB Infinity Cache, so HBM-vs-cache is settled by measurement), `cpu_baseline` (numpy re-score of the same sparse likelihood on
 the host) and `cpu_baseline_dense` (the C restatement of the reference's dense sub_compute_likelihood on the C2 stand-in), N = 1 only.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller -- the float64 [neighbours, 13] candidate
+deltas -- as DIR/candidate_deltas.npy.  Problem, layout, warm-up and proposals are all seeded and the sums are int64 fixed point, so
+the same arguments give the same file on every run and every build that computes the same thing.
 """
 import argparse
 import json
@@ -238,7 +242,14 @@ def main():
     ap.add_argument("--late-only", action="store_true", help="only the late stage's reference-arithmetic scoring steps (what profiles/valu_late.json is profiled on)")
     ap.add_argument("--late-repeats", type=int, default=1, help="--late-only: run the timed steps this many times")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / sharding check without a GPU (CPU test-suite)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its float64 [neighbours, 13] candidate deltas) "
+                         "as DIR/candidate_deltas.npy; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.late_only:
+        ap.error("--dump-outputs writes the headline region's last step, which --late-only does not run")
 
     from graal_amd import dist as gdist
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -524,12 +535,15 @@ def main():
     sync_all()
     t0 = time.perf_counter()
     for f, nb in timed_props:
-        smp._candidate_deltas(f, nb, max_id)   # records a HIP event pair around k_scan on the stream it runs on
+        last_deltas = smp._candidate_deltas(f, nb, max_id)   # records a HIP event pair around k_scan on the stream it runs on
         n_cand += 13 * len(nb)
         if step_t is not None:
             step_t.append(time.perf_counter())
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # (every rank holds the same summed deltas)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "candidate_deltas.npy"), np.asarray(last_deltas, dtype=np.float64))
     if step_t is not None and rank == 0:
         print("per-step us:", " ".join("%.1f" % (1e6 * (b - a)) for a, b in zip([t0] + step_t[:-1], step_t)),
               "| closing barrier + synchronize: %.1f" % (1e6 * (t0 + elapsed - step_t[-1])), file=sys.stderr)
