@@ -4315,6 +4315,9 @@ __global__ __launch_bounds__(256) void k_rep_delta(RepArgs R, const NbTables* __
 struct HostStep;                 // host_step.h: the sampler's per-step host logic
 void hs_free(HostStep* p);
 
+struct SimBuf;                 // simulate.h: graal_simulate_contacts' buffers
+void sim_free(SimBuf* b);
+
 struct Ctx {
     int device = 0;
     HostStep* hs = nullptr;
@@ -4508,6 +4511,7 @@ struct Ctx {
     long long* d_qout = nullptr;    // K*13
     long long counters[4] = {0, 0, 0, 0};
     float timing[4] = {0, 0, 0, 0};
+    SimBuf* sim = nullptr;        // graal_simulate_contacts' buffers (simulate.h; allocated by its first call)
 };
 
 #define CK(call)                                                                                     \
@@ -5247,6 +5251,7 @@ void graal_destroy(graal_ctx* h)
         for (void* p : ptrs) if (p) (void)hipFree(p);
         if (h->nccl_comm) { Rccl* R = rccl_load(nullptr); if (R) (void)R->CommDestroy(h->nccl_comm); h->nccl_comm = nullptr; }
         if (h->d_own_obs) (void)hipFree(h->d_own_obs);
+        sim_free(h->sim); h->sim = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
         if (h->h_stats) (void)hipHostFree(h->h_stats);
@@ -6740,3 +6745,5 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "host_fit.h"
 
 } // extern "C"
+
+#include "simulate.h"

@@ -51,6 +51,7 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_upload_subfrags", "graal_upload_repeats", "graal_upload_contacts", "graal_upload_contacts_f32", "graal_upload_frags", "graal_download_frags",
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
+           "graal_simulate_contacts", "graal_simulate_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
 STEP_DONE, STEP_PAUSED, STEP_FALLBACK, STEP_SELECT = 0, 1, 2, 3
@@ -122,6 +123,8 @@ def load():
         L.graal_take_carry_correction.argtypes = [ctypes.c_void_p, _i64p, _i32p]
         L.graal_upload_own_obs.argtypes = [ctypes.c_void_p, _f32p, ctypes.c_int32]
         L.graal_explode.argtypes = [ctypes.c_void_p, _i64p]
+        L.graal_simulate_contacts.argtypes = [ctypes.c_void_p, ctypes.c_uint64, _i64p]
+        L.graal_simulate_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i32p, ctypes.c_int64]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_finisher.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_mode.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -350,6 +353,19 @@ class Engine:
         self._ck(self._L.graal_upload_distance_ref(self._h, *[x.ctypes.data_as(_i32p) for x in a],
                                                    c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(c)),
                  "graal_upload_distance_ref")
+
+    def simulate_contacts(self, seed):
+        """graal_simulate_contacts + graal_simulate_fetch: contacts drawn from the uploaded layout under the contact model (one Poisson
+        count per sub-fragment pair, seeded Philox4x32-10) as the COO list graal_upload_contacts takes -- (row, col, count) int32, row < col,
+        sorted by (row, col).  Needs sub-fragments, parameters and fragments, no contacts."""
+        nnz = ctypes.c_int64(0)
+        self._ck(self._L.graal_simulate_contacts(self._h, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.byref(nnz)),
+                 "graal_simulate_contacts")
+        n = int(nnz.value)
+        row, col, cnt = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        self._ck(self._L.graal_simulate_fetch(self._h, row.ctypes.data_as(_i32p), col.ctypes.data_as(_i32p), cnt.ctypes.data_as(_i32p), n),
+                 "graal_simulate_fetch")
+        return row, col, cnt
 
     def genome_distance_half_units(self):
         v = ctypes.c_int64(0)

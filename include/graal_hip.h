@@ -251,6 +251,18 @@ int graal_upload_own_obs(graal_ctx* h, const float* own, int32_t n_bins);
  * bench.py reports out[1] as `fallbacks`. */
 int graal_run_counters(graal_ctx* h, int64_t out[12]);
 
+/* Simulated data: Hi-C contacts drawn from the CURRENT layout under the contact model -- the reference's simulate_data_2d
+ * (kernels3.cu:2331-2800) behind simulate_rippe_contacts (cuda_lib_gl.py:1355, called by simulation_loader.py:120).  Needs
+ * graal_upload_subfrags, graal_set_params and graal_upload_frags, no contact list (it relabels the contigs first if the layout changed
+ * since the last relabel).  For every pair of sub-fragments a < b of active fragments an independent count ~ Poisson(lambda), lambda =
+ * the expected value of that sub-pixel in the full likelihood (exact RF-count indexing; a negative value counts as 0).  The result is
+ * kept on the device: *nnz_out = its nonzero entries, graal_simulate_fetch copies them out (cap >= nnz) as graal_upload_contacts takes
+ * them -- row < col, count > 0, sorted by (row, col).  A function of (layout, tables, parameters, seed) alone: bit-identical from run
+ * to run and on any GPU (Philox4x32-10 keyed by the seed, counters from pair / chunk coordinates; graal_amd/csrc/simulate.h).
+ * GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats). */
+int graal_simulate_contacts(graal_ctx* h, uint64_t seed, int64_t* nnz_out);
+int graal_simulate_fetch(graal_ctx* h, int32_t* row, int32_t* col, int32_t* count, int64_t cap);
+
 /* ---- the sampler's per-step HOST logic behind the boundary (graal_amd/csrc/host_step.h) --------------------------------
  * What cuda_lib_gl.sampler.step_max_likelihood does on the host between its launches: return_neighbours
  * (cuda_lib_gl.py:2295-2331: RandomState.choice(xk, n, p=pk, replace=False), expansion to the copies of repeated bins,
