@@ -4318,6 +4318,9 @@ void hs_free(HostStep* p);
 struct SimBuf;                 // simulate.h: graal_simulate_contacts' buffers
 void sim_free(SimBuf* b);
 
+struct JnBuf;                  // junctions.h: graal_junction_scores' buffers
+void jn_free(JnBuf* b);
+
 struct Ctx {
     int device = 0;
     HostStep* hs = nullptr;
@@ -4512,6 +4515,7 @@ struct Ctx {
     long long counters[4] = {0, 0, 0, 0};
     float timing[4] = {0, 0, 0, 0};
     SimBuf* sim = nullptr;        // graal_simulate_contacts' buffers (simulate.h; allocated by its first call)
+    JnBuf* jn = nullptr;          // graal_junction_scores' buffers (junctions.h; allocated by its first call)
 };
 
 #define CK(call)                                                                                     \
@@ -5252,6 +5256,7 @@ void graal_destroy(graal_ctx* h)
         if (h->nccl_comm) { Rccl* R = rccl_load(nullptr); if (R) (void)R->CommDestroy(h->nccl_comm); h->nccl_comm = nullptr; }
         if (h->d_own_obs) (void)hipFree(h->d_own_obs);
         sim_free(h->sim); h->sim = nullptr;
+        jn_free(h->jn); h->jn = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
         if (h->h_stats) (void)hipHostFree(h->h_stats);
@@ -6747,3 +6752,4 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 } // extern "C"
 
 #include "simulate.h"
+#include "junctions.h"

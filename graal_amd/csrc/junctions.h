@@ -1,0 +1,381 @@
+// junctions.h -- the likelihood each join of the current layout carries, for every junction in one pass (graal_junction_scores).
+// Included by graal_hip.hip after the C ABI (it uses Ctx, Stat, centre_kb, rippe, to_q, WAVE_LDS_SYNC and model_math.h).
+//
+// J[f] = logL(layout) - logL(layout cut between f and next[f]), for f in a LINEAR contig with next[f] != -1, in the engine's exact
+// arithmetic: pairs on one side of the cut are exactly unchanged, so only the pairs that STRADDLE the cut contribute -- they go from their cis
+// price to their trans price (v_inter * norm, with the reference's trans-branch RF-count indexing under GRAAL_MODE_REF_TRANS_ACCU):
+//   a contact:                  ob * (ln ex_cis - ln ex_trans), rounded to Q once per contact;
+//   a fragment pair's mass:   -(sum over its sub-fragment pairs of ex_cis - ex_trans), rounded to Q once per fragment pair.
+//
+// Decomposition.  Number the fragments of the layout by slots: a contig's fragments are consecutive, in position order.  A straddling pair
+// (x at slot i, y at slot j > i, one contig) adds its term c to D[i] and subtracts it at D[j]; the junction behind slot k is straddled by
+// exactly the pairs with i <= k < j, so J = the inclusive prefix sum of D at f's slot.  Every pair adds and removes its term inside its own
+// contig, so one inclusive scan over all slots is the per-contig scan (int64 sums wrap, the differences are exact).
+//
+// The slot numbering is built here from the layout itself (contig label -> member count -> exclusive scan -> offset + position), not taken
+// from the engine's position index: the call does not relabel, and so leaves the ranked layout, the carried total and a pending commit's
+// correction exactly as they were.  Kernels, all on the engine's stream (behind any commit or relabel the host has launched):
+//   k_jn_count / scan / k_jn_prep  -- slots, a 48-byte record per slot and a 16-byte record per sub-fragment (centre as the pricing has it);
+//   k_jn_nnz   -- streams the row-sorted COO list, 64 consecutive contacts per wave; terms are summed per run of equal slots inside the wave
+//                 (a segmented shuffle scan) and only a run's last lane touches D: a row's contacts share its slot, so the row side costs
+//                 about one atomic per row and wave; the column side one per run of equal column slots;
+//   k_jn_mass  -- k_full_mass_t's tiling: a wave's lanes are 64 consecutive slots x, the slots y behind them staged in LDS 64 at a time, S waves
+//                 per x tile.  Lane l visits the staged y's in the order l, l+1, ... (mod 64), so at every step the 64 lanes hold 64 different
+//                 columns: the column sums of a tile are kept in LDS without atomics, then one device atomic per tile column, and one per
+//                 row at the end;
+//   k_jn_quirk -- only with GRAAL_MODE_REF_TRANS_ACCU and bins of mixed RF counts: straddling pairs beyond the window, whose trans price
+//                 differs from their (v_inter) cis price by the indexing alone;
+//   two inclusive scans (D, and a count of non-finite terms laid out the same way), then k_jn_out: J and a status byte per fragment.
+#pragma once
+
+namespace {
+
+struct JnSub { int label; float centre; int accu; int slot; };   // accu: RF count | under the trans-branch indexing << 16; slot -1: circular
+struct JnFrag { int frag, start_bp, len_bp, flags; int n, a0, a1, a2; float c0, c1, c2; int last; };   // per slot; flags bit0 fwd, bit1 circ
+
+struct JnBuf {
+    int n = 0, S = 0;
+    int *cnt = nullptr, *base = nullptr, *slot = nullptr;
+    JnFrag* fr = nullptr;
+    JnSub* sub = nullptr;
+    long long *D = nullptr, *P = nullptr;
+    int *B = nullptr, *PB = nullptr;
+    long long* q = nullptr; unsigned char* st = nullptr;   // the results, fragment-indexed
+    void* tmp = nullptr; size_t tmp_bytes = 0;
+    unsigned* err = nullptr;
+};
+
+void jn_free(JnBuf* b)
+{
+    if (!b) return;
+    void* p[] = {b->cnt, b->base, b->slot, b->fr, b->sub, b->D, b->P, b->B, b->PB, b->q, b->st, b->tmp, b->err};
+    for (void* q : p) if (q) (void)hipFree(q);
+    delete b;
+}
+
+// members per contig label (labels lie in [0, n + 2]: the mutations keep them in [0, n_contigs + 2])
+__global__ void k_jn_count(SoaPtr s, int n, int* __restrict__ cnt, unsigned* __restrict__ err)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    const int c = s.p[F_IDC][f];
+    if (c < 0 || c > n + 2) { atomicOr(err, 1u); return; }
+    atomicAdd(&cnt[c], 1);
+}
+
+__global__ __launch_bounds__(256) void k_jn_prep(SoaPtr s, int n, const Stat* __restrict__ stat, const int* __restrict__ sub_ids,
+                                                 const int* __restrict__ cnt, const int* __restrict__ base, int* __restrict__ slot_of,
+                                                 JnFrag* __restrict__ fr, JnSub* __restrict__ sub, unsigned* __restrict__ err)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    const int c = s.p[F_IDC][f], pos = s.p[F_POS][f];
+    if (c < 0 || c > n + 2 || pos < 0 || pos >= cnt[c]) { atomicOr(err, 2u); slot_of[f] = -1; return; }
+    const int slot = base[c] + pos;
+    if (slot < 0 || slot >= n) { atomicOr(err, 2u); slot_of[f] = -1; return; }
+    slot_of[f] = slot;
+    const Stat st = stat[f];
+    const bool fwd = s.p[F_ORI][f] == 1, circ = s.p[F_CIRC][f] == 1;
+    const int start = s.p[F_START][f];
+    JnFrag r;
+    r.frag = f; r.start_bp = start; r.len_bp = s.p[F_LEN][f]; r.flags = (fwd ? 1 : 0) | (circ ? 2 : 0);
+    r.n = st.n; r.a0 = st.a0; r.a1 = st.a1; r.a2 = st.a2;
+    r.c0 = st.n > 0 ? centre_kb(start, fwd, st, 0) : 0.0f;
+    r.c1 = st.n > 1 ? centre_kb(start, fwd, st, 1) : 0.0f;
+    r.c2 = st.n > 2 ? centre_kb(start, fwd, st, 2) : 0.0f;
+    r.last = base[c] + cnt[c] - 1;
+    fr[slot] = r;
+    int4 ids = make_int4(f, 0, 0, 1);
+    if (sub_ids) ids = reinterpret_cast<const int4*>(sub_ids)[f];
+    for (int k = 0; k < st.n; k++) {
+        JnSub u;
+        u.label = c;
+        u.centre = sel3(r.c0, r.c1, r.c2, k);
+        u.accu = stat_accu(st, k) | ((fwd ? stat_accu(st, k) : stat_accu(st, st.n - 1)) << 16);   // (RF counts are <= 30000)
+        u.slot = circ ? -1 : slot;
+        sub[sel3(ids.x, ids.y, ids.z, k)] = u;
+    }
+}
+
+// Segmented sum over the wave's runs of equal keys: on return `v` of a run's LAST lane (`tail`) holds the run's sum.  Whole wave.
+__device__ __forceinline__ void jn_run_sum(int key, long long& v, bool& tail)
+{
+    const int lane = threadIdx.x & 63;
+    const int kp = __shfl_up(key, 1, 64), kn = __shfl_down(key, 1, 64);
+    int f = (lane == 0 || kp != key) ? 1 : 0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long vu = __shfl_up(v, o, 64);
+        const int fu = __shfl_up(f, o, 64);
+        if (lane >= o && !f) { v += vu; f |= fu; }
+    }
+    tail = lane == 63 || kn != key;
+}
+
+__device__ __forceinline__ void jn_bad(int* __restrict__ B, int i, int j)
+{
+    atomicAdd(&B[i < j ? i : j], 1);
+    atomicAdd(&B[i < j ? j : i], -1);
+}
+
+__global__ __launch_bounds__(256) void k_jn_nnz(const int* __restrict__ row, const int* __restrict__ col, const int* __restrict__ cnt,
+                                                long long nnz, const JnSub* __restrict__ sub, const JnFrag* __restrict__ fr, float nfpb, Par par,
+                                                int quirk, long long* __restrict__ D, int* __restrict__ B)
+{
+    const int lane = threadIdx.x & 63;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
+    for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: jn_run_sum needs the whole wave)
+        const long long k = k0 + lane;
+        int ka = -1, kb = -1;
+        long long c = 0;
+        if (k < nnz) {
+            const JnSub A = sub[row[k]], Bs = sub[col[k]];
+            ka = A.slot; kb = Bs.slot;
+            if (A.slot >= 0 && Bs.slot >= 0 && A.label == Bs.label && A.slot != Bs.slot) {
+                const int lo_a = A.accu & 0xffff, lo_b = Bs.accu & 0xffff;
+                const int prod = lo_a * lo_b;
+                int prod_t = prod;
+                if (quirk && ((A.accu >> 16) != lo_a || (Bs.accu >> 16) != lo_b)) {
+                    const int bin_a = fr[A.slot].frag, bin_b = fr[Bs.slot].frag;
+                    prod_t = bin_a < bin_b ? (A.accu >> 16) * lo_b : lo_a * (Bs.accu >> 16);
+                }
+                const float sd = fabsf(Bs.centre - A.centre);
+                // (at |d| >= d_max rippe is v_inter exactly: the cis and trans prices are the same float32 value unless the indexing differs)
+                if (!(sd >= par.d_max && prod_t == prod && par.v_inter >= 0.0f)) {
+                    const float ex = rippe(sd, par) * ((float)prod / nfpb);
+                    const float et = par.v_inter * ((float)prod_t / nfpb);
+                    const double ob = (double)__int_as_float(cnt[k]);
+                    const long long q = to_q(ob * (mm_ln(ex) - mm_ln(et)));
+                    if (q == Q_BAD) jn_bad(B, A.slot, Bs.slot);
+                    else c = A.slot < Bs.slot ? q : -q;
+                }
+            }
+        }
+        long long vr = c, vc = -c;
+        bool tr, tc;
+        jn_run_sum(ka, vr, tr);
+        jn_run_sum(kb, vc, tc);
+        if (tr && ka >= 0 && vr != 0) atomicAdd((unsigned long long*)&D[ka], (unsigned long long)vr);
+        if (tc && kb >= 0 && vc != 0) atomicAdd((unsigned long long*)&D[kb], (unsigned long long)vc);
+    }
+}
+
+// trans price of sub-fragment pair (a, b) of fragments x, y: v_inter * norm, with the reference's indexing when `quirk` (ex_pair_ref)
+__device__ __forceinline__ float jn_trans(int ax, int ay, int lx, int ly, bool fwd_x, bool fwd_y, int fx, int fy, float nfpb, const Par& par, int quirk)
+{
+    if (quirk) { if (fx < fy) { if (!fwd_x) ax = lx; } else if (!fwd_y) ay = ly; }
+    return par.v_inter * ((float)(ax * ay) / nfpb);
+}
+
+__device__ __forceinline__ double jn_pair_mass(const JnFrag& x, const JnFrag& y, float nfpb, const Par& par, int quirk)
+{
+    double acc = 0.0;
+    const int lx = sel3(x.a0, x.a1, x.a2, x.n - 1), ly = sel3(y.a0, y.a1, y.a2, y.n - 1);
+    for (int a = 0; a < x.n; a++)
+        for (int b = 0; b < y.n; b++) {
+            const int ax = sel3(x.a0, x.a1, x.a2, a), ay = sel3(y.a0, y.a1, y.a2, b);
+            const float norm = (float)(ax * ay) / nfpb;
+            const float sd = fabsf(sel3(y.c0, y.c1, y.c2, b) - sel3(x.c0, x.c1, x.c2, a));
+            const float ex = rippe(sd, par) * norm;
+            acc += (double)ex - (double)jn_trans(ax, ay, lx, ly, x.flags & 1, y.flags & 1, x.frag, y.frag, nfpb, par, quirk);
+        }
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void k_jn_mass(int n, const JnFrag* __restrict__ fr, float nfpb, Par par, int quirk, int reach_bp, int S,
+                                                 long long* __restrict__ D, int* __restrict__ B)
+{
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const int W = blockIdx.x * 4 + wib, tile = W / S, s = W - tile * S;
+    __shared__ JnFrag s_y[4][64];
+    __shared__ long long s_col[4][64];
+    JnFrag* const ty = s_y[wib];
+    long long* const tc = s_col[wib];
+    const int i = tile * 64 + lane;
+    JnFrag x;
+    x.frag = 0; x.start_bp = 0; x.len_bp = 0; x.flags = 0; x.n = 0; x.a0 = x.a1 = x.a2 = 0; x.c0 = x.c1 = x.c2 = 0.0f; x.last = -1;
+    if (i < n) { x = fr[i]; x.last = min(x.last, n - 1); }
+    const int x_end = x.start_bp + x.len_bp;
+    long long row = 0;
+    tc[lane] = 0;
+    bool live = i < n && !(x.flags & 2) && x.last > i;
+    for (int c = s; ; c += S) {
+        const int j0 = tile * 64 + 64 * c;
+        if (__ballot(live && x.last >= j0) == 0ull) break;
+        if (j0 + lane < n) ty[lane] = fr[j0 + lane];
+        WAVE_LDS_SYNC();
+        bool beyond = false;
+        for (int t = 0; t < 64; t++) {
+            const int jj = (lane + t) & 63, j = j0 + jj;
+            if (live && j > i && j <= x.last) {               // (x.last < n)
+                const JnFrag& y = ty[jj];
+                if (y.start_bp - x_end > reach_bp) beyond = true;   // beyond the window: cis = trans exactly (k_jn_quirk: the indexing)
+                else {
+                    const long long q = to_q_fast(jn_pair_mass(x, y, nfpb, par, quirk));
+                    if (q == Q_BAD) jn_bad(B, i, j);
+                    else if (q != 0) { row -= q; tc[jj] += q; }
+                }
+            }
+            WAVE_LDS_SYNC();                                  // (step t + 1's lanes read the columns step t's lanes wrote)
+        }
+        const long long v = tc[lane];
+        if (v != 0 && j0 + lane < n) atomicAdd((unsigned long long*)&D[j0 + lane], (unsigned long long)v);
+        tc[lane] = 0;
+        live = live && !beyond && x.last >= j0 + 64;
+        WAVE_LDS_SYNC();
+    }
+    if (row != 0) atomicAdd((unsigned long long*)&D[i], (unsigned long long)row);
+}
+
+// GRAAL_MODE_REF_TRANS_ACCU with bins of mixed RF counts: a reversed such bin x, paired with a later-id bin y of its (linear) contig beyond
+// the window, is priced v_inter * plain norm now and with x's last RF count once the cut separates them.  One block per such bin.
+__global__ __launch_bounds__(256) void k_jn_quirk(int n, const int* __restrict__ ubins, const int* __restrict__ slot_of, const JnFrag* __restrict__ fr,
+                                                  float nfpb, Par par, int reach_bp, long long* __restrict__ D, int* __restrict__ B)
+{
+    const int xf = ubins[blockIdx.x];
+    const int i = slot_of[xf];
+    if (i < 0) return;
+    const JnFrag x = fr[i];
+    if ((x.flags & 2) || (x.flags & 1) || x.n < 1) return;
+    // (the contig's slots end at x.last and share it: walk back from there)
+    for (int j = min(x.last, n - 1) - (int)threadIdx.x; j >= 0; j -= (int)blockDim.x) {
+        const JnFrag y = fr[j];
+        if (y.last != x.last) break;                          // left the contig (slots of one contig share their last slot)
+        if (j == i || y.frag < xf || y.n < 1) continue;
+        const bool far = j > i ? y.start_bp - (x.start_bp + x.len_bp) > reach_bp : x.start_bp - (y.start_bp + y.len_bp) > reach_bp;
+        if (!far) continue;
+        double acc = 0.0;
+        const int lx = sel3(x.a0, x.a1, x.a2, x.n - 1);
+        for (int a = 0; a < x.n; a++)
+            for (int b = 0; b < y.n; b++) {
+                const int ay = sel3(y.a0, y.a1, y.a2, b);
+                acc += (double)(par.v_inter * ((float)(sel3(x.a0, x.a1, x.a2, a) * ay) / nfpb)) - (double)(par.v_inter * ((float)(lx * ay) / nfpb));
+            }
+        const long long q = to_q(acc);
+        if (q == Q_BAD) { jn_bad(B, i, j); continue; }
+        if (q == 0) continue;
+        const int lo = i < j ? i : j, hi = i < j ? j : i;
+        atomicAdd((unsigned long long*)&D[lo], (unsigned long long)(-q));
+        atomicAdd((unsigned long long*)&D[hi], (unsigned long long)q);
+    }
+}
+
+__global__ void k_jn_out(SoaPtr s, int n, const int* __restrict__ slot_of, const long long* __restrict__ P, const int* __restrict__ PB,
+                         long long* __restrict__ q_out, unsigned char* __restrict__ st_out)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    const int k = slot_of[f];
+    unsigned char st;
+    long long q = 0;
+    if (s.p[F_CIRC][f] == 1) st = GRAAL_JUNCTION_CIRCULAR;
+    else if (s.p[F_NEXT][f] == -1 || k < 0) st = GRAAL_JUNCTION_END;
+    else if (PB[k] != 0) st = GRAAL_JUNCTION_NONFINITE;
+    else { st = GRAAL_JUNCTION_VALID; q = P[k]; }
+    q_out[f] = q;
+    st_out[f] = st;
+}
+
+} // namespace
+
+extern "C" {
+
+int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status)
+{
+    if (!h || !q_out || !status) return GRAAL_E_ARG;
+    if (!(h->have_sub && h->have_par && h->have_frags && h->have_contacts))
+        return fail(h, GRAAL_E_STATE, "graal_junction_scores: upload sub-fragments, parameters, fragments and contacts first");
+    if (h->has_rep) return fail(h, GRAAL_E_UNSUPPORTED, "graal_junction_scores: bins with several copies (graal_upload_repeats) are not supported");
+    if (h->x_host || h->nccl_comm) return fail(h, GRAAL_E_STATE, "graal_junction_scores: one rank only (an exchange or RCCL is attached)");
+    CK(hipSetDevice(h->device));
+    const int n = h->n, S = h->n_sub_total;
+    if (n < 1) return GRAAL_OK;
+    if (!h->jn) h->jn = new JnBuf();
+    JnBuf* J = h->jn;
+    hipStream_t s = h->stream;
+    if (J->n != n || J->S != S) {
+        // (every pointer is freed AND nulled, and J->n stays 0 until the whole set is allocated: a failed hipMalloc leaves nothing to free twice)
+        J->n = 0; J->S = 0;
+        void** p[] = {(void**)&J->cnt, (void**)&J->base, (void**)&J->slot, (void**)&J->fr, (void**)&J->sub, (void**)&J->D, (void**)&J->P,
+                                    (void**)&J->B, (void**)&J->PB, (void**)&J->q, (void**)&J->st, &J->tmp, (void**)&J->err};
+        for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
+        J->tmp_bytes = 0;
+        CK(hipMalloc(&J->cnt, sizeof(int) * (size_t)(n + 3)));
+        CK(hipMalloc(&J->base, sizeof(int) * (size_t)(n + 3)));
+        CK(hipMalloc(&J->slot, sizeof(int) * (size_t)n));
+        CK(hipMalloc(&J->fr, sizeof(JnFrag) * (size_t)n));
+        CK(hipMalloc(&J->sub, sizeof(JnSub) * (size_t)std::max(S, 1)));
+        CK(hipMalloc(&J->D, sizeof(long long) * (size_t)n));
+        CK(hipMalloc(&J->P, sizeof(long long) * (size_t)n));
+        CK(hipMalloc(&J->B, sizeof(int) * (size_t)n));
+        CK(hipMalloc(&J->PB, sizeof(int) * (size_t)n));
+        CK(hipMalloc(&J->q, sizeof(long long) * (size_t)n));
+        CK(hipMalloc(&J->st, (size_t)n));
+        CK(hipMalloc(&J->err, sizeof(unsigned)));
+        size_t b1 = 0, b2 = 0, b3 = 0;
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, J->cnt, J->base, n + 3, s));
+        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b2, J->D, J->P, n, s));
+        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b3, J->B, J->PB, n, s));
+        const size_t tb = std::max(b1, std::max(b2, b3));
+        CK(hipMalloc(&J->tmp, tb));
+        J->tmp_bytes = tb;
+        J->n = n; J->S = S;
+    }
+    const SoaPtr sp = h->soa[h->cur];
+    const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
+    int rc = GRAAL_OK;
+    unsigned err = 0;
+    do {
+#define JN_CK(call) { const hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = hipGetErrorString(e_); rc = GRAAL_E_HIP; break; } }
+        JN_CK(hipMemsetAsync(J->err, 0, sizeof(unsigned), s));
+        JN_CK(hipMemsetAsync(J->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
+        JN_CK(hipMemsetAsync(J->D, 0, sizeof(long long) * (size_t)n, s));
+        JN_CK(hipMemsetAsync(J->B, 0, sizeof(int) * (size_t)n, s));
+        JN_CK(hipMemsetAsync(J->fr, 0, sizeof(JnFrag) * (size_t)n, s));   // (a slot no fragment claims -- a corrupt layout -- reads as empty)
+        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, J->cnt, J->err);
+        JN_CK(hipGetLastError());
+        size_t tb = J->tmp_bytes;
+        JN_CK(hipcub::DeviceScan::ExclusiveSum(J->tmp, tb, J->cnt, J->base, n + 3, s));
+        k_jn_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, h->stat_frag, h->d_sub_ids, J->cnt, J->base, J->slot, J->fr, J->sub, J->err);
+        JN_CK(hipGetLastError());
+        JN_CK(hipMemcpyAsync(&err, J->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        JN_CK(hipStreamSynchronize(s));
+        if (err) break;   // (a corrupt layout: the slots are not to be trusted, nothing reads them)
+        if (h->nnz > 0) {
+            const long long waves = (h->nnz + 63) / 64;
+            const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
+            k_jn_nnz<<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, J->sub, J->fr, h->nfpb, h->par, quirk, J->D, J->B);
+            JN_CK(hipGetLastError());
+        }
+        const int lc = std::min(std::max(std::max(h->max_lcont, h->lcont_bound), 1), n);
+        const int n_tiles = (n + 63) / 64;
+        const int Sw = std::min(16, std::max(1, ((lc + 63) / 64 + 7) / 8));
+        k_jn_mass<<<(n_tiles * Sw + 3) / 4, 256, 0, s>>>(n, J->fr, h->nfpb, h->par, quirk, reach_bp(h), Sw, J->D, J->B);
+        JN_CK(hipGetLastError());
+        if (quirk && h->n_ubins) {
+            k_jn_quirk<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, J->slot, J->fr, h->nfpb, h->par, reach_bp(h), J->D, J->B);
+            JN_CK(hipGetLastError());
+        }
+        tb = J->tmp_bytes;
+        JN_CK(hipcub::DeviceScan::InclusiveSum(J->tmp, tb, J->D, J->P, n, s));
+        tb = J->tmp_bytes;
+        JN_CK(hipcub::DeviceScan::InclusiveSum(J->tmp, tb, J->B, J->PB, n, s));
+        k_jn_out<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, J->slot, J->P, J->PB, J->q, J->st);
+        JN_CK(hipGetLastError());
+        JN_CK(hipMemcpyAsync(q_out, J->q, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, s));
+        JN_CK(hipMemcpyAsync(status, J->st, (size_t)n, hipMemcpyDeviceToHost, s));
+        JN_CK(hipStreamSynchronize(s));
+#undef JN_CK
+    } while (false);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    if (err) {
+        char m[160];
+        snprintf(m, sizeof m, "graal_junction_scores: corrupt layout (contig labels or positions out of range, flags %u)", err);
+        h->err = m;
+        return GRAAL_E_STATE;
+    }
+    return GRAAL_OK;
+}
+
+} // extern "C"

@@ -51,10 +51,11 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_upload_subfrags", "graal_upload_repeats", "graal_upload_contacts", "graal_upload_contacts_f32", "graal_upload_frags", "graal_download_frags",
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
-           "graal_simulate_contacts", "graal_simulate_fetch",
+           "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
 STEP_DONE, STEP_PAUSED, STEP_FALLBACK, STEP_SELECT = 0, 1, 2, 3
+JUNCTION_VALID, JUNCTION_END, JUNCTION_CIRCULAR, JUNCTION_NONFINITE = 0, 1, 2, 3   # graal_junction_scores' status bytes
 STEPS_ROW = 10   # GRAAL_STEPS_ROW: doubles per step in graal_steps' rows
 
 
@@ -125,6 +126,7 @@ def load():
         L.graal_explode.argtypes = [ctypes.c_void_p, _i64p]
         L.graal_simulate_contacts.argtypes = [ctypes.c_void_p, ctypes.c_uint64, _i64p]
         L.graal_simulate_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i32p, ctypes.c_int64]
+        L.graal_junction_scores.argtypes = [ctypes.c_void_p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_finisher.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_mode.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -366,6 +368,22 @@ class Engine:
         self._ck(self._L.graal_simulate_fetch(self._h, row.ctypes.data_as(_i32p), col.ctypes.data_as(_i32p), cnt.ctypes.data_as(_i32p), n),
                  "graal_simulate_fetch")
         return row, col, cnt
+
+    def junction_scores(self):
+        """graal_junction_scores: (J float64[n], status uint8[n]), indexed by fragment.  J[f] = logL(layout) - logL(layout cut between f and
+        next[f]) in the exact arithmetic, NaN where there is no score; status JUNCTION_VALID / _END / _CIRCULAR / _NONFINITE.  Needs
+        sub-fragments, parameters, fragments and contacts; one rank, no repeated bins.  Leaves the step state alone."""
+        q, st = self.junction_scores_q()
+        return np.where(st == JUNCTION_VALID, q.astype(np.float64) / Q_SCALE, np.nan), st
+
+    def junction_scores_q(self):
+        """The same as (int64 Q[n], status uint8[n])."""
+        n = int(self.n)
+        q = np.zeros(n, dtype=np.int64)
+        st = np.zeros(n, dtype=np.uint8)
+        self._ck(self._L.graal_junction_scores(self._h, q.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+                 "graal_junction_scores")
+        return q, st
 
     def genome_distance_half_units(self):
         v = ctypes.c_int64(0)

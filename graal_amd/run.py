@@ -43,6 +43,8 @@ def main(argv=None):
                                                            "main_gl.py:213, 283) into the output folder")
     ap.add_argument("--no-fit", action="store_true", help="skip the Rippe fit; needs --param (8 floats: kuhn lm c1 slope d d_max fact v_inter)")
     ap.add_argument("--param", type=float, nargs=8, default=None, help="param_simu to run with instead of the fit's")
+    ap.add_argument("--junctions", action="store_true", help="write junctions.tsv into the output folder: every join of the final layout "
+                                                             "with the log-likelihood it carries (graal_amd.junctions)")
     args = ap.parse_args(argv)
     if not 0 <= args.level < args.size_pyramid:
         raise SystemExit("--level must be in 0 .. size-pyramid - 1 (levels >= 1: the level below holds the observations; 0: the level itself)")
@@ -99,6 +101,9 @@ def main(argv=None):
         P.load_reference_sequence(args.fasta)
         g.copy_from_gpu()
         lev.generate_new_fasta(g, os.path.join(out, "genome.fasta"), os.path.join(out, "info_frags.txt"))
+    if args.junctions:
+        from . import junctions
+        junctions.write_junctions_tsv(os.path.join(out, "junctions.tsv"), junctions.junction_table(smp))
     n_steps = len(trace.likelihood)
     print("%d bins (%d fragments, %d sub-fragments), %d MCMC steps in %.1f s (%.0f us/step): %d contigs, logL %.6e, "
           "distance to the initial genome %.4f; traces in %s" % (inp["n_frags"], inp["n_new_frags"], inp["init_n_sub_frags"], n_steps,

@@ -263,6 +263,25 @@ int graal_run_counters(graal_ctx* h, int64_t out[12]);
 int graal_simulate_contacts(graal_ctx* h, uint64_t seed, int64_t* nnz_out);
 int graal_simulate_fetch(graal_ctx* h, int32_t* row, int32_t* col, int32_t* count, int64_t cap);
 
+/* Junction scores: how strongly the data support each join of the CURRENT layout, all junctions in one pass (graal_amd/csrc/junctions.h).
+ * For a fragment f with next[f] != -1 in a LINEAR contig:  J[f] = logL(layout) - logL(the same layout cut between f and next[f]),
+ * in the exact arithmetic: pairs on one side of the cut count as unchanged; every pair of sub-fragments of two bins on opposite sides
+ * (both in the contig) moves from its cis price to its trans price and contributes
+ *   per contact:     ob * (ln ex_cis - ln ex_trans),  rounded to Q once per contact;
+ *   expected mass:   -(ex_cis - ex_trans), summed over the sub-fragment pairs of a fragment pair and rounded to Q once per fragment pair,
+ * ex_cis priced from the layout's float32 centres as graal_eval_full_q prices it, ex_trans as graal_eval_full_q prices a trans pixel under
+ * the current mode flags (GRAAL_MODE_REF_TRANS_ACCU included).  q_out[f] = J[f] in Q (positive: the data prefer the join); int64 sums,
+ * bit-identical from call to call and for any grid.  status[f]: GRAAL_JUNCTION_VALID, _END (next[f] == -1: no junction), _CIRCULAR
+ * (opening a ring re-prices every pair of it: no score), _NONFINITE (a straddling term was not finite); q_out[f] = 0 unless VALID.
+ * Both arrays are indexed by fragment, n entries.  Needs sub-fragments, parameters, fragments and contacts.  Does not relabel and
+ * leaves the step state alone (ranked layout, carried total, a pending commit's correction): a later step behaves as without the call.
+ * GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats); GRAAL_E_STATE with an exchange or RCCL attached (one rank only). */
+#define GRAAL_JUNCTION_VALID 0
+#define GRAAL_JUNCTION_END 1
+#define GRAAL_JUNCTION_CIRCULAR 2
+#define GRAAL_JUNCTION_NONFINITE 3
+int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status);
+
 /* ---- the sampler's per-step HOST logic behind the boundary (graal_amd/csrc/host_step.h) --------------------------------
  * What cuda_lib_gl.sampler.step_max_likelihood does on the host between its launches: return_neighbours
  * (cuda_lib_gl.py:2295-2331: RandomState.choice(xk, n, p=pk, replace=False), expansion to the copies of repeated bins,
