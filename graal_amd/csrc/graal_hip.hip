@@ -4321,6 +4321,9 @@ void sim_free(SimBuf* b);
 struct JnBuf;                  // junctions.h: graal_junction_scores' buffers
 void jn_free(JnBuf* b);
 
+struct LnBuf;                  // links.h: graal_end_links' buffers and results
+void ln_free(LnBuf* b);
+
 struct Ctx {
     int device = 0;
     HostStep* hs = nullptr;
@@ -4516,6 +4519,7 @@ struct Ctx {
     float timing[4] = {0, 0, 0, 0};
     SimBuf* sim = nullptr;        // graal_simulate_contacts' buffers (simulate.h; allocated by its first call)
     JnBuf* jn = nullptr;          // graal_junction_scores' buffers (junctions.h; allocated by its first call)
+    LnBuf* ln = nullptr;          // graal_end_links' buffers and its last result (links.h; allocated by its first call)
 };
 
 #define CK(call)                                                                                     \
@@ -5257,6 +5261,7 @@ void graal_destroy(graal_ctx* h)
         if (h->d_own_obs) (void)hipFree(h->d_own_obs);
         sim_free(h->sim); h->sim = nullptr;
         jn_free(h->jn); h->jn = nullptr;
+        ln_free(h->ln); h->ln = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
         if (h->h_stats) (void)hipHostFree(h->h_stats);
@@ -6753,3 +6758,4 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 
 #include "simulate.h"
 #include "junctions.h"
+#include "links.h"

@@ -1,0 +1,770 @@
+// links.h -- the likelihood every join between two contig ends would add, for every pair of ends the contacts support (graal_end_links).
+// Included by graal_hip.hip after junctions.h (it uses Ctx, Stat, centre_kb, rippe, to_q, k_jn_count, jn_trans and model_math.h).
+//
+// Ends.  end = 2 * f + side of a LINEAR contig: side 0 its head (position 0), side 1 its tail (position l_cont - 1), f the fragment there.
+// For ends eA < eB of different contigs A, B the joined layout is canonical: A oriented so that eA is its tail (A reversed iff eA is a head),
+// B after it oriented so that eB is its head (B reversed iff eB is a tail); positions, start_bp and ori as m_paste writes them, the centres
+// through centre_kb from the integer offsets.  L(eA, eB) = logL(joined) - logL(current) in the exact arithmetic, with the junction call's
+// roundings: pairs inside A and inside B count as unchanged; every sub-fragment pair of A x B moves from its current trans price to its
+// price in the joined layout (a contact: ob * (ln ex_new - ln ex_trans), rounded to Q once; a fragment pair's mass: -(sum of ex_new -
+// ex_trans), rounded to Q once).  Under GRAAL_MODE_REF_TRANS_ACCU with bins of mixed RF counts two more terms belong to L:
+//   - A x B pairs beyond the window that involve such a bin (v_inter * plain norm after the join, v_inter * indexed norm now);
+//   - the MIRROR term: a reversed contig flips the orientation of its mixed bins, and the trans-branch indexing prices a pair by the
+//     orientation of its lower-id bin: every pair (x of the reversed contig, mixed; y outside it, y > x) changes its trans price.
+//     mirror[C] (one per contig, for its reversal) is summed once; a link adds it for each contig it reverses and takes off the part that
+//     falls on the partner contig, whose pairs it prices directly.
+//
+// Which links are listed: the pairs of ends with at least one contact between their contigs inside the window (sub-fragment centre
+// distance < d_max) in the joined orientation.  Kernels, all on the engine's stream:
+//   k_jn_count / scan / k_ln_prep -- slots (junctions.h's numbering: label -> count -> exclusive scan -> offset + position), a 48-byte
+//                 record per slot, a 32-byte record per sub-fragment and a 32-byte record per contig label (end fragments, bp length,
+//                 eligibility: linear with >= min_frags fragments);
+//   k_ln_nnz<COUNT> -- streams the row-sorted COO list, 64 contacts per wave; for a contact between two eligible contigs each of the 4
+//                 end combinations yields a record when its joined distance is inside the window or its term is not zero (the quirk).
+//                 Records are summed per run of equal keys inside the wave (segmented shuffle scans) and only a run's last lane touches
+//                 the table: the count pass counts those lanes (an upper bound of the distinct keys that sizes the table), the insert
+//                 pass adds into an open-addressing table keyed by (eA << 32 | eB) with 64-bit CAS and linear probing;
+//   k_ln_flag, hipCUB DeviceSelect::Flagged, k_ln_keys, a radix sort by key, k_ln_gather -- the listed keys in (end_a, end_b) order;
+//   k_ln_mass  -- a wave per (link, group of 8 fragments of A walked from eA); lanes are 8 x 8 fragment pairs, the tile steps along B from
+//                 eB and the wave stops when every pair has left the window (the joined gap only grows along both walks);
+//   k_ln_mirror, k_ln_quirk -- only with GRAAL_MODE_REF_TRANS_ACCU and mixed bins: mirror[C] (one block per mixed bin, all later bins),
+//                 and the A x B pairs with a mixed bin (beyond the window, and the mirror's part on the partner): a wave per (link, group
+//                 of 8 fragments of A) as k_ln_mass, over all of B -- the only work that grows with contig length outside the window;
+//   k_ln_out   -- q = direct + mirrors of the reversed contigs, and a status byte.
+#pragma once
+
+namespace {
+
+constexpr unsigned long long LN_EMPTY = ~0ull;
+
+struct LnSub { int label, frag, meta, acc, start, len, lbp, pad; };   // meta: sub k | n << 2 | fwd << 4 | mixed << 5 | eligible << 6 | circ << 7
+                                                                    // acc: RF count | RF count of the bin's last sub-fragment << 16
+struct LnFrag { int frag, start, len, fwd; Stat st; };              // per slot
+struct LnCtg { int head, tail, first, cnt, lbp, elig, nmix, pad; };   // per contig label; nmix: its bins of mixed RF counts
+
+struct LnBuf {
+    int n = 0, S = 0;
+    int *cnt = nullptr, *base = nullptr, *slot = nullptr, *lab = nullptr;
+    LnFrag* fr = nullptr;
+    LnSub* sub = nullptr;
+    LnCtg* ctg = nullptr;
+    long long* mir = nullptr; int* mirbad = nullptr;
+    unsigned* err = nullptr; unsigned long long* ctr = nullptr;       // ctr: [0] records counted, [1] listed keys, [2] eligible contigs
+    void* tmp = nullptr; size_t tmp_bytes = 0;
+    // the key table and the per-link arrays grow to the largest size a call needed (within GRAAL_LINKS_MAX_BYTES)
+    unsigned long long* keys = nullptr; long long *tq = nullptr, *tc = nullptr; int* tf = nullptr; unsigned char* tsel = nullptr; size_t cap = 0;
+    unsigned long long *ko = nullptr, *ks = nullptr; int *vo = nullptr, *vs = nullptr;
+    long long *q = nullptr, *c = nullptr, *ch = nullptr, *choff = nullptr; int* bad = nullptr; unsigned char* st = nullptr;
+    int *ea = nullptr, *eb = nullptr;
+    size_t lcap = 0;
+    void* stmp = nullptr; size_t stmp_bytes = 0;
+    long long n_links = -1;                                          // -1: no result to fetch
+};
+
+void ln_free_table(LnBuf* b)
+{
+    void** p[] = {(void**)&b->keys, (void**)&b->tq, (void**)&b->tc, (void**)&b->tf, (void**)&b->tsel};
+    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    b->cap = 0;
+}
+
+void ln_free_links(LnBuf* b)
+{
+    void** p[] = {(void**)&b->ko, (void**)&b->ks, (void**)&b->vo, (void**)&b->vs, (void**)&b->q, (void**)&b->c, (void**)&b->bad, (void**)&b->ch,
+                  (void**)&b->choff, (void**)&b->st, (void**)&b->ea, (void**)&b->eb};
+    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    b->lcap = 0;
+}
+
+void ln_free_fixed(LnBuf* b)
+{
+    void** p[] = {(void**)&b->cnt, (void**)&b->base, (void**)&b->slot, (void**)&b->lab, (void**)&b->fr, (void**)&b->sub, (void**)&b->ctg,
+                  (void**)&b->mir, (void**)&b->mirbad, (void**)&b->err, (void**)&b->ctr, &b->tmp};
+    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    b->tmp_bytes = 0; b->n = 0; b->S = 0;
+}
+
+void ln_free(LnBuf* b)
+{
+    if (!b) return;
+    ln_free_fixed(b); ln_free_table(b); ln_free_links(b);
+    if (b->stmp) (void)hipFree(b->stmp);
+    delete b;
+}
+
+__global__ __launch_bounds__(256) void k_ln_prep(SoaPtr s, int n, int min_frags, const Stat* __restrict__ stat, const int* __restrict__ sub_ids,
+                                                 const int* __restrict__ cnt, const int* __restrict__ base, int* __restrict__ slot_of,
+                                                 int* __restrict__ lab, LnFrag* __restrict__ fr, LnSub* __restrict__ sub, LnCtg* __restrict__ ctg,
+                                                 unsigned long long* __restrict__ n_elig, unsigned* __restrict__ err)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    const int c = s.p[F_IDC][f], pos = s.p[F_POS][f];
+    if (c < 0 || c > n + 2 || pos < 0 || pos >= cnt[c]) { atomicOr(err, 2u); slot_of[f] = -1; lab[f] = -1; return; }
+    const int slot = base[c] + pos;
+    if (slot < 0 || slot >= n) { atomicOr(err, 2u); slot_of[f] = -1; lab[f] = -1; return; }
+    slot_of[f] = slot;
+    lab[f] = c;
+    const Stat st = stat[f];
+    const bool fwd = s.p[F_ORI][f] == 1, circ = s.p[F_CIRC][f] == 1;
+    const int start = s.p[F_START][f], len = s.p[F_LEN][f], lbp = s.p[F_LCONTBP][f];
+    const bool elig = !circ && cnt[c] >= min_frags;
+    LnFrag r;
+    r.frag = f; r.start = start; r.len = len; r.fwd = fwd ? 1 : 0; r.st = st;
+    fr[slot] = r;
+    if (pos == 0) {
+        ctg[c].head = f; ctg[c].first = base[c]; ctg[c].cnt = cnt[c]; ctg[c].lbp = lbp; ctg[c].elig = elig ? 1 : 0;
+        if (elig) atomicAdd(n_elig, 1ull);
+    }
+    if (pos == cnt[c] - 1) ctg[c].tail = f;
+    const int last = stat_accu(st, st.n - 1);
+    const int mixed = stat_uniform(st) ? 0 : 1;
+    if (mixed && elig) atomicAdd(&ctg[c].nmix, 1);
+    int4 ids = make_int4(f, 0, 0, 1);
+    if (sub_ids) ids = reinterpret_cast<const int4*>(sub_ids)[f];
+    for (int k = 0; k < st.n; k++) {
+        LnSub u;
+        u.label = c; u.frag = f; u.start = start; u.len = len; u.lbp = lbp; u.pad = 0;
+        u.meta = k | (st.n << 2) | ((fwd ? 1 : 0) << 4) | (mixed << 5) | ((elig ? 1 : 0) << 6) | ((circ ? 1 : 0) << 7);
+        u.acc = stat_accu(st, k) | (last << 16);                     // (RF counts are <= 30000)
+        sub[sel3(ids.x, ids.y, ids.z, k)] = u;
+    }
+}
+
+__device__ __forceinline__ int ln_k(int meta) { return meta & 3; }
+__device__ __forceinline__ bool ln_fwd(int meta) { return (meta >> 4) & 1; }
+__device__ __forceinline__ bool ln_mixed(int meta) { return (meta >> 5) & 1; }
+__device__ __forceinline__ bool ln_elig(int meta) { return (meta >> 6) & 1; }
+
+// start_bp in the joined layout of a fragment (start, len) of a contig of lbp bp: first (A) or second (B) in the join, reversed or not
+__device__ __forceinline__ int ln_new_start(int start, int len, int lbp, int lbp_first, bool first, bool rev)
+{
+    const int s = rev ? lbp - start - len : start;
+    return first ? s : lbp_first + s;
+}
+
+// 64-bit key mixer (splitmix64's finaliser) and the table slot of `key`: linear probing from the mixed key, claimed with a 64-bit CAS
+__device__ __forceinline__ unsigned long long ln_mix(unsigned long long z)
+{
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ long long ln_slot(unsigned long long* __restrict__ keys, unsigned long long cap, unsigned long long key,
+                                             unsigned* __restrict__ err)
+{
+    unsigned long long i = __umul64hi(ln_mix(key), cap);
+    for (unsigned long long t = 0; t < cap; t++) {
+        const unsigned long long old = atomicCAS(&keys[i], LN_EMPTY, key);
+        if (old == LN_EMPTY || old == key) return (long long)i;
+        if (++i == cap) i = 0;
+    }
+    atomicOr(err, 4u);                                               // (cannot happen: the table holds more slots than records)
+    return -1;
+}
+
+// Segmented sums over the wave's runs of equal 64-bit keys: on return a run's LAST lane (`tail`) holds the run's sums.  Whole wave.
+__device__ __forceinline__ void ln_run_sum(unsigned long long key, long long& v0, long long& v1, long long& v2, bool& tail)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long kp = __shfl_up(key, 1, 64), kn = __shfl_down(key, 1, 64);
+    int f = (lane == 0 || kp != key) ? 1 : 0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long u0 = __shfl_up(v0, o, 64), u1 = __shfl_up(v1, o, 64), u2 = __shfl_up(v2, o, 64);
+        const int fu = __shfl_up(f, o, 64);
+        if (lane >= o && !f) { v0 += u0; v1 += u1; v2 += u2; f |= fu; }
+    }
+    tail = lane == 63 || kn != key;
+}
+
+// The contact pass.  COUNT: count the records a wave would insert (after its run sums).  Otherwise insert them, and sum the contact part
+// of mirror[C] (the quirk) per contig.
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_ln_nnz(const int* __restrict__ row, const int* __restrict__ col, const int* __restrict__ cnt, long long nnz,
+                                                const LnSub* __restrict__ sub, const Stat* __restrict__ stat, const LnCtg* __restrict__ ctg,
+                                                float nfpb, Par par, int quirk, unsigned long long cap, unsigned long long* __restrict__ keys,
+                                                long long* __restrict__ tq, long long* __restrict__ tc, int* __restrict__ tf,
+                                                long long* __restrict__ mir, int* __restrict__ mirbad, unsigned long long* __restrict__ n_rec,
+                                                unsigned* __restrict__ err)
+{
+    const int lane = threadIdx.x & 63;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
+    unsigned long long n_wave = 0;                                   // COUNT: the wave's records, one atomic at the end
+    for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: the run sums need the whole wave)
+        const long long k = k0 + lane;
+        LnSub X = {-1, -1, 0, 0, 0, 0, 0, 0}, Y = X;                   // (lanes past the list: no contig, no bin, no flags)
+        bool diff = false;
+        if (k < nnz) {
+            X = sub[row[k]]; Y = sub[col[k]];
+            diff = X.label != Y.label;
+        }
+        const bool pair = diff && ln_elig(X.meta) && ln_elig(Y.meta);
+        // the quirk: the lower-id bin's orientation picks the trans price's indexing
+        const bool x_low = X.frag < Y.frag;
+        const LnSub& lo = x_low ? X : Y;
+        const bool mq = quirk && diff && ln_mixed(lo.meta) && ln_elig(lo.meta);
+        if (__ballot(pair || mq) == 0ull) continue;
+        const double ob = k < nnz ? (double)__int_as_float(cnt[k]) : 0.0;
+        const int own_x = X.acc & 0xffff, own_y = Y.acc & 0xffff;
+        const int prod = own_x * own_y;
+        int prod_t = prod, prod_f = prod;                            // the current trans indexing, and with the lower bin flipped
+        if (quirk && diff) {
+            const int own_l = lo.acc & 0xffff, last_l = lo.acc >> 16, other = x_low ? own_y : own_x;
+            prod_t = (ln_fwd(lo.meta) ? own_l : last_l) * other;
+            prod_f = (ln_fwd(lo.meta) ? last_l : own_l) * other;
+        }
+        long long m_term = 0;
+        bool m_bad = false;
+        if (mq && prod_f != prod_t) {
+            const float et = par.v_inter * ((float)prod_t / nfpb), ef = par.v_inter * ((float)prod_f / nfpb);
+            m_term = to_q(ob * (mm_ln(ef) - mm_ln(et)));
+            if (m_term == Q_BAD) { m_bad = true; m_term = 0; }
+        }
+        if (!COUNT) {                                                // mirror[C]'s contacts, summed per run of the lower bin's contig
+            const unsigned long long mk = (mq && (m_term != 0 || m_bad)) ? (unsigned long long)lo.label : LN_EMPTY;
+            if (__ballot(mk != LN_EMPTY) != 0ull) {
+                long long v0 = m_term, v1 = m_bad ? 1 : 0, v2 = 0;
+                bool tail;
+                ln_run_sum(mk, v0, v1, v2, tail);
+                if (tail && mk != LN_EMPTY) {
+                    if (v0 != 0) atomicAdd((unsigned long long*)&mir[mk], (unsigned long long)v0);
+                    if (v1 != 0) atomicAdd(&mirbad[mk], (int)v1);
+                }
+            }
+        }
+        if (__ballot(pair) == 0ull) continue;
+        LnCtg CX, CY;
+        Stat SX, SY;
+        if (pair) { CX = ctg[X.label]; CY = ctg[Y.label]; SX = stat[X.frag]; SY = stat[Y.frag]; }
+        const float et = par.v_inter * ((float)prod_t / nfpb);
+        const double ln_et = mm_ln(et);
+#pragma unroll 1
+        for (int c = 0; c < 4; c++) {
+            unsigned long long key = LN_EMPTY;
+            long long q = 0, n_in = 0, fl = 0;
+            if (pair) {
+                const int sx = c >> 1, sy = c & 1;
+                const int ex = 2 * (sx ? CX.tail : CX.head) + sx, ey = 2 * (sy ? CY.tail : CY.head) + sy;
+                const bool x_first = ex < ey;
+                // A (first) is reversed iff its end is a head; B (second) iff its end is a tail
+                const bool rev_x = x_first ? sx == 0 : sx == 1, rev_y = x_first ? sy == 1 : sy == 0;
+                const int lbp_first = x_first ? X.lbp : Y.lbp;
+                const int nsx = ln_new_start(X.start, X.len, X.lbp, lbp_first, x_first, rev_x);
+                const int nsy = ln_new_start(Y.start, Y.len, Y.lbp, lbp_first, !x_first, rev_y);
+                const float cx = centre_kb(nsx, ln_fwd(X.meta) != rev_x, SX, ln_k(X.meta));
+                const float cy = centre_kb(nsy, ln_fwd(Y.meta) != rev_y, SY, ln_k(Y.meta));
+                const float sd = fabsf(cy - cx);
+                const bool in_win = sd < par.d_max;
+                bool bad = false;
+                // (at |d| >= d_max rippe is v_inter exactly: the joined and the trans prices are the same float32 value unless the indexing differs)
+                if (!(sd >= par.d_max && prod_t == prod && par.v_inter >= 0.0f)) {
+                    const float exn = rippe(sd, par) * ((float)prod / nfpb);
+                    const long long t = to_q(ob * (mm_ln(exn) - ln_et));
+                    if (t == Q_BAD) bad = true; else q = t;
+                }
+                if (mq && (x_low ? rev_x : rev_y)) { q -= m_term; bad = bad || m_bad; }   // the mirror's part on the partner: priced above
+                if (in_win || q != 0 || bad) {
+                    key = x_first ? ((unsigned long long)ex << 32) | (unsigned)ey : ((unsigned long long)ey << 32) | (unsigned)ex;
+                    n_in = in_win ? (long long)llrint(ob) : 0;
+                    fl = (bad ? 1 : 0) + (in_win ? (1ll << 32) : 0);
+                }
+            }
+            if (__ballot(key != LN_EMPTY) == 0ull) continue;
+            bool tail;
+            ln_run_sum(key, q, n_in, fl, tail);
+            const bool rec = tail && key != LN_EMPTY;
+            if (COUNT) {
+                n_wave += (unsigned long long)__popcll(__ballot(rec));
+            } else if (rec) {
+                const long long i = ln_slot(keys, cap, key, err);
+                if (i >= 0) {
+                    if (q != 0) atomicAdd((unsigned long long*)&tq[i], (unsigned long long)q);
+                    if (n_in != 0) atomicAdd((unsigned long long*)&tc[i], (unsigned long long)n_in);
+                    const int b = ((fl & 0xffffffffll) ? 1 : 0) | ((fl >> 32) ? 2 : 0);
+                    if (b) atomicOr(&tf[i], b);
+                }
+            }
+        }
+    }
+    if (COUNT && lane == 0 && n_wave) atomicAdd(n_rec, n_wave);     // (a single counter: one atomic per wave, not per contact group)
+}
+
+// the listed slots of the table (a contact inside the window), for hipCUB's DeviceSelect::Flagged; then the keys of the selected slots
+__global__ void k_ln_flag(const unsigned long long* __restrict__ keys, const int* __restrict__ tf, long long cap, unsigned char* __restrict__ sel)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cap) sel[i] = (keys[i] != LN_EMPTY && (tf[i] & 2)) ? 1 : 0;
+}
+
+__global__ void k_ln_keys(long long m, const unsigned long long* __restrict__ keys, const int* __restrict__ vo, unsigned long long* __restrict__ ko)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < m) ko[j] = keys[vo[j]];
+}
+
+__global__ void k_ln_gather(long long m, const unsigned long long* __restrict__ ks, const int* __restrict__ vs, const long long* __restrict__ tq,
+                            const long long* __restrict__ tc, const int* __restrict__ tf, const int* __restrict__ lab,
+                            const LnCtg* __restrict__ ctg, long long* __restrict__ q, long long* __restrict__ c, int* __restrict__ bad,
+                            long long* __restrict__ ch, int* __restrict__ ea, int* __restrict__ eb)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const int i = vs[k];
+    const unsigned long long key = ks[k];
+    ea[k] = (int)(key >> 32); eb[k] = (int)(key & 0xffffffffull);
+    q[k] = tq[i]; c[k] = tc[i]; bad[k] = tf[i] & 1;
+    ch[k] = (ctg[lab[ea[k] >> 1]].cnt + 7) / 8;                      // k_ln_mass: groups of 8 fragments of A
+}
+
+// one side of a link: the contig's slots walked from the end, its bp length and its orientation in the join
+struct LnSide { int first, cnt, lbp; bool from_tail, rev; };
+
+__device__ __forceinline__ LnSide ln_side(const LnCtg& C, int side, bool is_first)
+{
+    LnSide s;
+    s.first = C.first; s.cnt = C.cnt; s.lbp = C.lbp;
+    s.from_tail = side == 1;                                         // the walk starts at the joined end
+    s.rev = is_first ? side == 0 : side == 1;
+    return s;
+}
+__device__ __forceinline__ int ln_walk(const LnSide& s, int i) { return s.from_tail ? s.first + s.cnt - 1 - i : s.first + i; }
+__device__ __forceinline__ int ln_gap(const LnSide& s, const LnFrag& x) { return s.from_tail ? s.lbp - (x.start + x.len) : x.start; }
+
+// mass term of fragment pair (x of A, y of B): sum over sub-fragment pairs of ex_joined - ex_trans (current orientation, `quirk` indexing)
+__device__ __forceinline__ double ln_pair_mass(const LnFrag& x, int nsx, bool fx, const LnFrag& y, int nsy, bool fy, float nfpb, const Par& par,
+                                               int quirk)
+{
+    double acc = 0.0;
+    const int lx = stat_accu(x.st, x.st.n - 1), ly = stat_accu(y.st, y.st.n - 1);
+    for (int a = 0; a < x.st.n; a++) {
+        const float ca = centre_kb(nsx, fx, x.st, a);
+        const int ax = stat_accu(x.st, a);
+        for (int b = 0; b < y.st.n; b++) {
+            const int ay = stat_accu(y.st, b);
+            const float ex = rippe(fabsf(centre_kb(nsy, fy, y.st, b) - ca), par) * ((float)(ax * ay) / nfpb);
+            acc += (double)ex - (double)jn_trans(ax, ay, lx, ly, x.fwd, y.fwd, x.frag, y.frag, nfpb, par, quirk);
+        }
+    }
+    return acc;
+}
+
+__device__ __forceinline__ long long ln_wave_sum(long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_ln_mass(long long m, long long n_groups, const long long* __restrict__ choff, const long long* __restrict__ ch,
+                                                 const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ lab,
+                                                 const LnCtg* __restrict__ ctg, const LnFrag* __restrict__ fr, float nfpb, Par par, int quirk,
+                                                 int reach_bp, long long* __restrict__ q, int* __restrict__ bad)
+{
+    const int lane = threadIdx.x & 63;
+    const long long W = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (W >= n_groups) return;
+    // the link of group W: the last k with choff[k] <= W (links with no group never match)
+    long long lo = 0, hi = m - 1;
+    while (lo < hi) {
+        const long long mid = (lo + hi + 1) >> 1;
+        if (choff[mid] <= W) lo = mid; else hi = mid - 1;
+    }
+    const long long k = lo;
+    const long long g = W - choff[k];
+    if (g < 0 || g >= ch[k]) return;
+    const int e_a = ea[k], e_b = eb[k];
+    const LnCtg CA = ctg[lab[e_a >> 1]], CB = ctg[lab[e_b >> 1]];
+    const LnSide A = ln_side(CA, e_a & 1, true), B = ln_side(CB, e_b & 1, false);
+    const int i = g * 8 + (lane >> 3), jl = lane & 7;
+    LnFrag x;
+    int gx = 0, nsx = 0;
+    bool fx = false, live = i < A.cnt;
+    if (live) {
+        x = fr[ln_walk(A, i)];
+        gx = ln_gap(A, x);
+        nsx = ln_new_start(x.start, x.len, A.lbp, A.lbp, true, A.rev);
+        fx = (x.fwd != 0) != A.rev;
+        live = gx <= reach_bp;
+    }
+    long long sum = 0, nb = 0;
+    for (int j0 = 0; ; j0 += 8) {
+        const int j = j0 + jl;
+        bool in = live && j < B.cnt;
+        LnFrag y;
+        int gy = 0;
+        if (in) { y = fr[ln_walk(B, j)]; gy = ln_gap(B, y); in = (long long)gx + gy <= reach_bp; }
+        if (__ballot(in) == 0ull) break;                             // (the gap grows along both walks: no later tile is in the window)
+        if (in) {
+            const int nsy = ln_new_start(y.start, y.len, B.lbp, A.lbp, false, B.rev);
+            const long long t = to_q_fast(ln_pair_mass(x, nsx, fx, y, nsy, (y.fwd != 0) != B.rev, nfpb, par, quirk));
+            if (t == Q_BAD) nb++; else sum -= t;
+        }
+    }
+    sum = ln_wave_sum(sum);
+    nb = ln_wave_sum(nb);
+    if (lane == 0) {
+        if (sum != 0) atomicAdd((unsigned long long*)&q[k], (unsigned long long)sum);
+        if (nb != 0) atomicAdd(&bad[k], (int)nb);
+    }
+}
+
+// mirror mass term of bins x (mixed, flipped) and y (x < y): -(sum of trans(x flipped) - trans(x as now)), rounded to Q
+__device__ __forceinline__ long long ln_mirror_q(const LnFrag& x, const LnFrag& y, float nfpb, const Par& par)
+{
+    double acc = 0.0;
+    const int lx = stat_accu(x.st, x.st.n - 1);
+    for (int a = 0; a < x.st.n; a++) {
+        const int ax = stat_accu(x.st, a);
+        const int now = x.fwd ? ax : lx, flip = x.fwd ? lx : ax;
+        for (int b = 0; b < y.st.n; b++) {
+            const int ay = stat_accu(y.st, b);
+            acc += (double)(par.v_inter * ((float)(flip * ay) / nfpb)) - (double)(par.v_inter * ((float)(now * ay) / nfpb));
+        }
+    }
+    const long long q = to_q(acc);
+    return q == Q_BAD ? Q_BAD : -q;
+}
+
+__device__ __forceinline__ void ln_block_add(long long v, long long nb, long long* __restrict__ q, int* __restrict__ bad)
+{
+    v = ln_wave_sum(v);
+    nb = ln_wave_sum(nb);
+    if ((threadIdx.x & 63) == 0) {
+        if (v != 0) atomicAdd((unsigned long long*)q, (unsigned long long)v);
+        if (nb != 0) atomicAdd(bad, (int)nb);
+    }
+}
+
+// mirror[C], the mass part: one block per mixed bin x of an eligible contig, against every later bin of another contig
+__global__ __launch_bounds__(256) void k_ln_mirror(int n, const int* __restrict__ ubins, const int* __restrict__ slot_of, const int* __restrict__ lab,
+                                                   const LnCtg* __restrict__ ctg, const LnFrag* __restrict__ fr, float nfpb, Par par,
+                                                   long long* __restrict__ mir, int* __restrict__ mirbad)
+{
+    const int xf = ubins[blockIdx.x];
+    if (xf < 0 || xf >= n || slot_of[xf] < 0) return;
+    const int c = lab[xf];
+    if (!ctg[c].elig) return;
+    const LnFrag x = fr[slot_of[xf]];
+    if (x.st.n < 1) return;
+    long long sum = 0, nb = 0;
+    for (int y = xf + 1 + (int)threadIdx.x; y < n; y += (int)blockDim.x) {
+        if (lab[y] == c || slot_of[y] < 0) continue;
+        const long long t = ln_mirror_q(x, fr[slot_of[y]], nfpb, par);
+        if (t == Q_BAD) nb++; else sum += t;
+    }
+    ln_block_add(sum, nb, &mir[c], &mirbad[c]);
+}
+
+// per link, the A x B pairs with a mixed bin: beyond the window their joined price (v_inter * plain norm) differs from the indexed trans
+// price; and the mirror of a reversed contig counted a pair (its mixed bin, the partner's later bin) that the link prices directly.
+__device__ __forceinline__ void ln_quirk_pair(const LnFrag& x, const LnFrag& y, bool beyond, bool rev_x, bool rev_y, float nfpb, const Par& par,
+                                              long long& sum, long long& nb)
+{
+    if (beyond) {
+        double acc = 0.0;
+        const int lx = stat_accu(x.st, x.st.n - 1), ly = stat_accu(y.st, y.st.n - 1);
+        for (int a = 0; a < x.st.n; a++)
+            for (int b = 0; b < y.st.n; b++) {
+                const int ax = stat_accu(x.st, a), ay = stat_accu(y.st, b);
+                acc += (double)(par.v_inter * ((float)(ax * ay) / nfpb)) - (double)jn_trans(ax, ay, lx, ly, x.fwd, y.fwd, x.frag, y.frag, nfpb, par, 1);
+            }
+        const long long t = to_q(acc);
+        if (t == Q_BAD) nb++; else sum -= t;
+    }
+    if (rev_x && !stat_uniform(x.st) && x.frag < y.frag) {
+        const long long t = ln_mirror_q(x, y, nfpb, par);
+        if (t == Q_BAD) nb++; else sum -= t;
+    }
+    if (rev_y && !stat_uniform(y.st) && y.frag < x.frag) {
+        const long long t = ln_mirror_q(y, x, nfpb, par);
+        if (t == Q_BAD) nb++; else sum -= t;
+    }
+}
+
+// A wave per (link, group of 8 fragments of A) -- k_ln_mass's groups -- over ALL of B: lanes are 8 x 8 fragment pairs, and a pair is
+// priced when one of its bins is mixed (ln_quirk_pair).  Links whose two contigs hold no mixed bin return at once.
+__global__ __launch_bounds__(256) void k_ln_quirk(long long m, long long n_groups, const long long* __restrict__ choff, const long long* __restrict__ ch,
+                                                  const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ lab,
+                                                  const LnCtg* __restrict__ ctg, const LnFrag* __restrict__ fr, float nfpb, Par par, int reach_bp,
+                                                  long long* __restrict__ q, int* __restrict__ bad)
+{
+    const int lane = threadIdx.x & 63;
+    const long long W = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (W >= n_groups) return;
+    long long lo = 0, hi = m - 1;
+    while (lo < hi) {
+        const long long mid = (lo + hi + 1) >> 1;
+        if (choff[mid] <= W) lo = mid; else hi = mid - 1;
+    }
+    const long long k = lo;
+    const long long g = W - choff[k];
+    if (g < 0 || g >= ch[k]) return;
+    const int e_a = ea[k], e_b = eb[k];
+    const LnCtg CA = ctg[lab[e_a >> 1]], CB = ctg[lab[e_b >> 1]];
+    if (CA.nmix == 0 && CB.nmix == 0) return;
+    const LnSide A = ln_side(CA, e_a & 1, true), B = ln_side(CB, e_b & 1, false);
+    const long long i = g * 8 + (lane >> 3);
+    const int jl = lane & 7;
+    const bool live = i < A.cnt;
+    LnFrag x;
+    int gx = 0;
+    bool mx = false;
+    if (live) { x = fr[ln_walk(A, (int)i)]; gx = ln_gap(A, x); mx = !stat_uniform(x.st); }
+    if (__ballot(live) == 0ull) return;
+    long long sum = 0, nb = 0;
+    for (int j0 = 0; j0 < B.cnt; j0 += 8) {
+        const int j = j0 + jl;
+        if (!live || j >= B.cnt) continue;
+        const LnFrag y = fr[ln_walk(B, j)];
+        if (!mx && stat_uniform(y.st)) continue;
+        ln_quirk_pair(x, y, (long long)gx + ln_gap(B, y) > reach_bp, A.rev, B.rev, nfpb, par, sum, nb);
+    }
+    sum = ln_wave_sum(sum);
+    nb = ln_wave_sum(nb);
+    if (lane == 0) {
+        if (sum != 0) atomicAdd((unsigned long long*)&q[k], (unsigned long long)sum);
+        if (nb != 0) atomicAdd(&bad[k], (int)nb);
+    }
+}
+
+__global__ void k_ln_out(long long m, const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ lab,
+                         const long long* __restrict__ mir, const int* __restrict__ mirbad, int quirk, long long* __restrict__ q,
+                         const int* __restrict__ bad, unsigned char* __restrict__ st)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    long long v = q[k];
+    int b = bad[k];
+    if (quirk) {
+        const int ca = lab[ea[k] >> 1], cb = lab[eb[k] >> 1];
+        if ((ea[k] & 1) == 0) { v += mir[ca]; b += mirbad[ca]; }      // A reversed (its end is a head)
+        if ((eb[k] & 1) == 1) { v += mir[cb]; b += mirbad[cb]; }      // B reversed (its end is a tail)
+    }
+    st[k] = b ? GRAAL_LINK_NONFINITE : GRAAL_LINK_VALID;
+    q[k] = b ? 0 : v;
+}
+
+} // namespace
+
+extern "C" {
+
+int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
+{
+    if (!h || !n_links) return GRAAL_E_ARG;
+    if (min_frags < 1) return fail(h, GRAAL_E_ARG, "graal_end_links: min_frags must be >= 1");
+    if (!(h->have_sub && h->have_par && h->have_frags && h->have_contacts))
+        return fail(h, GRAAL_E_STATE, "graal_end_links: upload sub-fragments, parameters, fragments and contacts first");
+    if (h->has_rep) return fail(h, GRAAL_E_UNSUPPORTED, "graal_end_links: bins with several copies (graal_upload_repeats) are not supported");
+    if (h->x_host || h->nccl_comm) return fail(h, GRAAL_E_STATE, "graal_end_links: one rank only (an exchange or RCCL is attached)");
+    CK(hipSetDevice(h->device));
+    *n_links = 0;
+    const int n = h->n, S = h->n_sub_total;
+    if (!h->ln) h->ln = new LnBuf();
+    LnBuf* Lb = h->ln;
+    Lb->n_links = -1;
+    if (n < 1) { Lb->n_links = 0; return GRAAL_OK; }
+    hipStream_t s = h->stream;
+    if (Lb->n != n || Lb->S != S) {
+        // (every pointer is freed AND nulled, and Lb->n stays 0 until the whole set is allocated: a failed hipMalloc leaves nothing to free twice)
+        ln_free_fixed(Lb);
+        CK(hipMalloc(&Lb->cnt, sizeof(int) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->base, sizeof(int) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->slot, sizeof(int) * (size_t)n));
+        CK(hipMalloc(&Lb->lab, sizeof(int) * (size_t)n));
+        CK(hipMalloc(&Lb->fr, sizeof(LnFrag) * (size_t)n));
+        CK(hipMalloc(&Lb->sub, sizeof(LnSub) * (size_t)std::max(S, 1)));
+        CK(hipMalloc(&Lb->ctg, sizeof(LnCtg) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->mir, sizeof(long long) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->mirbad, sizeof(int) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->err, sizeof(unsigned)));
+        CK(hipMalloc(&Lb->ctr, sizeof(unsigned long long) * 3));
+        size_t b1 = 0;
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, Lb->cnt, Lb->base, n + 3, s));
+        CK(hipMalloc(&Lb->tmp, b1));
+        Lb->tmp_bytes = b1;
+        Lb->n = n; Lb->S = S;
+    }
+    const SoaPtr sp = h->soa[h->cur];
+    const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
+    const int mq = quirk && h->n_ubins > 0;
+    int rc = GRAAL_OK;
+    unsigned err = 0;
+    unsigned long long ctr[3] = {0, 0, 0};
+    long long m = 0;
+    const char* why = nullptr;
+    char msg[320];
+    do {
+#define LN_CK(call) { const hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = hipGetErrorString(e_); rc = GRAAL_E_HIP; break; } }
+        // ---- records
+        LN_CK(hipMemsetAsync(Lb->err, 0, sizeof(unsigned), s));
+        LN_CK(hipMemsetAsync(Lb->ctr, 0, sizeof(unsigned long long) * 3, s));
+        LN_CK(hipMemsetAsync(Lb->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
+        LN_CK(hipMemsetAsync(Lb->ctg, 0, sizeof(LnCtg) * (size_t)(n + 3), s));   // (labels no fragment holds: not eligible)
+        LN_CK(hipMemsetAsync(Lb->fr, 0, sizeof(LnFrag) * (size_t)n, s));
+        LN_CK(hipMemsetAsync(Lb->mir, 0, sizeof(long long) * (size_t)(n + 3), s));
+        LN_CK(hipMemsetAsync(Lb->mirbad, 0, sizeof(int) * (size_t)(n + 3), s));
+        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, Lb->cnt, Lb->err);
+        LN_CK(hipGetLastError());
+        size_t tb = Lb->tmp_bytes;
+        LN_CK(hipcub::DeviceScan::ExclusiveSum(Lb->tmp, tb, Lb->cnt, Lb->base, n + 3, s));
+        k_ln_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, min_frags, h->stat_frag, h->d_sub_ids, Lb->cnt, Lb->base, Lb->slot, Lb->lab, Lb->fr,
+                                                     Lb->sub, Lb->ctg, &Lb->ctr[2], Lb->err);
+        LN_CK(hipGetLastError());
+        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        LN_CK(hipStreamSynchronize(s));
+        if (err) break;   // (a corrupt layout: the slots and the sub-fragment records are not to be trusted, nothing reads them)
+        // ---- count pass: an upper bound of the distinct keys
+        const long long waves = (h->nnz + 63) / 64;
+        const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
+        if (h->nnz > 0) {
+            k_ln_nnz<true><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, Lb->sub, h->stat_frag, Lb->ctg, h->nfpb, h->par, quirk, 0, nullptr,
+                                              nullptr, nullptr, nullptr, nullptr, nullptr, &Lb->ctr[0], Lb->err);
+            LN_CK(hipGetLastError());
+        }
+        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        LN_CK(hipMemcpyAsync(ctr, Lb->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        LN_CK(hipStreamSynchronize(s));
+        if (err) break;
+        const unsigned long long E = 2ull * ctr[2];
+        const unsigned long long bound = std::min<unsigned long long>(ctr[0], E * (E > 0 ? E - 1 : 0) / 2);
+        const unsigned long long cap = bound + bound / 2 + 64;       // (load factor <= 2/3)
+        const unsigned long long L = bound + 1;
+        // device memory: the table (key, q, contacts, flags, selection byte per slot), the per-link arrays sized to the bound (keys x2,
+        // indices x2, q, contacts, groups x2, bad, ends x2, status) and the hipCUB temp storage of the selection, the sort and the scan
+        unsigned long long need = cap * (unsigned long long)(8 + 8 + 8 + 4 + 1) + L * (unsigned long long)(8 * 2 + 4 * 2 + 8 + 8 + 8 * 2 + 4 + 4 * 2 + 1);
+        size_t b_sel = 0, b_sort = 0, b_scan = 0;
+        if (cap < (unsigned long long)INT_MAX) {
+            LN_CK(hipcub::DeviceSelect::Flagged(nullptr, b_sel, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr, (int*)nullptr,
+                                                (unsigned long long*)nullptr, (int)cap, s));
+            LN_CK(hipcub::DeviceRadixSort::SortPairs(nullptr, b_sort, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                                     (const int*)nullptr, (int*)nullptr, (int)L, 0, 64, s));
+            LN_CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b_scan, (const long long*)nullptr, (long long*)nullptr, (int)L, s));
+        }
+        const size_t tneed = std::max(b_sel, std::max(b_sort, b_scan));
+        need += tneed;
+        if (cap >= (unsigned long long)INT_MAX || need > (unsigned long long)GRAAL_LINKS_MAX_BYTES) {
+            snprintf(msg, sizeof msg, "graal_end_links: the candidate table needs %llu bytes (%llu records counted), over the budget of %llu bytes "
+                     "(GRAAL_LINKS_MAX_BYTES): use a larger min_frags", need, ctr[0], (unsigned long long)GRAAL_LINKS_MAX_BYTES);
+            why = msg;
+            break;
+        }
+        if (cap > Lb->cap) {
+            ln_free_table(Lb);
+            LN_CK(hipMalloc(&Lb->keys, sizeof(unsigned long long) * cap));
+            LN_CK(hipMalloc(&Lb->tq, sizeof(long long) * cap));
+            LN_CK(hipMalloc(&Lb->tc, sizeof(long long) * cap));
+            LN_CK(hipMalloc(&Lb->tf, sizeof(int) * cap));
+            LN_CK(hipMalloc(&Lb->tsel, cap));
+            Lb->cap = cap;
+        }
+        // (the table is used at size `cap`, whatever its allocation: the probe sequence depends on it)
+        LN_CK(hipMemsetAsync(Lb->keys, 0xff, sizeof(unsigned long long) * cap, s));
+        LN_CK(hipMemsetAsync(Lb->tq, 0, sizeof(long long) * cap, s));
+        LN_CK(hipMemsetAsync(Lb->tc, 0, sizeof(long long) * cap, s));
+        LN_CK(hipMemsetAsync(Lb->tf, 0, sizeof(int) * cap, s));
+        if (L > Lb->lcap) {
+            ln_free_links(Lb);
+            LN_CK(hipMalloc(&Lb->ko, sizeof(unsigned long long) * L)); LN_CK(hipMalloc(&Lb->ks, sizeof(unsigned long long) * L));
+            LN_CK(hipMalloc(&Lb->vo, sizeof(int) * L)); LN_CK(hipMalloc(&Lb->vs, sizeof(int) * L));
+            LN_CK(hipMalloc(&Lb->q, sizeof(long long) * L)); LN_CK(hipMalloc(&Lb->c, sizeof(long long) * L));
+            LN_CK(hipMalloc(&Lb->ch, sizeof(long long) * L)); LN_CK(hipMalloc(&Lb->choff, sizeof(long long) * L));
+            LN_CK(hipMalloc(&Lb->bad, sizeof(int) * L));
+            LN_CK(hipMalloc(&Lb->ea, sizeof(int) * L)); LN_CK(hipMalloc(&Lb->eb, sizeof(int) * L)); LN_CK(hipMalloc(&Lb->st, L));
+            Lb->lcap = L;
+        }
+        if (tneed > Lb->stmp_bytes) {
+            if (Lb->stmp) (void)hipFree(Lb->stmp);
+            Lb->stmp = nullptr; Lb->stmp_bytes = 0;
+            LN_CK(hipMalloc(&Lb->stmp, tneed));
+            Lb->stmp_bytes = tneed;
+        }
+        // ---- insert pass, selection of the listed slots, sort by key
+        if (h->nnz > 0) {
+            k_ln_nnz<false><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, Lb->sub, h->stat_frag, Lb->ctg, h->nfpb, h->par, quirk, cap, Lb->keys,
+                                               Lb->tq, Lb->tc, Lb->tf, Lb->mir, Lb->mirbad, &Lb->ctr[0], Lb->err);
+            LN_CK(hipGetLastError());
+        }
+        k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(Lb->keys, Lb->tf, (long long)cap, Lb->tsel);
+        LN_CK(hipGetLastError());
+        tb = Lb->stmp_bytes;
+        LN_CK(hipcub::DeviceSelect::Flagged(Lb->stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)Lb->tsel, Lb->vo, &Lb->ctr[1],
+                                            (int)cap, s));
+        LN_CK(hipMemcpyAsync(ctr, Lb->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        LN_CK(hipStreamSynchronize(s));
+        if (err) break;
+        m = (long long)ctr[1];
+        if (m == 0) break;
+        k_ln_keys<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->keys, Lb->vo, Lb->ko);
+        LN_CK(hipGetLastError());
+        tb = Lb->stmp_bytes;
+        LN_CK(hipcub::DeviceRadixSort::SortPairs(Lb->stmp, tb, Lb->ko, Lb->ks, Lb->vo, Lb->vs, (int)m, 0, 64, s));
+        k_ln_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->ks, Lb->vs, Lb->tq, Lb->tc, Lb->tf, Lb->lab, Lb->ctg, Lb->q, Lb->c, Lb->bad, Lb->ch,
+                                                       Lb->ea, Lb->eb);
+        LN_CK(hipGetLastError());
+        tb = Lb->stmp_bytes;
+        LN_CK(hipcub::DeviceScan::ExclusiveSum(Lb->stmp, tb, Lb->ch, Lb->choff, (int)m, s));
+        long long last[2] = {0, 0};
+        LN_CK(hipMemcpyAsync(&last[0], Lb->choff + (m - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
+        LN_CK(hipMemcpyAsync(&last[1], Lb->ch + (m - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
+        LN_CK(hipStreamSynchronize(s));
+        const long long groups = last[0] + last[1];
+        if ((groups + 3) / 4 > (long long)INT_MAX) {
+            snprintf(msg, sizeof msg, "graal_end_links: %lld wave groups exceed one launch: use a larger min_frags", groups);
+            why = msg;
+            break;
+        }
+        // ---- the mass pass, the quirk's passes, the result
+        if (groups > 0) {
+            k_ln_mass<<<(unsigned)((groups + 3) / 4), 256, 0, s>>>(m, groups, Lb->choff, Lb->ch, Lb->ea, Lb->eb, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par,
+                                                                 quirk, reach_bp(h), Lb->q, Lb->bad);
+            LN_CK(hipGetLastError());
+        }
+        if (mq) {
+            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, Lb->slot, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par, Lb->mir, Lb->mirbad);
+            LN_CK(hipGetLastError());
+            if (groups > 0)
+                k_ln_quirk<<<(unsigned)((groups + 3) / 4), 256, 0, s>>>(m, groups, Lb->choff, Lb->ch, Lb->ea, Lb->eb, Lb->lab, Lb->ctg, Lb->fr, h->nfpb,
+                                                                      h->par, reach_bp(h), Lb->q, Lb->bad);
+            LN_CK(hipGetLastError());
+        }
+        k_ln_out<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->ea, Lb->eb, Lb->lab, Lb->mir, Lb->mirbad, mq, Lb->q, Lb->bad, Lb->st);
+        LN_CK(hipGetLastError());
+        LN_CK(hipStreamSynchronize(s));
+#undef LN_CK
+    } while (false);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    if (why) { h->err = why; return GRAAL_E_UNSUPPORTED; }
+    if (err) {
+        snprintf(msg, sizeof msg, "graal_end_links: corrupt layout (contig labels or positions out of range, flags %u)", err);
+        h->err = msg;
+        return GRAAL_E_STATE;
+    }
+    Lb->n_links = m;
+    *n_links = m;
+    return GRAAL_OK;
+}
+
+int graal_end_links_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, int64_t* q, int64_t* contacts, uint8_t* status, int64_t cap)
+{
+    if (!h || !end_a || !end_b || !q || !contacts || !status) return GRAAL_E_ARG;
+    LnBuf* Lb = h->ln;
+    if (!Lb || Lb->n_links < 0) return fail(h, GRAAL_E_STATE, "graal_end_links_fetch: call graal_end_links first");
+    const long long m = Lb->n_links;
+    if (cap < m) return fail(h, GRAAL_E_ARG, "graal_end_links_fetch: cap is smaller than the number of links");
+    if (m == 0) return GRAAL_OK;
+    CK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    CK(hipMemcpyAsync(end_a, Lb->ea, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(end_b, Lb->eb, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(q, Lb->q, sizeof(long long) * (size_t)m, hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(contacts, Lb->c, sizeof(long long) * (size_t)m, hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(status, Lb->st, (size_t)m, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    return GRAAL_OK;
+}
+
+} // extern "C"

@@ -51,11 +51,12 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_upload_subfrags", "graal_upload_repeats", "graal_upload_contacts", "graal_upload_contacts_f32", "graal_upload_frags", "graal_download_frags",
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
-           "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores",
+           "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
 STEP_DONE, STEP_PAUSED, STEP_FALLBACK, STEP_SELECT = 0, 1, 2, 3
 JUNCTION_VALID, JUNCTION_END, JUNCTION_CIRCULAR, JUNCTION_NONFINITE = 0, 1, 2, 3   # graal_junction_scores' status bytes
+LINK_VALID, LINK_NONFINITE = 0, 1   # graal_end_links' status bytes
 STEPS_ROW = 10   # GRAAL_STEPS_ROW: doubles per step in graal_steps' rows
 
 
@@ -127,6 +128,8 @@ def load():
         L.graal_simulate_contacts.argtypes = [ctypes.c_void_p, ctypes.c_uint64, _i64p]
         L.graal_simulate_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i32p, ctypes.c_int64]
         L.graal_junction_scores.argtypes = [ctypes.c_void_p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
+        L.graal_end_links.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i64p]
+        L.graal_end_links_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_finisher.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_mode.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -384,6 +387,30 @@ class Engine:
         self._ck(self._L.graal_junction_scores(self._h, q.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
                  "graal_junction_scores")
         return q, st
+
+    def end_links(self, min_frags=1):
+        """graal_end_links: the pairs of contig ends the contacts support, as numpy columns (end_a int32, end_b int32, score float64,
+        contacts int64, status uint8), sorted by (end_a, end_b).  end = 2 * fragment + side (0: the contig's head, 1: its tail);
+        score = logL(the canonical join of the two ends) - logL(layout) in the exact arithmetic, NaN unless status is LINK_VALID.
+        Both contigs linear with >= min_frags fragments.  Needs sub-fragments, parameters, fragments and contacts; one rank, no
+        repeated bins.  Leaves the step state alone."""
+        a, b, q, c, st = self.end_links_q(min_frags)
+        return a, b, np.where(st == LINK_VALID, q.astype(np.float64) / Q_SCALE, np.nan), c, st
+
+    def end_links_q(self, min_frags=1):
+        """The same with the score as int64 Q: (end_a, end_b, q, contacts, status)."""
+        m = ctypes.c_int64(0)
+        self._ck(self._L.graal_end_links(self._h, int(min_frags), ctypes.byref(m)), "graal_end_links")
+        m = int(m.value)
+        a = np.zeros(m, dtype=np.int32)
+        b = np.zeros(m, dtype=np.int32)
+        q = np.zeros(m, dtype=np.int64)
+        c = np.zeros(m, dtype=np.int64)
+        st = np.zeros(m, dtype=np.uint8)
+        self._ck(self._L.graal_end_links_fetch(self._h, a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p), q.ctypes.data_as(_i64p),
+                                               c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), m),
+                 "graal_end_links_fetch")
+        return a, b, q, c, st
 
     def genome_distance_half_units(self):
         v = ctypes.c_int64(0)

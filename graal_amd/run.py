@@ -45,6 +45,10 @@ def main(argv=None):
     ap.add_argument("--param", type=float, nargs=8, default=None, help="param_simu to run with instead of the fit's")
     ap.add_argument("--junctions", action="store_true", help="write junctions.tsv into the output folder: every join of the final layout "
                                                              "with the log-likelihood it carries (graal_amd.junctions)")
+    ap.add_argument("--links", action="store_true", help="write links.tsv into the output folder: every pair of contig ends of the final "
+                                                         "layout with contacts between them, with the log-likelihood their join would add "
+                                                         "(graal_amd.links)")
+    ap.add_argument("--links-min-frags", type=int, default=1, help="with --links: only contigs of at least this many fragments (default 1)")
     args = ap.parse_args(argv)
     if not 0 <= args.level < args.size_pyramid:
         raise SystemExit("--level must be in 0 .. size-pyramid - 1 (levels >= 1: the level below holds the observations; 0: the level itself)")
@@ -104,6 +108,9 @@ def main(argv=None):
     if args.junctions:
         from . import junctions
         junctions.write_junctions_tsv(os.path.join(out, "junctions.tsv"), junctions.junction_table(smp))
+    if args.links:
+        from . import links
+        links.write_links_tsv(os.path.join(out, "links.tsv"), links.link_table(smp, args.links_min_frags))
     n_steps = len(trace.likelihood)
     print("%d bins (%d fragments, %d sub-fragments), %d MCMC steps in %.1f s (%.0f us/step): %d contigs, logL %.6e, "
           "distance to the initial genome %.4f; traces in %s" % (inp["n_frags"], inp["n_new_frags"], inp["init_n_sub_frags"], n_steps,

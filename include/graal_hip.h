@@ -282,6 +282,34 @@ int graal_simulate_fetch(graal_ctx* h, int32_t* row, int32_t* col, int32_t* coun
 #define GRAAL_JUNCTION_NONFINITE 3
 int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status);
 
+/* End links: the likelihood each join between two contig ends would add, for every pair of ends the contacts support, in one pass
+ * (graal_amd/csrc/links.h).  An end is end = 2*f + side of a LINEAR contig: side 0 its head (position 0), side 1 its tail (position
+ * l_cont - 1), f the fragment there (a single-fragment contig has the ends 2f and 2f+1).  For ends eA < eB of DIFFERENT contigs A, B the
+ * joined layout is canonical: A oriented so that eA is its tail (reversed iff eA is a head), then B oriented so that eB is its head
+ * (reversed iff eB is a tail), positions / start_bp / ori as m_paste writes them (integer bp offsets, then the float32 centres).
+ *   L(eA, eB) = logL(joined layout) - logL(current layout)
+ * in the exact arithmetic under the current mode flags, with graal_junction_scores' roundings: pairs inside A and inside B count as
+ * unchanged; every sub-fragment pair of A x B moves from its current trans price to its joined price (a contact: ob * (ln ex_new -
+ * ln ex_trans), rounded to Q once per contact; a fragment pair's mass: -(sum of ex_new - ex_trans), rounded to Q once per fragment
+ * pair).  Under GRAAL_MODE_REF_TRANS_ACCU with bins of mixed RF counts L also holds the A x B pairs beyond the window that involve such
+ * a bin, and, for a reversed A or B, the changed trans prices of its mixed bins against every fragment outside A u B.  Positive L:
+ * the data prefer the join.  int64 sums: bit-identical from call to call and for any grid.
+ * Listed: the pairs of ends with at least one contact between A and B inside the window (sub-fragment centre distance < d_max) in the
+ * joined orientation, both contigs linear with >= min_frags (>= 1) fragments.  Any other pair of ends would score only its negative
+ * expected mass and is NOT listed.  Not covered: joining a contig's two ends (circularisation), circular contigs.
+ * graal_end_links computes the table and returns its size in *n_links; graal_end_links_fetch copies the last table out, sorted by
+ * (end_a, end_b) with end_a < end_b: q in Q, contacts = the summed count inside the window (the evidence behind the score),
+ * status GRAAL_LINK_VALID or GRAAL_LINK_NONFINITE (a term was not finite; q = 0).  cap < n_links: GRAAL_E_ARG.
+ * Needs sub-fragments, parameters, fragments and contacts.  Does not relabel and leaves the step state alone (ranked layout, carried
+ * total, a pending commit's correction, the proposal tables).  GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats), and when
+ * the candidate table would need more than GRAAL_LINKS_MAX_BYTES of device memory (the message gives the bytes needed: use a larger
+ * min_frags); GRAAL_E_STATE with an exchange or RCCL attached (one rank only: the contact part is shard-local). */
+#define GRAAL_LINK_VALID 0
+#define GRAAL_LINK_NONFINITE 1
+#define GRAAL_LINKS_MAX_BYTES (8ull << 30)
+int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links);
+int graal_end_links_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, int64_t* q, int64_t* contacts, uint8_t* status, int64_t cap);
+
 /* ---- the sampler's per-step HOST logic behind the boundary (graal_amd/csrc/host_step.h) --------------------------------
  * What cuda_lib_gl.sampler.step_max_likelihood does on the host between its launches: return_neighbours
  * (cuda_lib_gl.py:2295-2331: RandomState.choice(xk, n, p=pk, replace=False), expansion to the copies of repeated bins,
