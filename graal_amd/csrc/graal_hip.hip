@@ -4323,6 +4323,8 @@ void jn_free(JnBuf* b);
 
 struct LnBuf;                  // links.h: graal_end_links' buffers and results
 void ln_free(LnBuf* b);
+struct EdBuf;                  // edit.h: graal_edit_layout's buffers
+void ed_free(EdBuf* b);
 
 struct Ctx {
     int device = 0;
@@ -4520,6 +4522,7 @@ struct Ctx {
     SimBuf* sim = nullptr;        // graal_simulate_contacts' buffers (simulate.h; allocated by its first call)
     JnBuf* jn = nullptr;          // graal_junction_scores' buffers (junctions.h; allocated by its first call)
     LnBuf* ln = nullptr;          // graal_end_links' buffers and its last result (links.h; allocated by its first call)
+    EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
 };
 
 #define CK(call)                                                                                     \
@@ -5262,6 +5265,7 @@ void graal_destroy(graal_ctx* h)
         sim_free(h->sim); h->sim = nullptr;
         jn_free(h->jn); h->jn = nullptr;
         ln_free(h->ln); h->ln = nullptr;
+        ed_free(h->ed); h->ed = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
         if (h->h_stats) (void)hipHostFree(h->h_stats);
@@ -6759,3 +6763,4 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "simulate.h"
 #include "junctions.h"
 #include "links.h"
+#include "edit.h"

@@ -59,6 +59,10 @@ struct LnBuf {
     size_t lcap = 0;
     void* stmp = nullptr; size_t stmp_bytes = 0;
     long long n_links = -1;                                          // -1: no result to fetch
+    // graal_end_links_best: per end (2n) the best Q and partner, the mutual flag, and the mutual links compacted
+    long long* bq = nullptr; int* be = nullptr; unsigned char* bflag = nullptr; int *bsel = nullptr, *mea = nullptr, *meb = nullptr;
+    long long* mq = nullptr; size_t bcap = 0;
+    long long n_mutual = -1;                                         // -1: no result to fetch
 };
 
 void ln_free_table(LnBuf* b)
@@ -84,10 +88,17 @@ void ln_free_fixed(LnBuf* b)
     b->tmp_bytes = 0; b->n = 0; b->S = 0;
 }
 
+void ln_free_best(LnBuf* b)
+{
+    void** p[] = {(void**)&b->bq, (void**)&b->be, (void**)&b->bflag, (void**)&b->bsel, (void**)&b->mea, (void**)&b->meb, (void**)&b->mq};
+    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    b->bcap = 0;
+}
+
 void ln_free(LnBuf* b)
 {
     if (!b) return;
-    ln_free_fixed(b); ln_free_table(b); ln_free_links(b);
+    ln_free_fixed(b); ln_free_table(b); ln_free_links(b); ln_free_best(b);
     if (b->stmp) (void)hipFree(b->stmp);
     delete b;
 }
@@ -547,6 +558,159 @@ __global__ void k_ln_out(long long m, const int* __restrict__ ea, const int* __r
     q[k] = b ? 0 : v;
 }
 
+// ---- graal_end_links_best: the same scored links without the materialised output.  A wave per slot of the candidate table (unlisted
+// slots return at once) walks the groups of 8 fragments of A from eA that k_ln_mass's waves would cover, so every fragment pair gets the
+// same Q-rounded term and the int64 sums are the same; the final score stays in the table (tq), then two atomic passes per end.
+__device__ __forceinline__ bool lb_listed(const unsigned long long* __restrict__ keys, const int* __restrict__ tf, long long i)
+{
+    return keys[i] != LN_EMPTY && (tf[i] & 2);
+}
+
+__global__ __launch_bounds__(256) void k_lb_mass(long long cap, const unsigned long long* __restrict__ keys, int* __restrict__ tf,
+                                                 const int* __restrict__ lab, const LnCtg* __restrict__ ctg, const LnFrag* __restrict__ fr,
+                                                 float nfpb, Par par, int quirk, int reach_bp, long long* __restrict__ tq)
+{
+    const int lane = threadIdx.x & 63;
+    const long long W = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (W >= cap || !lb_listed(keys, tf, W)) return;                 // (wave-uniform)
+    const unsigned long long key = keys[W];
+    const int e_a = (int)(key >> 32), e_b = (int)(key & 0xffffffffull);
+    const LnCtg CA = ctg[lab[e_a >> 1]], CB = ctg[lab[e_b >> 1]];
+    const LnSide A = ln_side(CA, e_a & 1, true), B = ln_side(CB, e_b & 1, false);
+    const int jl = lane & 7;
+    long long sum = 0, nb = 0;
+    for (int g = 0; g * 8 < A.cnt; g++) {
+        const int i = g * 8 + (lane >> 3);
+        LnFrag x;
+        int gx = 0, nsx = 0;
+        bool fx = false, live = i < A.cnt;
+        if (live) {
+            x = fr[ln_walk(A, i)];
+            gx = ln_gap(A, x);
+            nsx = ln_new_start(x.start, x.len, A.lbp, A.lbp, true, A.rev);
+            fx = (x.fwd != 0) != A.rev;
+            live = gx <= reach_bp;
+        }
+        if (__ballot(live) == 0ull) break;                           // (the gap grows along the walk of A: no later group is in the window)
+        for (int j0 = 0; ; j0 += 8) {
+            const int j = j0 + jl;
+            bool in = live && j < B.cnt;
+            LnFrag y;
+            int gy = 0;
+            if (in) { y = fr[ln_walk(B, j)]; gy = ln_gap(B, y); in = (long long)gx + gy <= reach_bp; }
+            if (__ballot(in) == 0ull) break;
+            if (in) {
+                const int nsy = ln_new_start(y.start, y.len, B.lbp, A.lbp, false, B.rev);
+                const long long t = to_q_fast(ln_pair_mass(x, nsx, fx, y, nsy, (y.fwd != 0) != B.rev, nfpb, par, quirk));
+                if (t == Q_BAD) nb++; else sum -= t;
+            }
+        }
+    }
+    sum = ln_wave_sum(sum);
+    nb = ln_wave_sum(nb);
+    if (lane == 0) {                                                 // (the slot's only writer in this kernel)
+        tq[W] += sum;
+        if (nb) tf[W] |= 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lb_quirk(long long cap, const unsigned long long* __restrict__ keys, int* __restrict__ tf,
+                                                  const int* __restrict__ lab, const LnCtg* __restrict__ ctg, const LnFrag* __restrict__ fr,
+                                                  float nfpb, Par par, int reach_bp, long long* __restrict__ tq)
+{
+    const int lane = threadIdx.x & 63;
+    const long long W = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (W >= cap || !lb_listed(keys, tf, W)) return;
+    const unsigned long long key = keys[W];
+    const int e_a = (int)(key >> 32), e_b = (int)(key & 0xffffffffull);
+    const LnCtg CA = ctg[lab[e_a >> 1]], CB = ctg[lab[e_b >> 1]];
+    if (CA.nmix == 0 && CB.nmix == 0) return;
+    const LnSide A = ln_side(CA, e_a & 1, true), B = ln_side(CB, e_b & 1, false);
+    const int jl = lane & 7;
+    long long sum = 0, nb = 0;
+    for (int g = 0; g * 8 < A.cnt; g++) {
+        const int i = g * 8 + (lane >> 3);
+        if (i >= A.cnt) continue;
+        const LnFrag x = fr[ln_walk(A, i)];
+        const int gx = ln_gap(A, x);
+        const bool mx = !stat_uniform(x.st);
+        for (int j = jl; j < B.cnt; j += 8) {
+            const LnFrag y = fr[ln_walk(B, j)];
+            if (!mx && stat_uniform(y.st)) continue;
+            ln_quirk_pair(x, y, (long long)gx + ln_gap(B, y) > reach_bp, A.rev, B.rev, nfpb, par, sum, nb);
+        }
+    }
+    sum = ln_wave_sum(sum);
+    nb = ln_wave_sum(nb);
+    if (lane == 0) {
+        tq[W] += sum;
+        if (nb) tf[W] |= 1;
+    }
+}
+
+__global__ void k_lb_init(long long n2, long long* __restrict__ bq, int* __restrict__ be)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n2) { bq[e] = LLONG_MIN; be[e] = INT_MAX; }
+}
+
+// k_ln_out per slot: the final Q (mirrors of the reversed contigs added) stays in tq, bit 4 of tf marks a valid link; then the highest Q per end
+__global__ void k_lb_out(long long cap, const unsigned long long* __restrict__ keys, int* __restrict__ tf, const int* __restrict__ lab,
+                         const long long* __restrict__ mir, const int* __restrict__ mirbad, int quirk, long long* __restrict__ tq,
+                         long long* __restrict__ bq)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap || !lb_listed(keys, tf, i)) return;
+    const int ea = (int)(keys[i] >> 32), eb = (int)(keys[i] & 0xffffffffull);
+    long long v = tq[i];
+    int b = tf[i] & 1;
+    if (quirk) {
+        const int ca = lab[ea >> 1], cb = lab[eb >> 1];
+        if ((ea & 1) == 0) { v += mir[ca]; b += mirbad[ca]; }
+        if ((eb & 1) == 1) { v += mir[cb]; b += mirbad[cb]; }
+    }
+    if (b) return;
+    tq[i] = v;
+    tf[i] |= 4;
+    atomicMax(&bq[ea], v);
+    atomicMax(&bq[eb], v);
+}
+
+// the lowest partner among the valid links that reach an end's highest Q
+__global__ void k_lb_arg(long long cap, const unsigned long long* __restrict__ keys, const int* __restrict__ tf, const long long* __restrict__ tq,
+                         const long long* __restrict__ bq, int* __restrict__ be)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap || keys[i] == LN_EMPTY || !(tf[i] & 4)) return;
+    const int ea = (int)(keys[i] >> 32), eb = (int)(keys[i] & 0xffffffffull);
+    if (tq[i] == bq[ea]) atomicMin(&be[ea], eb);
+    if (tq[i] == bq[eb]) atomicMin(&be[eb], ea);
+}
+
+__global__ void k_lb_norm(long long n2, long long* __restrict__ bq, int* __restrict__ be)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n2 && be[e] == INT_MAX) { be[e] = -1; bq[e] = 0; }
+}
+
+// end e heads a mutual link when its best partner p > e has e as ITS best partner, with Q > 0
+__global__ void k_lb_flag(long long n2, const long long* __restrict__ bq, const int* __restrict__ be, unsigned char* __restrict__ flag)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n2) return;
+    const int p = be[e];
+    flag[e] = (p > e && p < n2 && be[p] == (int)e && bq[e] > 0) ? 1 : 0;
+}
+
+__global__ void k_lb_gather(long long m, const int* __restrict__ sel, const long long* __restrict__ bq, const int* __restrict__ be,
+                            int* __restrict__ ea, int* __restrict__ eb, long long* __restrict__ q)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const int e = sel[k];
+    ea[k] = e; eb[k] = be[e]; q[k] = bq[e];
+}
+
 } // namespace
 
 extern "C" {
@@ -763,6 +927,194 @@ int graal_end_links_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, int64_t*
     CK(hipMemcpyAsync(q, Lb->q, sizeof(long long) * (size_t)m, hipMemcpyDeviceToHost, s));
     CK(hipMemcpyAsync(contacts, Lb->c, sizeof(long long) * (size_t)m, hipMemcpyDeviceToHost, s));
     CK(hipMemcpyAsync(status, Lb->st, (size_t)m, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    return GRAAL_OK;
+}
+
+int graal_end_links_best(graal_ctx* h, int32_t min_frags, int32_t* best_end, int64_t* best_q, int64_t* n_mutual)
+{
+    if (!h || !best_end || !best_q || !n_mutual) return GRAAL_E_ARG;
+    if (min_frags < 1) return fail(h, GRAAL_E_ARG, "graal_end_links_best: min_frags must be >= 1");
+    if (!(h->have_sub && h->have_par && h->have_frags && h->have_contacts))
+        return fail(h, GRAAL_E_STATE, "graal_end_links_best: upload sub-fragments, parameters, fragments and contacts first");
+    if (h->has_rep) return fail(h, GRAAL_E_UNSUPPORTED, "graal_end_links_best: bins with several copies (graal_upload_repeats) are not supported");
+    if (h->x_host || h->nccl_comm) return fail(h, GRAAL_E_STATE, "graal_end_links_best: one rank only (an exchange or RCCL is attached)");
+    CK(hipSetDevice(h->device));
+    *n_mutual = 0;
+    const int n = h->n, S = h->n_sub_total;
+    const long long n2 = 2ll * n;
+    if (!h->ln) h->ln = new LnBuf();
+    LnBuf* Lb = h->ln;
+    Lb->n_mutual = -1;
+    if (n < 1) { Lb->n_mutual = 0; return GRAAL_OK; }
+    hipStream_t s = h->stream;
+    if (Lb->n != n || Lb->S != S) {   // (graal_end_links' fixed buffers, allocated the same way)
+        ln_free_fixed(Lb);
+        CK(hipMalloc(&Lb->cnt, sizeof(int) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->base, sizeof(int) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->slot, sizeof(int) * (size_t)n));
+        CK(hipMalloc(&Lb->lab, sizeof(int) * (size_t)n));
+        CK(hipMalloc(&Lb->fr, sizeof(LnFrag) * (size_t)n));
+        CK(hipMalloc(&Lb->sub, sizeof(LnSub) * (size_t)std::max(S, 1)));
+        CK(hipMalloc(&Lb->ctg, sizeof(LnCtg) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->mir, sizeof(long long) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->mirbad, sizeof(int) * (size_t)(n + 3)));
+        CK(hipMalloc(&Lb->err, sizeof(unsigned)));
+        CK(hipMalloc(&Lb->ctr, sizeof(unsigned long long) * 3));
+        size_t b1 = 0;
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, Lb->cnt, Lb->base, n + 3, s));
+        CK(hipMalloc(&Lb->tmp, b1));
+        Lb->tmp_bytes = b1;
+        Lb->n = n; Lb->S = S;
+    }
+    const SoaPtr sp = h->soa[h->cur];
+    const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
+    const int mq = quirk && h->n_ubins > 0;
+    int rc = GRAAL_OK;
+    unsigned err = 0;
+    unsigned long long ctr[3] = {0, 0, 0};
+    long long m = 0;
+    const char* why = nullptr;
+    char msg[320];
+    do {
+#define LN_CK(call) { const hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = hipGetErrorString(e_); rc = GRAAL_E_HIP; break; } }
+        // ---- records, as graal_end_links
+        LN_CK(hipMemsetAsync(Lb->err, 0, sizeof(unsigned), s));
+        LN_CK(hipMemsetAsync(Lb->ctr, 0, sizeof(unsigned long long) * 3, s));
+        LN_CK(hipMemsetAsync(Lb->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
+        LN_CK(hipMemsetAsync(Lb->ctg, 0, sizeof(LnCtg) * (size_t)(n + 3), s));
+        LN_CK(hipMemsetAsync(Lb->fr, 0, sizeof(LnFrag) * (size_t)n, s));
+        LN_CK(hipMemsetAsync(Lb->mir, 0, sizeof(long long) * (size_t)(n + 3), s));
+        LN_CK(hipMemsetAsync(Lb->mirbad, 0, sizeof(int) * (size_t)(n + 3), s));
+        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, Lb->cnt, Lb->err);
+        LN_CK(hipGetLastError());
+        size_t tb = Lb->tmp_bytes;
+        LN_CK(hipcub::DeviceScan::ExclusiveSum(Lb->tmp, tb, Lb->cnt, Lb->base, n + 3, s));
+        k_ln_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, min_frags, h->stat_frag, h->d_sub_ids, Lb->cnt, Lb->base, Lb->slot, Lb->lab, Lb->fr,
+                                                     Lb->sub, Lb->ctg, &Lb->ctr[2], Lb->err);
+        LN_CK(hipGetLastError());
+        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        LN_CK(hipStreamSynchronize(s));
+        if (err) break;
+        // ---- count pass
+        const long long waves = (h->nnz + 63) / 64;
+        const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
+        if (h->nnz > 0) {
+            k_ln_nnz<true><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, Lb->sub, h->stat_frag, Lb->ctg, h->nfpb, h->par, quirk, 0, nullptr,
+                                              nullptr, nullptr, nullptr, nullptr, nullptr, &Lb->ctr[0], Lb->err);
+            LN_CK(hipGetLastError());
+        }
+        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        LN_CK(hipMemcpyAsync(ctr, Lb->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        LN_CK(hipStreamSynchronize(s));
+        if (err) break;
+        const unsigned long long E = 2ull * ctr[2];
+        const unsigned long long bound = std::min<unsigned long long>(ctr[0], E * (E > 0 ? E - 1 : 0) / 2);
+        const unsigned long long cap = bound + bound / 2 + 64;
+        // device memory: the table (key, q, contacts, flags, selection byte per slot), the per-end arrays (best q, best partner, flag,
+        // selected end, mutual end_a / end_b / q) and the hipCUB temp storage of the selection over the ends -- no per-link arrays
+        unsigned long long need = cap * (unsigned long long)(8 + 8 + 8 + 4 + 1) + (unsigned long long)n2 * (8 + 4 + 1 + 4 + 4 + 4 + 8);
+        size_t b_sel = 0;
+        LN_CK(hipcub::DeviceSelect::Flagged(nullptr, b_sel, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr, (int*)nullptr,
+                                            (unsigned long long*)nullptr, (int)n2, s));
+        need += b_sel;
+        if (cap >= (unsigned long long)INT_MAX || (cap + 3) / 4 >= (unsigned long long)INT_MAX || need > (unsigned long long)GRAAL_LINKS_MAX_BYTES) {
+            snprintf(msg, sizeof msg, "graal_end_links_best: the candidate table needs %llu bytes (%llu records counted), over the budget of %llu "
+                     "bytes (GRAAL_LINKS_MAX_BYTES): use a larger min_frags", need, ctr[0], (unsigned long long)GRAAL_LINKS_MAX_BYTES);
+            why = msg;
+            break;
+        }
+        if (cap > Lb->cap) {
+            ln_free_table(Lb);
+            LN_CK(hipMalloc(&Lb->keys, sizeof(unsigned long long) * cap));
+            LN_CK(hipMalloc(&Lb->tq, sizeof(long long) * cap));
+            LN_CK(hipMalloc(&Lb->tc, sizeof(long long) * cap));
+            LN_CK(hipMalloc(&Lb->tf, sizeof(int) * cap));
+            LN_CK(hipMalloc(&Lb->tsel, cap));
+            Lb->cap = cap;
+        }
+        if ((size_t)n2 > Lb->bcap) {
+            ln_free_best(Lb);
+            LN_CK(hipMalloc(&Lb->bq, sizeof(long long) * (size_t)n2)); LN_CK(hipMalloc(&Lb->be, sizeof(int) * (size_t)n2));
+            LN_CK(hipMalloc(&Lb->bflag, (size_t)n2)); LN_CK(hipMalloc(&Lb->bsel, sizeof(int) * (size_t)n2));
+            LN_CK(hipMalloc(&Lb->mea, sizeof(int) * (size_t)n2)); LN_CK(hipMalloc(&Lb->meb, sizeof(int) * (size_t)n2));
+            LN_CK(hipMalloc(&Lb->mq, sizeof(long long) * (size_t)n2));
+            Lb->bcap = (size_t)n2;
+        }
+        if (b_sel > Lb->stmp_bytes) {
+            if (Lb->stmp) (void)hipFree(Lb->stmp);
+            Lb->stmp = nullptr; Lb->stmp_bytes = 0;
+            LN_CK(hipMalloc(&Lb->stmp, b_sel));
+            Lb->stmp_bytes = b_sel;
+        }
+        LN_CK(hipMemsetAsync(Lb->keys, 0xff, sizeof(unsigned long long) * cap, s));
+        LN_CK(hipMemsetAsync(Lb->tq, 0, sizeof(long long) * cap, s));
+        LN_CK(hipMemsetAsync(Lb->tc, 0, sizeof(long long) * cap, s));
+        LN_CK(hipMemsetAsync(Lb->tf, 0, sizeof(int) * cap, s));
+        // ---- insert pass, then the scores in place: mass, the quirk's passes, mirrors and status
+        if (h->nnz > 0) {
+            k_ln_nnz<false><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, Lb->sub, h->stat_frag, Lb->ctg, h->nfpb, h->par, quirk, cap, Lb->keys,
+                                               Lb->tq, Lb->tc, Lb->tf, Lb->mir, Lb->mirbad, &Lb->ctr[0], Lb->err);
+            LN_CK(hipGetLastError());
+        }
+        const unsigned wblocks = (unsigned)((cap + 3) / 4);          // a wave per slot, 4 waves per block
+        k_lb_mass<<<wblocks, 256, 0, s>>>((long long)cap, Lb->keys, Lb->tf, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par, quirk, reach_bp(h), Lb->tq);
+        LN_CK(hipGetLastError());
+        if (mq) {
+            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, Lb->slot, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par, Lb->mir, Lb->mirbad);
+            LN_CK(hipGetLastError());
+            k_lb_quirk<<<wblocks, 256, 0, s>>>((long long)cap, Lb->keys, Lb->tf, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par, reach_bp(h), Lb->tq);
+            LN_CK(hipGetLastError());
+        }
+        // ---- per end: the highest Q, then the lowest partner that reaches it, then the mutual links
+        k_lb_init<<<blocks_for(n2, 256), 256, 0, s>>>(n2, Lb->bq, Lb->be);
+        k_lb_out<<<blocks_for((long long)cap, 256), 256, 0, s>>>((long long)cap, Lb->keys, Lb->tf, Lb->lab, Lb->mir, Lb->mirbad, mq, Lb->tq, Lb->bq);
+        k_lb_arg<<<blocks_for((long long)cap, 256), 256, 0, s>>>((long long)cap, Lb->keys, Lb->tf, Lb->tq, Lb->bq, Lb->be);
+        k_lb_norm<<<blocks_for(n2, 256), 256, 0, s>>>(n2, Lb->bq, Lb->be);
+        k_lb_flag<<<blocks_for(n2, 256), 256, 0, s>>>(n2, Lb->bq, Lb->be, Lb->bflag);
+        LN_CK(hipGetLastError());
+        tb = Lb->stmp_bytes;
+        LN_CK(hipcub::DeviceSelect::Flagged(Lb->stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)Lb->bflag, Lb->bsel,
+                                            &Lb->ctr[1], (int)n2, s));
+        LN_CK(hipMemcpyAsync(ctr, Lb->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        LN_CK(hipStreamSynchronize(s));
+        if (err) break;
+        m = (long long)ctr[1];
+        if (m > 0) {
+            k_lb_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->bsel, Lb->bq, Lb->be, Lb->mea, Lb->meb, Lb->mq);
+            LN_CK(hipGetLastError());
+        }
+        LN_CK(hipMemcpyAsync(best_end, Lb->be, sizeof(int) * (size_t)n2, hipMemcpyDeviceToHost, s));
+        LN_CK(hipMemcpyAsync(best_q, Lb->bq, sizeof(long long) * (size_t)n2, hipMemcpyDeviceToHost, s));
+        LN_CK(hipStreamSynchronize(s));
+#undef LN_CK
+    } while (false);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    if (why) { h->err = why; return GRAAL_E_UNSUPPORTED; }
+    if (err) {
+        snprintf(msg, sizeof msg, "graal_end_links_best: corrupt layout (contig labels or positions out of range, flags %u)", err);
+        h->err = msg;
+        return GRAAL_E_STATE;
+    }
+    Lb->n_mutual = m;
+    *n_mutual = m;
+    return GRAAL_OK;
+}
+
+int graal_end_links_mutual_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, int64_t* q, int64_t cap)
+{
+    if (!h || !end_a || !end_b || !q) return GRAAL_E_ARG;
+    LnBuf* Lb = h->ln;
+    if (!Lb || Lb->n_mutual < 0) return fail(h, GRAAL_E_STATE, "graal_end_links_mutual_fetch: call graal_end_links_best first");
+    const long long m = Lb->n_mutual;
+    if (cap < m) return fail(h, GRAAL_E_ARG, "graal_end_links_mutual_fetch: cap is smaller than the number of mutual links");
+    if (m == 0) return GRAAL_OK;
+    CK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    CK(hipMemcpyAsync(end_a, Lb->mea, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(end_b, Lb->meb, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(q, Lb->mq, sizeof(long long) * (size_t)m, hipMemcpyDeviceToHost, s));
     CK(hipStreamSynchronize(s));
     return GRAAL_OK;
 }

@@ -52,11 +52,14 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
+           "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
 STEP_DONE, STEP_PAUSED, STEP_FALLBACK, STEP_SELECT = 0, 1, 2, 3
 JUNCTION_VALID, JUNCTION_END, JUNCTION_CIRCULAR, JUNCTION_NONFINITE = 0, 1, 2, 3   # graal_junction_scores' status bytes
 LINK_VALID, LINK_NONFINITE = 0, 1   # graal_end_links' status bytes
+# graal_edit_layout's status words
+EDIT_OK, EDIT_BAD_CUT, EDIT_DUP_CUT, EDIT_BAD_END, EDIT_CIRCULAR, EDIT_END_TWICE, EDIT_SAME_CONTIG, EDIT_CYCLE = range(8)
 STEPS_ROW = 10   # GRAAL_STEPS_ROW: doubles per step in graal_steps' rows
 
 
@@ -130,6 +133,9 @@ def load():
         L.graal_junction_scores.argtypes = [ctypes.c_void_p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
         L.graal_end_links.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i64p]
         L.graal_end_links_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
+        L.graal_end_links_best.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i64p, _i64p]
+        L.graal_end_links_mutual_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i64p, ctypes.c_int64]
+        L.graal_edit_layout.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, ctypes.c_int32, _i32p, _i32p, _i32p]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_finisher.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_mode.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -411,6 +417,44 @@ class Engine:
                                                c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), m),
                  "graal_end_links_fetch")
         return a, b, q, c, st
+
+    def end_links_best(self, min_frags=1):
+        """graal_end_links_best: every end's best partner, and the mutual-best links, without copying the link table out.
+        Returns (best_end int32[2n], best_q int64[2n], mutual) indexed by end = 2 * fragment + side; best_end -1 (and best_q 0) where an
+        end has no valid link.  mutual = (end_a int32, end_b int32, q int64), sorted by (end_a, end_b): the links whose ends are each
+        other's best partner with Q > 0.  Scores in Q (divide by Q_SCALE).  Same preconditions and refusals as end_links."""
+        n2 = 2 * int(self.n)
+        be = np.zeros(n2, dtype=np.int32)
+        bq = np.zeros(n2, dtype=np.int64)
+        m = ctypes.c_int64(0)
+        self._ck(self._L.graal_end_links_best(self._h, int(min_frags), be.ctypes.data_as(_i32p), bq.ctypes.data_as(_i64p), ctypes.byref(m)),
+                 "graal_end_links_best")
+        m = int(m.value)
+        a = np.zeros(m, dtype=np.int32)
+        b = np.zeros(m, dtype=np.int32)
+        q = np.zeros(m, dtype=np.int64)
+        self._ck(self._L.graal_end_links_mutual_fetch(self._h, a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p), q.ctypes.data_as(_i64p), m),
+                 "graal_end_links_mutual_fetch")
+        return be, bq, (a, b, q)
+
+    def edit_layout(self, cuts=(), joins=()):
+        """graal_edit_layout: cut the junction after every fragment of `cuts`, then apply `joins` (pairs of ends, end = 2 * fragment +
+        side, of the layout after the cuts) in one call; see include/graal_hip.h for the canonical result.  Returns the status array
+        (int32[len(cuts) + len(joins)], EDIT_OK everywhere).  A refused edit raises GraalError (layout unchanged) with the status array
+        as its .status attribute.  Afterwards the engine is as after upload_frags of the new layout."""
+        c = _c(np.asarray(cuts, dtype=np.int64).reshape(-1), np.int32)
+        j = np.asarray(joins, dtype=np.int64).reshape(-1, 2)
+        a, b = _c(j[:, 0], np.int32), _c(j[:, 1], np.int32)
+        st = np.zeros(len(c) + len(a), dtype=np.int32)
+        rc = self._L.graal_edit_layout(self._h, len(c), c.ctypes.data_as(_i32p), len(a), a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p),
+                                       st.ctypes.data_as(_i32p))
+        if rc != 0:
+            try:
+                self._ck(rc, "graal_edit_layout")
+            except GraalError as err:
+                err.status, err.code = st, rc
+                raise
+        return st
 
     def genome_distance_half_units(self):
         v = ctypes.c_int64(0)

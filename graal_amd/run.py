@@ -49,6 +49,12 @@ def main(argv=None):
                                                          "layout with contacts between them, with the log-likelihood their join would add "
                                                          "(graal_amd.links)")
     ap.add_argument("--links-min-frags", type=int, default=1, help="with --links: only contigs of at least this many fragments (default 1)")
+    ap.add_argument("--scaffold", action="store_true", help="after the explode and before the MCMC, join mutual-best contig ends round by "
+                                                            "round (graal_amd.scaffold); writes scaffold.tsv")
+    ap.add_argument("--scaffold-min-score", type=float, default=0.0, help="with --scaffold: only joins scoring above this (default 0)")
+    ap.add_argument("--polish", action="store_true", help="before the outputs, cut the final layout's junctions scoring below "
+                                                          "--polish-cut-below and rejoin the pieces (graal_amd.scaffold); writes polish.tsv")
+    ap.add_argument("--polish-cut-below", type=float, default=0.0, help="with --polish: the junction score below which a join is cut (default 0)")
     args = ap.parse_args(argv)
     if not 0 <= args.level < args.size_pyramid:
         raise SystemExit("--level must be in 0 .. size-pyramid - 1 (levels >= 1: the level below holds the observations; 0: the level itself)")
@@ -96,10 +102,20 @@ def main(argv=None):
     os.makedirs(out, exist_ok=True)
     images = (os.path.join(out, "pre_simu.tiff"), os.path.join(out, "post_em.tiff")) if args.images else None
     t0 = time.perf_counter()
-    trace = em.run_em(smp, args.cycles, args.neighbours, rng=rng, sample_param=args.sample_params, scrambled=not args.no_explode,
+    scrambled = not args.no_explode
+    if args.scaffold:
+        from . import scaffold
+        if scrambled:
+            smp.explode_genome()
+        scaffold.write_scaffold_tsv(os.path.join(out, "scaffold.tsv"), scaffold.scaffold(smp, min_score=args.scaffold_min_score))
+        scrambled = False
+    trace = em.run_em(smp, args.cycles, args.neighbours, rng=rng, sample_param=args.sample_params, scrambled=scrambled,
                       matrix_files=images)
     dt = time.perf_counter() - t0
     em.save_behaviour_to_txt(trace, out)
+    if args.polish:
+        from . import scaffold
+        scaffold.write_scaffold_tsv(os.path.join(out, "polish.tsv"), scaffold.scaffold(smp, cut_below=args.polish_cut_below))
     lev = P.get_level(args.level)
     if args.fasta:
         P.load_reference_sequence(args.fasta)

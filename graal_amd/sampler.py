@@ -759,6 +759,12 @@ class sampler(object):
         self.n_stale_paste += self.engine.explode()  # (the same loop behind the C ABI: include/graal_hip.h, graal_explode)
         self.likelihood_t = None                     # (a layout change outside step_max_likelihood, as test_copy_struct notes)
 
+    def edit_layout(self, cuts=(), joins=()):
+        """A batch of cuts and joins on the device (Engine.edit_layout, graal_edit_layout); returns its status array."""
+        st = self.engine.edit_layout(cuts, joins)
+        self.likelihood_t = None                     # (a layout change outside step_max_likelihood, as explode_genome)
+        return st
+
     def define_repeats(self):
         """``cuda_lib_gl.py:452-473``: every copy of a duplicated bin (the original included) is a "repeat"."""
         self._black_set = set(int(x) for x in self.id_frags_blacklisted)

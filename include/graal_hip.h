@@ -310,6 +310,52 @@ int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status);
 int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links);
 int graal_end_links_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, int64_t* q, int64_t* contacts, uint8_t* status, int64_t cap);
 
+/* Best partner per end, on the device (graal_amd/csrc/links.h): the links pipeline of graal_end_links up to the scored links (same listed
+ * set, same Q values, same statuses), then a reduction per end instead of the sorted table.  For every end e (2n entries, indexed by
+ * end = 2*f + side): best_end[e] = the partner of e's valid link with the highest Q, ties towards the lower partner end (as
+ * graal_amd.links.best_links), best_q[e] = that Q; best_end[e] = -1 and best_q[e] = 0 for an end with no valid link (not an end, not
+ * eligible, or no listed link).  A link is MUTUAL when each of its ends is the other's best partner and Q > 0: *n_mutual counts them and
+ * graal_end_links_mutual_fetch copies them out sorted by (end_a, end_b), end_a < end_b (cap < n_mutual: GRAAL_E_ARG).  Only the
+ * candidate table, its per-slot scores and the per-end arrays count against GRAAL_LINKS_MAX_BYTES (no selection, no sort).  Refuses
+ * what graal_end_links refuses, with the same codes; does not relabel, leaves the step state alone, and leaves graal_end_links' last
+ * table in place for graal_end_links_fetch. */
+int graal_end_links_best(graal_ctx* h, int32_t min_frags, int32_t* best_end, int64_t* best_q, int64_t* n_mutual);
+int graal_end_links_mutual_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, int64_t* q, int64_t cap);
+
+/* A batch of cuts and joins applied to the CURRENT layout in one call (graal_amd/csrc/edit.h).  Labels must be < 2n + 4 and positions a
+ * permutation of 0 .. count - 1 per label, as graal_upload_frags accepts them.
+ * CUTS first: for every fragment f of cut_after[0 .. n_cuts), the junction after f is cut.  In a linear contig f must not be its last
+ * fragment and the right part starts after f; a circular contig (>= 2 fragments) cut at f opens into a linear contig that starts at the
+ * fragment after f (by position, the last position followed by the first).  Several cuts in one contig leave several pieces.  A piece
+ * keeps its orientation, positions count from its first fragment, start_bp from 0 (offsets from the old start_bp as m_split computes
+ * them; a ring's wrapped part adds l_cont_bp), l_cont / l_cont_bp its own, circ 0, prev / next along the piece (-1 at its ends).  The
+ * piece holding the contig's position-0 fragment keeps the contig's label; every other piece takes a fresh label max + 1, max + 2, ...
+ * (max: the largest label before the edit) in increasing order of its first fragment's index.
+ * JOINS then: (end_a[j], end_b[j]) name two ends of the layout AFTER the cuts, end = 2*f + side (0 head, 1 tail) of a linear contig, in
+ * either order.  The joins must be a matching (every end at most once; the two ends of a join on different contigs); they link contigs
+ * into chains.  A chain's order is canonical: e_min = the lowest end any join of the chain holds; the contig of e_min comes before its
+ * partner across that join, which fixes the direction of the whole chain; every contig is reversed iff the end it enters the chain
+ * through is a tail (so a single join (ea < eb) gives graal_end_links' joined layout: A reversed iff ea is a head, B iff eb is a
+ * tail).  Positions and start_bp run along the chain (a reversed contig's start_bp = its l_cont_bp - start - len_bp, then the
+ * chain offset, as m_paste writes them), ori flips for a reversed contig, prev / next follow the chain, l_cont / l_cont_bp are the
+ * chain's, circ 0, and the chain takes the LOWEST label of its contigs (after the cuts).  Contigs neither cut nor joined keep every field.
+ * status[n_cuts + n_joins]: status[i] for cut i, status[n_cuts + j] for join j, GRAAL_EDIT_OK or why it was refused; any refusal returns
+ * GRAAL_E_ARG and leaves the layout as it was.  Joins that close a cycle of contigs are refused with GRAAL_EDIT_CYCLE on every join of
+ * the cycle (breaking cycles is the caller's choice).  Afterwards the engine is in the state graal_upload_frags of the new layout leaves
+ * it in: the next graal_begin_step / graal_step relabels, the carried total and any pending commit's correction are void, and a stale-
+ * paste count a pending commit left is reported by the next graal_begin_step (the edit itself writes every field: it adds none).
+ * GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats); GRAAL_E_STATE with an exchange or RCCL attached. */
+#define GRAAL_EDIT_OK 0
+#define GRAAL_EDIT_BAD_CUT 1       /* fragment out of range, the last fragment of a linear contig, or a one-fragment ring */
+#define GRAAL_EDIT_DUP_CUT 2       /* the same fragment cut twice */
+#define GRAAL_EDIT_BAD_END 3       /* an end out of range or not an end of a contig after the cuts */
+#define GRAAL_EDIT_CIRCULAR 4      /* an end of a circular contig that no cut opens */
+#define GRAAL_EDIT_END_TWICE 5     /* an end used by two joins */
+#define GRAAL_EDIT_SAME_CONTIG 6   /* both ends on one contig (circularisation is not offered) */
+#define GRAAL_EDIT_CYCLE 7         /* the join closes a cycle of contigs */
+int graal_edit_layout(graal_ctx* h, int32_t n_cuts, const int32_t* cut_after, int32_t n_joins, const int32_t* end_a, const int32_t* end_b,
+                      int32_t* status);
+
 /* ---- the sampler's per-step HOST logic behind the boundary (graal_amd/csrc/host_step.h) --------------------------------
  * What cuda_lib_gl.sampler.step_max_likelihood does on the host between its launches: return_neighbours
  * (cuda_lib_gl.py:2295-2331: RandomState.choice(xk, n, p=pk, replace=False), expansion to the copies of repeated bins,
