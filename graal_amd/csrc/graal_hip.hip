@@ -4325,6 +4325,8 @@ struct LnBuf;                  // links.h: graal_end_links' buffers and results
 void ln_free(LnBuf* b);
 struct EdBuf;                  // edit.h: graal_edit_layout's buffers
 void ed_free(EdBuf* b);
+struct InBuf;                  // insert.h: graal_insertions' buffers and results
+void in_free(InBuf* b);
 
 struct Ctx {
     int device = 0;
@@ -4523,6 +4525,7 @@ struct Ctx {
     JnBuf* jn = nullptr;          // graal_junction_scores' buffers (junctions.h; allocated by its first call)
     LnBuf* ln = nullptr;          // graal_end_links' buffers and its last result (links.h; allocated by its first call)
     EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
+    InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
 };
 
 #define CK(call)                                                                                     \
@@ -5266,6 +5269,7 @@ void graal_destroy(graal_ctx* h)
         jn_free(h->jn); h->jn = nullptr;
         ln_free(h->ln); h->ln = nullptr;
         ed_free(h->ed); h->ed = nullptr;
+        in_free(h->ins); h->ins = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
         if (h->h_stats) (void)hipHostFree(h->h_stats);
@@ -6763,4 +6767,5 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "simulate.h"
 #include "junctions.h"
 #include "links.h"
+#include "insert.h"
 #include "edit.h"

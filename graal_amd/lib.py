@@ -52,12 +52,13 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
-           "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout",
+           "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
 STEP_DONE, STEP_PAUSED, STEP_FALLBACK, STEP_SELECT = 0, 1, 2, 3
 JUNCTION_VALID, JUNCTION_END, JUNCTION_CIRCULAR, JUNCTION_NONFINITE = 0, 1, 2, 3   # graal_junction_scores' status bytes
 LINK_VALID, LINK_NONFINITE = 0, 1   # graal_end_links' status bytes
+INSERT_VALID, INSERT_NONFINITE = 0, 1   # graal_insertions' status bytes
 # graal_edit_layout's status words
 EDIT_OK, EDIT_BAD_CUT, EDIT_DUP_CUT, EDIT_BAD_END, EDIT_CIRCULAR, EDIT_END_TWICE, EDIT_SAME_CONTIG, EDIT_CYCLE = range(8)
 STEPS_ROW = 10   # GRAAL_STEPS_ROW: doubles per step in graal_steps' rows
@@ -136,6 +137,9 @@ def load():
         L.graal_end_links_best.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i64p, _i64p]
         L.graal_end_links_mutual_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i64p, ctypes.c_int64]
         L.graal_edit_layout.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, ctypes.c_int32, _i32p, _i32p, _i32p]
+        L.graal_insertions.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i64p]
+        L.graal_insertions_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, ctypes.POINTER(ctypes.c_uint8), _i64p, _i64p,
+                                             ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_finisher.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_mode.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -436,6 +440,32 @@ class Engine:
         self._ck(self._L.graal_end_links_mutual_fetch(self._h, a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p), q.ctypes.data_as(_i64p), m),
                  "graal_end_links_mutual_fetch")
         return be, bq, (a, b, q)
+
+    def insertions(self, max_piece_frags=1):
+        """graal_insertions: every insertion of a piece (a linear contig of 1 .. max_piece_frags fragments) into a junction of another
+        linear contig that the contacts support, as numpy columns (piece int32, after int32, rev uint8, score float64, contacts int64,
+        status uint8), sorted by (after, piece, rev).  piece = the piece's position-0 fragment, after = f: the piece goes between f and
+        next[f], its head next to f (rev 0) or its tail (rev 1); score = logL(inserted layout) - logL(layout) in the exact arithmetic,
+        NaN unless status is INSERT_VALID.  Same preconditions and refusals as end_links; leaves the step state alone."""
+        p, f, r, q, c, st = self.insertions_q(max_piece_frags)
+        return p, f, r, np.where(st == INSERT_VALID, q.astype(np.float64) / Q_SCALE, np.nan), c, st
+
+    def insertions_q(self, max_piece_frags=1):
+        """The same with the score as int64 Q: (piece, after, rev, q, contacts, status)."""
+        m = ctypes.c_int64(0)
+        self._ck(self._L.graal_insertions(self._h, int(max_piece_frags), ctypes.byref(m)), "graal_insertions")
+        m = int(m.value)
+        p = np.zeros(m, dtype=np.int32)
+        f = np.zeros(m, dtype=np.int32)
+        r = np.zeros(m, dtype=np.uint8)
+        q = np.zeros(m, dtype=np.int64)
+        c = np.zeros(m, dtype=np.int64)
+        st = np.zeros(m, dtype=np.uint8)
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        self._ck(self._L.graal_insertions_fetch(self._h, p.ctypes.data_as(_i32p), f.ctypes.data_as(_i32p), r.ctypes.data_as(u8),
+                                                q.ctypes.data_as(_i64p), c.ctypes.data_as(_i64p), st.ctypes.data_as(u8), m),
+                 "graal_insertions_fetch")
+        return p, f, r, q, c, st
 
     def edit_layout(self, cuts=(), joins=()):
         """graal_edit_layout: cut the junction after every fragment of `cuts`, then apply `joins` (pairs of ends, end = 2 * fragment +

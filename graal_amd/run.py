@@ -55,6 +55,14 @@ def main(argv=None):
     ap.add_argument("--polish", action="store_true", help="before the outputs, cut the final layout's junctions scoring below "
                                                           "--polish-cut-below and rejoin the pieces (graal_amd.scaffold); writes polish.tsv")
     ap.add_argument("--polish-cut-below", type=float, default=0.0, help="with --polish: the junction score below which a join is cut (default 0)")
+    ap.add_argument("--insert", action="store_true", help="after --scaffold and --polish, before the outputs: put pieces of up to "
+                                                          "--insert-max-frags fragments into the junctions they belong to, round by round "
+                                                          "(graal_amd.scaffold with insertions); writes insert.tsv")
+    ap.add_argument("--insert-max-frags", type=int, default=3, help="with --insert / --insertions: the largest piece, in fragments (default 3)")
+    ap.add_argument("--insert-min-score", type=float, default=0.0, help="with --insert: only insertions scoring above this (default 0)")
+    ap.add_argument("--insertions", action="store_true", help="write insertions.tsv into the output folder: every insertion of a piece of "
+                                                              "up to --insert-max-frags fragments into a junction of the final layout that the "
+                                                              "contacts support, with the log-likelihood it would add (graal_amd.insert)")
     args = ap.parse_args(argv)
     if not 0 <= args.level < args.size_pyramid:
         raise SystemExit("--level must be in 0 .. size-pyramid - 1 (levels >= 1: the level below holds the observations; 0: the level itself)")
@@ -116,6 +124,10 @@ def main(argv=None):
     if args.polish:
         from . import scaffold
         scaffold.write_scaffold_tsv(os.path.join(out, "polish.tsv"), scaffold.scaffold(smp, cut_below=args.polish_cut_below))
+    if args.insert:
+        from . import scaffold
+        scaffold.write_scaffold_tsv(os.path.join(out, "insert.tsv"),
+                                    scaffold.scaffold(smp, insert_max_frags=args.insert_max_frags, insert_min_score=args.insert_min_score))
     lev = P.get_level(args.level)
     if args.fasta:
         P.load_reference_sequence(args.fasta)
@@ -127,6 +139,11 @@ def main(argv=None):
     if args.links:
         from . import links
         links.write_links_tsv(os.path.join(out, "links.tsv"), links.link_table(smp, args.links_min_frags))
+    if args.insertions:
+        from . import insert
+        table, _ = insert.fitting_insertion_table(smp, args.insert_max_frags)   # (a smaller piece size when over the device budget)
+        if table is not None:
+            insert.write_insertions_tsv(os.path.join(out, "insertions.tsv"), table)
     n_steps = len(trace.likelihood)
     print("%d bins (%d fragments, %d sub-fragments), %d MCMC steps in %.1f s (%.0f us/step): %d contigs, logL %.6e, "
           "distance to the initial genome %.4f; traces in %s" % (inp["n_frags"], inp["n_new_frags"], inp["init_n_sub_frags"], n_steps,

@@ -1,6 +1,7 @@
 """Greedy scaffolding and polishing of a layout on the GPU: join mutual-best contig ends, cut the junctions the data reject, round by round.
 
-    scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None)   -- the rounds; returns their record
+    scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None,
+             insert_max_frags=None, insert_min_score=0.0)                             -- the rounds; returns their record
     break_cycles(ea, eb, score, contig_of_end)                                            -- drop the weakest join of every cycle
     write_scaffold_tsv(path, record)                                                      -- one tab-separated row per round
 
@@ -13,7 +14,11 @@ A round:
   3. every cycle of contigs those joins would close is broken at its weakest join (lowest score; ties: the larger (end_a, end_b));
   4. the joins in one graal_edit_layout call;
   5. a full evaluation (relabel, eval_full).
-Scaffolding stops when a round has no join left.  Joins are scored one at a time and combined joins are not additive: a round that lowers
+With insert_max_frags set, a round whose step 2 finds no join runs an insertion step instead (graal_amd.insert.plan_insertions: the
+mutual-best insertions of pieces of <= insert_max_frags fragments scoring above insert_min_score, each a cut and two joins, in one
+graal_edit_layout call), then the full evaluation; its row counts those cuts and joins.  When the insertion table of pieces that
+large is over the device budget, the step uses the largest smaller piece size that fits (down to 1, else it is skipped).
+Scaffolding stops when a round has no join (and no insertion) left.  Joins are scored one at a time and combined joins are not additive: a round that lowers
 logL is undone (the layout from before the round is uploaded again) and scaffolding stops there.
 """
 import numpy as np
@@ -85,9 +90,10 @@ def plan_joins(mutual, min_score, contig_of_end):
     return a[keep], b[keep], score[keep]
 
 
-def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None):
-    """Scaffold (and with cut_below, polish) the engine's current layout; see the module's docstring.  Returns the record: a list of
-    dicts with the keys COLUMNS, round 0 the layout as it came (kept 0 marks a round that was undone)."""
+def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None, insert_max_frags=None, insert_min_score=0.0):
+    """Scaffold (and with cut_below, polish; with insert_max_frags, insert pieces) the engine's current layout; see the module's
+    docstring.  Returns the record: a list of dicts with the keys COLUMNS, round 0 the layout as it came (kept 0 marks a round that was
+    undone)."""
     obj = sampler_or_engine
     e = _engine(obj)
     logl, nc = _evaluate(e)
@@ -103,12 +109,22 @@ def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below
         idc = e.download_frags()["id_c"] if len(cuts) else before["id_c"]
         _, _, mutual = e.end_links_best(min_frags)
         a, b, _ = plan_joins(mutual, min_score, lambda end: idc[end >> 1])
-        if len(a) == 0 and len(cuts) == 0:
+        icuts, ijoins = np.zeros(0, dtype=np.int64), np.zeros((0, 2), dtype=np.int64)
+        if len(a) == 0 and insert_max_frags is not None:
+            from . import insert
+            soa = e.download_frags() if len(cuts) else before
+            table, insert_max_frags = insert.fitting_insertion_table(e, insert_max_frags)
+            if table is not None:
+                icuts, ijoins, _ = insert.plan_insertions(table, soa, insert_min_score)
+            if len(icuts):
+                _edit(obj, e, icuts, ijoins)
+        if len(a) == 0 and len(cuts) == 0 and len(icuts) == 0:
             break
         if len(a):
             _edit(obj, e, [], np.stack([a, b], axis=1))
         new_logl, nc = _evaluate(e)
-        row = {"round": r, "cuts": int(len(cuts)), "joins": int(len(a)), "contigs": nc, "logL": new_logl, "kept": 1}
+        row = {"round": r, "cuts": int(len(cuts) + len(icuts)), "joins": int(len(a) + len(ijoins)), "contigs": nc, "logL": new_logl,
+               "kept": 1}
         if not new_logl >= logl:       # (NaN included)
             row["kept"] = 0
             record.append(row)
@@ -117,7 +133,7 @@ def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below
             break
         record.append(row)
         logl = new_logl
-        if len(a) == 0:
+        if len(a) == 0 and len(icuts) == 0:
             break
     return record
 

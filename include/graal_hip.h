@@ -356,6 +356,45 @@ int graal_end_links_mutual_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, i
 int graal_edit_layout(graal_ctx* h, int32_t n_cuts, const int32_t* cut_after, int32_t n_joins, const int32_t* end_a, const int32_t* end_b,
                       int32_t* status);
 
+/* Insertions: the likelihood each insertion of a small contig into a junction would add, for every (piece, junction, orientation) the
+ * contacts support, in one pass (graal_amd/csrc/insert.h).
+ * A PIECE is a linear contig P with 1 <= l_cont <= max_piece_frags fragments.  A TARGET junction is a fragment f with next[f] = g != -1
+ * in a linear contig T != P (the fragments graal_junction_scores scores, status neither END nor CIRCULAR).  The INSERTED layout for
+ * (P, f, rev) cuts T between f and g into T1 (.. f) and T2 (g ..) and makes the contig T1, P, T2: T1 and T2 keep T's direction,
+ * orientation and label; P enters as it is (rev 0: P's head next to f) or reversed (rev 1: P's tail next to f).  Positions, start_bp,
+ * ori, prev / next, l_cont and l_cont_bp as m_paste writes them: integer bp offsets first (P's fragments at end(f) + their offset in the
+ * oriented P, T2's shifted by len(P) = P's l_cont_bp), then the float32 centres through centre_kb.  Every other contig is untouched;
+ * labels do not enter the score.
+ *   I(P, f, rev) = logL(inserted) - logL(current)
+ * in the exact arithmetic under the current mode flags, with graal_junction_scores' / graal_end_links' roundings:
+ *   - every sub-fragment pair of P x T moves from its trans price to its cis price in the inserted layout;
+ *   - every pair of T1 x T2 moves from its cis price at distance d to its cis price at d + len(P) (past d_max: v_inter * norm, as
+ *     graal_eval_full_q prices a cis pair there);
+ *   - pairs inside P, inside T1 and inside T2 count as unchanged;
+ *   - a contact's term ob * (ln ex_new - ln ex_old) is rounded to Q once per contact, a fragment pair's mass -(sum of ex_new - sum of
+ *     ex_old) once per fragment pair; int64 sums: bit-identical from call to call and for any grid;
+ *   - under GRAAL_MODE_REF_TRANS_ACCU with bins of mixed RF counts, also the P x T pairs beyond the window that involve such a bin, and
+ *     for rev 1 P's mirror term (graal_end_links' term for a reversed contig) less its part on T.
+ * graal_edit_layout orders a chain canonically and may write the same insertion with the whole chain reversed: in the exact arithmetic
+ * that is the same likelihood to the rounding of the centres, under GRAAL_MODE_REF_TRANS_ACCU it differs by T's mirror term.  I is
+ * defined on T's direction.
+ * Listed: the candidates with at least one contact between P and T inside the window (sub-fragment centre distance < d_max) in the
+ * inserted layout; any other would score only its negative expected mass.  graal_insertions computes the table and returns its size in
+ * *n_out; graal_insertions_fetch copies it out sorted by (after, piece, rev): piece = P's position-0 fragment, after = f, rev 0 / 1,
+ * q = I in Q, contacts = the summed count inside the window, status GRAAL_INSERT_VALID or GRAAL_INSERT_NONFINITE (q = 0).
+ * The contact list may come in any order; one that is not sorted by row is radix-sorted by row on the device in every call (12 bytes
+ * per contact, counted against the budget below), with the same result.
+ * Needs sub-fragments, parameters, fragments and contacts.  Does not relabel and leaves the step state alone (ranked layout, carried
+ * total, a pending commit's correction, the proposal tables).  GRAAL_E_ARG for max_piece_frags < 1 and for cap < n_out;
+ * GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats), and when the candidate tables would need more than
+ * GRAAL_LINKS_MAX_BYTES of device memory (the message gives the bytes needed: use a smaller max_piece_frags); GRAAL_E_STATE with an
+ * exchange or RCCL attached (one rank only). */
+#define GRAAL_INSERT_VALID 0
+#define GRAAL_INSERT_NONFINITE 1
+int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out);
+int graal_insertions_fetch(graal_ctx* h, int32_t* piece, int32_t* after, uint8_t* rev, int64_t* q, int64_t* contacts, uint8_t* status,
+                           int64_t cap);
+
 /* ---- the sampler's per-step HOST logic behind the boundary (graal_amd/csrc/host_step.h) --------------------------------
  * What cuda_lib_gl.sampler.step_max_likelihood does on the host between its launches: return_neighbours
  * (cuda_lib_gl.py:2295-2331: RandomState.choice(xk, n, p=pk, replace=False), expansion to the copies of repeated bins,
