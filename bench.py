@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- candidate logL evaluations per second of the per-move likelihood scan (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and nothing else: it builds the workload, warms up, times the K steps, writes
+`--dump-outputs` and prints the result line -- `value`, `ms_per_step`, the configuration, the set-up times, the engine's counters
+(and `distributed`, N > 1).  `--full` then measures everything else behind the same timed steps: the fields marked "--full" below.
 
 N = 1 runs in this process.  N > 1 with WORLD_SIZE unset starts the N ranks itself: a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -13,21 +17,22 @@ generator seed 20141217; layout = exploded genome + 2,000 real MCMC warm-up step
 "step" = the scoring phase of one MCMC step: ONE fused pass over the contact list for the 13 x 5 = 65 candidates of a
 (fA, 5 neighbours) proposal, their expected-mass tasks, the exchange of the ranks' 65 int64 values (N > 1) and the
 device->host hand-over of the result (N > 1: each rank's GPU publishes its 65 int64 sums to pinned host memory shared by
-the ranks of the node and every host adds them up; the same region is then timed once more with an all-reduce of a device
-buffer instead, reported as `exchange_alt`).  Inputs are resident in HBM; proposals are drawn beforehand.  With N GPUs the SAME
+the ranks of the node and every host adds them up; with --full the same region is then timed once more with an all-reduce of a
+device buffer instead, reported as `exchange_alt`).  Inputs are resident in HBM; proposals are drawn beforehand.  With N GPUs the SAME
 contact list is sharded N ways (strong scaling).
 
 `value` is measured in REFERENCE ARITHMETIC (`config.reference_arithmetic` = "strict": every pixel of contig(A) u contig(B) re-priced
 from float32 kb coordinates like sub_compute_likelihood, kernels3.cu:3259-3718 -- the sampler's default, whose traces are the
-reference's); the same proposals are then timed in the exact arithmetic (`other_arithmetic`).  `--arithmetic exact` swaps the two.
+reference's); with --full the same proposals are then timed in the exact arithmetic (`other_arithmetic`).  `--arithmetic exact`
+swaps the two.
 
-Extra fields: `value_1000` (SURVEY 8d's 1,000-step region), `full_mcmc_step_ms` (graal_step: relabel + proposal + scoring + sampling +
+Extra fields (--full): `value_1000` (SURVEY 8d's 1,000-step region), `full_mcmc_step_ms` (graal_step: relabel + proposal + scoring + sampling +
 commit + statistics), `full_eval_ms` (one full likelihood evaluation: what a nuisance-parameter step adds to every MCMC step),
 `full_mcmc_step_sample_param_ms`, `late_stage` (the same map with its 7 original contigs -- millions of queued contacts and thousands
 of work units per step, sharded over the ranks -- in both arithmetics, with its own full-step / full-evaluation figures),
-`exchange_alt` and `distributed` (N > 1).
+`regimes`, `phase_ms`, the work counters of the roofline's last step (`*_last_step`), `exchange_alt` (N > 1).
 
-Output: one JSON line on rank 0 (contract in the task statement) with `roofline` (fused scan kernel k_scan: algorithmic bytes
+Output: one JSON line on rank 0; with --full also `roofline` (fused scan kernel k_scan: algorithmic bytes
 = 4 B x contacts (row words) + n/8 B (bitmap) + 16 B x queued contacts per launch; duration = MEDIAN of HIP event pairs around the
 launches of the timed region (every 8th step) and of an untimed repeat of the same steps with a pair on every step; plus the flat
 `hbm_control_*` fields: the same kernel, same layout, same proposals over a list whose row array (480 MB) cannot stay in the
@@ -227,13 +232,17 @@ def main():
     ap.add_argument("--nnz", type=int, default=int(os.environ.get("GRAAL_BENCH_NNZ", 20_000_000)))
     ap.add_argument("--mcmc-warmup", type=int, default=int(os.environ.get("GRAAL_BENCH_MCMC_WARMUP", 2000)))
     ap.add_argument("--neighbours", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the headline's timed steps, measure everything else: the other arithmetic, the long region, roofline "
+                         "and control, full steps and evaluations, the late stage, the CPU baselines, exchange_alt (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--arithmetic", choices=("strict", "exact"), default="strict",
                     help="arithmetic of the headline `value`: strict = the reference's (kernels3.cu:3259-3718; the sampler's default), "
-                         "exact = mathematically exact deltas; the other one is reported next to it")
-    ap.add_argument("--long-steps", type=int, default=1000, help="steps of the second timed region (`value_1000`, SURVEY 8d); 0 = skip")
-    ap.add_argument("--no-late-stage", action="store_true", help="skip the extra measurement on the map's 7 original contigs")
-    ap.add_argument("--no-hbm-control", action="store_true", help="skip the Infinity-Cache control of the roofline figure")
+                         "exact = mathematically exact deltas; --full reports the other one next to it")
+    ap.add_argument("--long-steps", type=int, default=1000, help="--full: steps of the second timed region (`value_1000`, SURVEY 8d); "
+                                                                  "0 = skip.  Every run draws its proposals, so it also fixes the timed steps' inputs")
+    ap.add_argument("--no-late-stage", action="store_true", help="--full: skip the extra measurement on the map's 7 original contigs")
+    ap.add_argument("--no-hbm-control", action="store_true", help="--full: skip the Infinity-Cache control of the roofline figure")
     ap.add_argument("--control-repeat", type=int, default=6, help="hbm_control: list every contact this many times")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                                                       "the multi-rank code path with several ranks on ONE GPU)")
@@ -465,7 +474,8 @@ def main():
     # ---- proposals for the timed regions, drawn BEFORE the MCMC warm-up (the neighbour distribution is the contact map's, not the
     # layout's): drawn right in front of the timed region -- ~1,000 Python calls, 30 ms -- they left the GPU idle, and the first timed
     # steps were 10 us slower than the rest (r03: 1.645 M in the driver's 20-step run against 1.754 M over 1,000).  The generator is put back
-    # where it was: the warm-up steps draw what they always drew.
+    # where it was: the warm-up steps draw what they always drew.  (The neighbours are drawn behind all `total` fragments, so the
+    # long region's proposals are drawn in a plain run too: without them the timed steps' proposals would not be --full's.)
     total = args.warmup + max(args.steps, args.long_steps)
     rng_state = rng.get_state()
     frags = rng.randint(0, n, size=total)
@@ -581,9 +591,61 @@ def main():
             d = [one(i) for i in range(6)]
             print("bracket: steps %s | synchronize %.1f, again %.1f | steps behind it %s | behind a 200 us spin %s | behind a 2 ms sleep %s" % (
                 " ".join("%.0f" % x for x in a), s1, s2, " ".join("%.0f" % x for x in b), " ".join("%.0f" % x for x in c), " ".join("%.0f" % x for x in d)), file=sys.stderr)
+    elapsed = max_over_ranks(elapsed)
+
+    def headline():
+        """What every run's line carries: the headline, what it was measured on, the set-up times and the engine's counters."""
+        rc_ = smp.engine.run_counters()
+        h = {
+            "metric": "candidate logL evals/sec", "value": n_cand / elapsed, "unit": "candidate logL evals/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32 model / f64 log / int64 Q30 sums",
+            "data": "synthetic",
+            "config": {"workload": "C5 synthetic %d-fragment / %d-contact map, %s + %d MCMC warm-up steps"
+                                   % (n, len(P["coo_row"]), args.layout, args.mcmc_warmup),
+                       "reference_arithmetic": args.arithmetic,
+                       "reference_arithmetic_note": "strict = every pixel of contig(A) u contig(B) re-priced from float32 kb coordinates like "
+                                                    "sub_compute_likelihood (kernels3.cu:3259-3718) + the trans-branch RF-count indexing: the "
+                                                    "sampler's default, traces are the reference's; exact = mathematically exact deltas",
+                       "neighbours_per_step": K, "candidates_per_step": 13 * K, "contacts_per_gpu": int(smp.engine.nnz),
+                       "n_contigs": int(stats[0]), "max_contig_len": int(stats[4]),
+                       "parallelism": "contacts sharded x%d, %s" % (world, {
+                           "none": "single rank", "rccl": "1 all-reduce(65 x int64)/step (%s)" % args.backend,
+                           "host": "65 x int64 per rank and step published to pinned host memory shared by the ranks, summed by every host"
+                       }[smp.exchange])},
+            "setup_s": {"generate": t_gen, "sampler": t_setup, "mcmc_warmup": t_mcmc},
+            # steps the engine had to REPEAT behind events because an in-kernel wait between two kernels of a step ran out (k_tm waiting for the
+            # scan's announcement, k_strict2 for k_gprep's completion word: include/graal_hip.h, graal_run_counters) over this handle's whole
+            # life -- warm-up, settling, timed region and, with --full, the extras; 0 unless a tool serialises the dispatches
+            "fallbacks": rc_["fallbacks"], "engine_counters": rc_,
+        }
+        if world > 1:
+            h["distributed"] = {"backend": td.get_backend(), "ranks": int(td.get_world_size()), "exchange": smp.exchange,
+                                "rccl_ranks": int(td.get_world_size()) if td.get_backend() == "nccl" else 0,
+                                "value_produced_by_exchange": smp.exchange,
+                                "north_star_exchange": "one RCCL all-reduce of the per-shard candidate vector per MCMC step over xGMI: timed as `exchange_alt` "
+                                                       "(--full, last in the job); `value` is produced by the exchange named in value_produced_by_exchange -- "
+                                                       "'host' = the ranks' 65 int64 sums through pinned host memory of the node (bit-identical sums, nothing "
+                                                       "added to the GPU timeline), DESIGN.md section 6"}
+        return h
+
+    def finish():
+        smp.free_gpu()
+        if world > 1:
+            try:
+                td.barrier()
+                td.destroy_process_group()
+            except Exception:
+                pass
+
+    if not args.full:   # a plain run: the headline line, nothing more
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        finish()
+        return
+
     n_timed_pairs = min(args.steps // EVENT_EVERY, 1024) if EVENT_EVERY > 0 else 0
     scan_ms_timed = smp.engine.scan_times(n_timed_pairs) if n_timed_pairs else np.zeros(0, np.float32)   # pairs of the timed region
-    elapsed = max_over_ranks(elapsed)
     n2 = min(args.steps, 64)
     smp.engine.set_timing(1)
     for f, nb in props[args.warmup:args.warmup + n2]:
@@ -723,23 +785,8 @@ def main():
                     trace_us = tj.get("kernel_avg_us_rocprof_in_a_step")
             except Exception:
                 traffic = None
-        out = {
-            "metric": "candidate logL evals/sec", "value": n_cand / elapsed, "unit": "candidate logL evals/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32 model / f64 log / int64 Q30 sums",
-            "data": "synthetic",
-            "config": {"workload": "C5 synthetic %d-fragment / %d-contact map, %s + %d MCMC warm-up steps"
-                                   % (n, len(P["coo_row"]), args.layout, args.mcmc_warmup),
-                       "reference_arithmetic": args.arithmetic,
-                       "reference_arithmetic_note": "strict = every pixel of contig(A) u contig(B) re-priced from float32 kb coordinates like "
-                                                    "sub_compute_likelihood (kernels3.cu:3259-3718) + the trans-branch RF-count indexing: the "
-                                                    "sampler's default, traces are the reference's; exact = mathematically exact deltas",
-                       "neighbours_per_step": K, "candidates_per_step": 13 * K, "contacts_per_gpu": int(nnz_local),
-                       "n_contigs": int(stats[0]), "max_contig_len": int(stats[4]),
-                       "parallelism": "contacts sharded x%d, %s" % (world, {
-                           "none": "single rank", "rccl": "1 all-reduce(65 x int64)/step (%s)" % args.backend,
-                           "host": "65 x int64 per rank and step published to pinned host memory shared by the ranks, summed by every host"
-                       }[smp.exchange])},
+        out = headline()
+        out.update({
             "roofline": dict({"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_source": "committed rocprofv3 --pmc run of this workload (profiles/traffic.json), not measured in this run",
@@ -764,14 +811,7 @@ def main():
             "mass_items_last_step": int(counters[3]),
             "full_mcmc_step_ms": 1e3 * full_step_s, "full_eval_ms": 1e3 * full_eval_s,
             "full_mcmc_step_sample_param_ms": 1e3 * full_step_sp_s,
-            "setup_s": {"generate": t_gen, "sampler": t_setup, "mcmc_warmup": t_mcmc},
-        }
-        # steps the engine had to REPEAT behind events because an in-kernel wait between two kernels of a step ran out (k_tm waiting for the
-        # scan's announcement, k_strict2 for k_gprep's completion word: include/graal_hip.h, graal_run_counters) over this handle's whole
-        # life -- warm-up, settling, timed regions and extras; 0 unless a tool serialises the dispatches
-        rc_ = smp.engine.run_counters()
-        out["fallbacks"] = rc_["fallbacks"]
-        out["engine_counters"] = rc_
+        })
         out["other_arithmetic"] = other_block
         if long_region:
             out.update(long_region)
@@ -786,14 +826,6 @@ def main():
                 "ms_per_step": late.get("ms_per_step"), "sharded_kernels_us_this_rank": late.get("sharded_kernels_us_this_rank"),
                 "non_sharded_us_per_step": late.get("non_sharded_us_per_step"),
                 "expected_at_8_gpus": "units dealt (ti + tj) % world, contacts by shard: ~0.23 ms per step, ~6x -- the regime that can meet north_star's >= 6x"}}
-        if world > 1:
-            out["distributed"] = {"backend": td.get_backend(), "ranks": int(td.get_world_size()), "exchange": smp.exchange,
-                                  "rccl_ranks": int(td.get_world_size()) if td.get_backend() == "nccl" else 0,
-                                  "value_produced_by_exchange": smp.exchange,
-                                  "north_star_exchange": "one RCCL all-reduce of the per-shard candidate vector per MCMC step over xGMI: timed as `exchange_alt` "
-                                                         "(last in the job); `value` is produced by the exchange named in value_produced_by_exchange -- 'host' = "
-                                                         "the ranks' 65 int64 sums through pinned host memory of the node (bit-identical sums, nothing added to the "
-                                                         "GPU timeline), DESIGN.md section 6"}
         if alt is not None:
             out["exchange_alt"] = alt
         if late is not None:
@@ -824,13 +856,7 @@ def main():
         if rank == 0 and alt is not None:
             out["exchange_alt"] = alt
             print(json.dumps(out), flush=True)     # (the same line again, with the extra: the last line is the complete one)
-    smp.free_gpu()
-    if world > 1:
-        try:
-            td.barrier()
-            td.destroy_process_group()
-        except Exception:
-            pass
+    finish()
 
 
 if __name__ == "__main__":

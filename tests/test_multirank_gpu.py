@@ -186,8 +186,8 @@ def test_rccl_all_reduce_driven_by_the_library_on_the_gpu_timeline(which, tmp_pa
 
 @pytest.mark.timeout(900)
 def test_bench_runs_two_ranks_from_one_command():
-    """`python bench.py --gpus 2` (no torchrun around it) on a small map: the launcher starts both ranks (here both on this one
-    GPU, gloo instead of RCCL), rank 0 prints the one JSON line with both exchanges and the late-stage extra."""
+    """`python bench.py --gpus 2 --full` (no torchrun around it) on a small map: the launcher starts both ranks (here both on this
+    one GPU, gloo instead of RCCL), rank 0 prints the one JSON line with both exchanges and the late-stage extra."""
     import json
     import subprocess
     import sys
@@ -195,7 +195,7 @@ def test_bench_runs_two_ranks_from_one_command():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["GRAAL_BENCH_PHASES"] = "1"    # (where the run is, on stderr: shown if it fails)
     env["GRAAL_DEBUG_ADDR"] = "1"      # (... and where the engines' buffers are: a fault's address can be matched to one)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--n-bins", "2000",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--backend", "gloo", "--n-bins", "2000",
            "--nnz", "100000", "--steps", "6", "--warmup", "2", "--mcmc-warmup", "300"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
     if out.returncode != 0:      # (keep everything the ranks said -- phase markers, the engines' buffer map: gpurun_out/ travels back from the GPU box.

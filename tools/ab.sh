@@ -16,7 +16,7 @@ for round in 1 2; do for spec in "$@"; do
   envs=${rest%%:*}; flags=${rest#*:}; [ "$flags" = "$rest" ] && flags=""
   E=""; [ -n "$envs" ] && E=$(echo $envs | tr ',' ' ')
   [ -n "$flags" ] && E="$E GRAAL_HIP_LIB=/tmp/lib_$name.so"
-  env $E timeout -k 10 300 python bench.py --steps ${AB_STEPS:-300} --warmup 20 --long-steps 0 --no-cpu-baseline ${AB_LATE:---no-late-stage} --no-hbm-control 2>/dev/null | python -c "
+  env $E timeout -k 10 300 python bench.py --full --steps ${AB_STEPS:-300} --warmup 20 --long-steps 0 --no-cpu-baseline ${AB_LATE:---no-late-stage} --no-hbm-control 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 for round in 1 2 3; do for spec in "$@"; do
   name=${spec%%=*}; lib=${spec#*=}
   if [ "$lib" = "-" ]; then unset GRAAL_HIP_LIB; else export GRAAL_HIP_LIB=$lib; fi
-  timeout -k 10 300 python bench.py --steps 300 --warmup 20 --long-steps 1000 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
+  timeout -k 10 300 python bench.py --full --steps 300 --warmup 20 --long-steps 1000 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -8,7 +8,7 @@ OUT=gpurun_out/ab_scan.log
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -DGRAAL_SCAN_PRE=0 -o /tmp/libgraal_pre0.so graal_amd/csrc/graal_hip.hip 2>>$OUT
 run() {
   echo "== $*" >> $OUT
-  env "$@" timeout -k 10 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
+  env "$@" timeout -k 10 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -9,7 +9,7 @@ $B -DGRAAL_EXP_NOHITS -o /tmp/lib_nohits.so graal_amd/csrc/graal_hip.hip 2>>$OUT
 wait
 run() {
   echo "== $*" >> $OUT
-  env "$@" timeout -k 10 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
+  env "$@" timeout -k 10 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

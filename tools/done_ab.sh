@@ -3,7 +3,7 @@
 out=gpurun_out/done_ab.log; : > $out
 for n in 1 16 8 4 16 1; do
   echo "== GRAAL_SCAN_DONE_N=$n" >> $out
-  GRAAL_SCAN_DONE_N=$n timeout -k 10 300 python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
+  GRAAL_SCAN_DONE_N=$n timeout -k 10 300 python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

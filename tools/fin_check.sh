@@ -7,7 +7,7 @@ for shape in "1086 120000 3" "3500 600000 3"; do
   timeout -k 10 120 python tools/step_breakdown.py --n-bins $1 --nnz $2 --n-sub $3 --original --steps 1500 2>&1 | grep -E "full MCMC step|scoring|Error|error" >> $out || exit 1
 done
 echo "== C5, 7 original contigs (late stage)" >> $out
-timeout -k 10 300 python bench.py --layout original --steps 30 --warmup 5 --mcmc-warmup 0 --no-cpu-baseline --no-late-stage --no-hbm-control 2>&1 | python -c "
+timeout -k 10 300 python bench.py --full --layout original --steps 30 --warmup 5 --mcmc-warmup 0 --no-cpu-baseline --no-late-stage --no-hbm-control 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

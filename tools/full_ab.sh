@@ -6,7 +6,7 @@ OUT=gpurun_out/full_ab.log
 : > $OUT
 run() {
   echo "== $*" >> $OUT
-  env "$@" timeout -k 10 200 python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
+  env "$@" timeout -k 10 200 python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ OUT=gpurun_out/full_ab2.log
 : > $OUT
 run() {
   echo "== $*" >> $OUT
-  ( cd /tmp && env TMPDIR=/tmp "$@" timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tr_$$ -- python3 $REPO/bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-late-stage --no-hbm-control > /tmp/tr.log 2>&1 )
+  ( cd /tmp && env TMPDIR=/tmp "$@" timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tr_$$ -- python3 $REPO/bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-late-stage --no-hbm-control > /tmp/tr.log 2>&1 )
   python3 - /tmp/tr_$$ >> $OUT <<'PY'
 import sys, glob, csv, collections
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]

@@ -8,7 +8,7 @@ OUT=gpurun_out/late_ab.log
 : > $OUT
 run() {
   echo "== $*" >> $OUT
-  env "$@" timeout -k 10 200 python bench.py --layout original --steps 30 --warmup 5 --mcmc-warmup 0 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
+  env "$@" timeout -k 10 200 python bench.py --full --layout original --steps 30 --warmup 5 --mcmc-warmup 0 --no-cpu-baseline --no-late-stage --no-hbm-control 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
@@ -20,7 +20,7 @@ run X=1
 run GRAAL_FIN_SKIP=1
 run GRAAL_FIN_SKIP=2
 run GRAAL_FIN_SKIP=3
-( cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/late_trace -- python3 $REPO/bench.py --layout original --steps 30 --warmup 5 --mcmc-warmup 0 --no-cpu-baseline --no-late-stage --no-hbm-control > /tmp/late_trace.log 2>&1 )
+( cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/late_trace -- python3 $REPO/bench.py --full --layout original --steps 30 --warmup 5 --mcmc-warmup 0 --no-cpu-baseline --no-late-stage --no-hbm-control > /tmp/late_trace.log 2>&1 )
 python3 - /tmp/late_trace >> $OUT <<'PY'
 import sys, glob, csv, collections
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]

@@ -15,7 +15,7 @@ REPO=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 case $WHAT in
-  c5)   ARGS="$REPO/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-late-stage --no-hbm-control" ;;
+  c5)   ARGS="$REPO/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-late-stage --no-hbm-control" ;;
   late) ARGS="$REPO/bench.py --late-only --late-repeats 3" ;;   # exactly the launches bench.py's late_stage.roofline is quoted on (3 warm-up + 3 x 12 timed steps)
   c2)   ARGS="$REPO/tools/step_breakdown.py --n-bins 1086 --nnz 120000 --n-sub 3 --original --steps 400" ;;
   c4)   ARGS="$REPO/tools/run_configs.py C4 --cycles ${C4_CYCLES:-2}" ;;

@@ -6,7 +6,7 @@ i=0
 while read -r cfg; do
   [ -z "$cfg" ] && continue
   i=$((i+1)); OUT=/tmp/sweep_$i; rm -rf $OUT
-  ( cd /tmp && env $cfg timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --steps 200 --warmup 20 --no-cpu-baseline > /tmp/sweep_$i.log 2>&1 )
+  ( cd /tmp && env $cfg timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > /tmp/sweep_$i.log 2>&1 )
   python3 - $OUT "$cfg" /tmp/sweep_$i.log <<'PY'
 import sys, glob, csv, collections, json
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]

@@ -4,7 +4,7 @@ TAG=$1; shift
 export TMPDIR=/tmp
 REPO=${GRAFT_REPO_ROOT:-$PWD}
 OUT=/tmp/trace_$TAG; rm -rf $OUT
-( cd /tmp && env "$@" timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-late-stage --no-hbm-control > /tmp/trace_$TAG.log 2>&1 )
+( cd /tmp && env "$@" timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-late-stage --no-hbm-control > /tmp/trace_$TAG.log 2>&1 )
 python3 - $OUT "$TAG $*" /tmp/trace_$TAG.log <<'PY'
 import sys, glob, csv, collections, json
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
