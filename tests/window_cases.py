@@ -1,0 +1,99 @@
+"""TEST INFRASTRUCTURE -- seeded problems for the windowed restatement (tests/window_reference.py): small ones that the brute-force
+restatements can still afford, with contigs several contact windows long, and mid-size ones that reach the kernels' tiling, striding and
+window exits (tests/test_layout_scores_midsize_gpu.py).  Not product code.
+"""
+import numpy as np
+
+from graal_amd import synth
+from tests import link_reference as LR
+
+
+def _with_state(P, s, par):
+    P["S_o_A_frags"] = s
+    P["param_simu"] = par
+    return P
+
+
+def small(name):
+    """'w1': n_sub 1, 240 bins, ~2,000 contacts, a 6 kb window (~9 fragments) against contigs of 24-58 kb.  'w3': n_sub 3 ragged with
+    RF counts 1..4 and every 4th bin reversed, 160 bins, a 12 kb window (~8 bins) against contigs of 50-120 kb."""
+    if name == "w1":
+        par = synth.make_param_simu(fact=2000.0, v_inter=0.05, d_max=6.0)
+        P = synth.make_problem(n_bins=240, nnz=2000, n_sub=1, seed=51, contig_weights=(5, 3, 2), param=par)
+        s = {k: np.array(v) for k, v in P["S_o_A_frags"].items()}
+        s["ori"][1::3] = -1
+    else:
+        par = synth.make_param_simu(fact=2000.0, v_inter=0.05, d_max=12.0)
+        P = synth.make_problem(n_bins=160, nnz=2000, n_sub=3, seed=52, contig_weights=(5, 3, 2), mean_len_bp=500.0, accu=("random", 1, 4),
+                               param=par)
+        s = {k: np.array(v) for k, v in P["S_o_A_frags"].items()}
+        s["ori"][::4] = -1
+    return _with_state(P, s, par)
+
+
+def cut_pieces(P, lengths, seed, rings=()):
+    """P with its linear contigs cut into pieces whose lengths cycle through `lengths`, shuffled, every third one reversed; the contigs
+    labelled in `rings` stay whole and become rings."""
+    s = P["S_o_A_frags"]
+    lists = LR.contig_lists(s)
+    rng = np.random.RandomState(seed)
+    pieces, whole = [], []
+    k = 0
+    for c, frags in lists.items():
+        if c in rings:
+            whole.append(frags)
+            continue
+        i = 0
+        while i < len(frags):
+            w = lengths[k % len(lengths)]; k += 1
+            pieces.append(frags[i:i + w])
+            i += w
+    order = rng.permutation(len(pieces))
+    pieces = [pieces[j] for j in order]
+    pieces = [[(f, -o) for f, o in reversed(p)] if j % 3 == 0 else p for j, p in enumerate(pieces)]
+    Q = dict(P)
+    Q["S_o_A_frags"] = LR.layout(s["len_bp"], whole + pieces, set(range(len(whole))))
+    return Q
+
+
+SMALL_PIECES = (2, 30, 1, 4, 45, 3, 1, 25, 2, 4, 60, 1, 3, 35)
+
+
+def small_cut(name):
+    """The small problems cut into pieces of 1-4 fragments (insertion pieces) and of 25-60 fragments (several windows long)."""
+    return cut_pieces(small(name), SMALL_PIECES, {"w1": 5, "w3": 6}[name])
+
+
+def m1(d_max=None):
+    """n_sub 1, 11,000 fragments of ~150 bp, 600,000 contacts; contigs of 8,401, 1,800, 500 (a ring), 200, 63 and 36 fragments.  The
+    model's own window (fact 2000, v_inter 0.01) is 233 kb, ~1,550 fragments; d_max narrows it."""
+    par = synth.make_param_simu(fact=2000.0, v_inter=0.01, d_max=d_max)
+    P = synth.make_problem(n_bins=11000, nnz=600_000, n_sub=1, seed=31, contig_weights=(8400, 1800, 500, 200, 64, 36), mean_len_bp=150.0,
+                           param=par)
+    s = {k: np.array(v) for k, v in P["S_o_A_frags"].items()}
+    s["ori"][1::3] = -1
+    s["circ"][s["id_c"] == 3] = 1
+    return _with_state(P, s, par)
+
+
+def m2():
+    """n_sub 3 ragged, RF counts 1..4, every 4th bin reversed, 3,000 bins of ~0.9 kb, 120,000 contacts, a 100 kb window (~110 bins);
+    contigs of 1,100, 800, 600 and 500 bins."""
+    par = synth.make_param_simu(fact=2000.0, v_inter=0.05, d_max=100.0)
+    P = synth.make_problem(n_bins=3000, nnz=120_000, n_sub=3, seed=32, contig_weights=(1100, 800, 600, 500), mean_len_bp=300.0,
+                           accu=("random", 1, 4), param=par)
+    s = {k: np.array(v) for k, v in P["S_o_A_frags"].items()}
+    s["ori"][::4] = -1
+    return _with_state(P, s, par)
+
+
+MID_PIECES = (3, 120, 1, 40, 2, 260, 4, 1, 75, 9, 2, 180, 1, 3, 60, 4, 1, 320, 2, 5, 7, 1, 150, 6)
+
+
+def m1_cut():
+    """m1 with a 25 kb window (~170 fragments), cut into shuffled pieces of 1-9 and 40-320 fragments; the ring stays."""
+    return cut_pieces(m1(d_max=25.0), MID_PIECES, 7, rings=(3,))
+
+
+def m2_cut():
+    return cut_pieces(m2(), MID_PIECES, 8)
