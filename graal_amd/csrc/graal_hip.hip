@@ -33,6 +33,7 @@
 #include "frag_ops.h"
 #include "strict_sets.h"
 #include "model_math.h"
+#include "scan_rows.h"
 
 using namespace graal;
 
@@ -2577,39 +2578,20 @@ struct ScanArgs { // by value: kernel-argument pointers are known to be GLOBAL (
     unsigned long long relabel_seq;     // 0: nobody waits
 };
 
-// word j (0 .. 4G-1) of G groups held in registers (select chain over constant indices: stays in registers)
-template <int G> __device__ __forceinline__ int sel_words(const int4 (&a)[G], int j)
-{
-    int v = 0;
-#pragma unroll
-    for (int i = 0; i < G; i++) {
-        const int4 q = a[i];
-        const int w = (j & 3) == 0 ? q.x : ((j & 3) == 1 ? q.y : ((j & 3) == 2 ? q.z : q.w));
-        v = (j >> 2) == i ? w : v;
-    }
-    return v;
-}
-
-// G = groups of 4 contacts per thread and iteration.  G = 4 with two 1024-thread blocks per CU (8 waves/SIMD, <= 64 VGPRs);
-// G = 8 with one block per CU (half the waves to launch, the same bytes in flight).
-template <bool SINGLE_SUB, int G>
-__global__ __launch_bounds__(1024, (G <= 4 ? 8 : 4)) void k_scan(ScanArgs sa, int fA, Neigh nb, int K, int max_id,
-                                                int dry /* timing replays: count, do not queue */)
+// The prologue of the contact producers (k_scan, k_scan_rows): marks the affected ids -- the (sub-)fragments of contig(fA) and of the
+// neighbours' contigs -- in the 1-bit-per-id bitmap at the start of the block's dynamic LDS.  The bitmap is complete for every thread
+// when this returns.  `clear` runs in thread 0 in front of the block's barrier (the caller's own LDS words); `pre` runs in every thread
+// between the prologue's loads and its first wait: k_scan requests its first batch of row words there.
+// (inlined, with the kernel's argument struct by reference: a CALLED function would see generic pointers and load FLAT)
+template <bool SINGLE_SUB, class Clear, class Pre>
+__device__ __forceinline__ void scan_mark_affected(const ScanArgs& sa, const int fA, const Neigh& nb, const int K, Clear&& clear, Pre&& pre)
 {
     extern __shared__ unsigned s_bm[];
     __shared__ Rec s_rec[MAXK + 1];
     __shared__ int s_cbase[MAXK + 1], s_clen[MAXK + 1], s_pref[MAXK + 2], s_fB[MAXK];
-    __shared__ int s_waves_done, s_long;
-    __shared__ int s_hitbuf[16][64 * 3];   // per wave: the doubly-affected contacts of one iteration (row id, col id, contact index), dealt one per lane
+    __shared__ int s_long;
     __shared__ unsigned s_keys_ready;
-    __shared__ unsigned long long s_nrel;
     const int t = threadIdx.x;
-    const int lane = t & 63;
-    if (sa.relabel_seq != 0ull && blockIdx.x == 0 && t == 0)
-        __hip_atomic_store(sa.relabel_flag, sa.relabel_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the relabel's writes were released when it ended)
-    (void)max_id;   // (the candidates' geometry is k_tm's and the consumers' business; kept in the signature for the timing replays)
-    STAMP(8, blockIdx.x == 0 && t == 0 && !dry);
-    STAMP_BLK(0, t == 0 && !dry);
     // ---- prologue.  Only the affected BITMAP stands between a block and its stream, so wave 0 builds nothing else: one
     // 32-byte load per fragment (fA and the K neighbours: their mates rows = the fragments of their contigs when those hold
     // <= N_MATES fragments, a marker row otherwise), LDS bit sets, the block's one barrier.  Everything the rare later tests
@@ -2628,23 +2610,7 @@ __global__ __launch_bounds__(1024, (G <= 4 ? 8 : 4)) void k_scan(ScanArgs sa, in
         my_f = t == 64 ? fA : sel_nb(nb, t - 65);
         my_geo = sa.geo[my_f]; my_link = sa.link[my_f]; my_cbase = sa.cbase[my_f];
     }
-    const long long nnz = sa.nnz;
-    const int n4 = (int)(nnz >> 2);           // groups of 4 contacts: 0 .. n4 (the last one partial or empty; nnz < 2^33)
-    const int4* __restrict__ row4 = sa.row4;
-    const int stride = (int)(gridDim.x * blockDim.x);
-    int g0 = (int)(blockIdx.x * blockDim.x) + t;
-    // unconditional loads with a clamped group index (group n4 is in bounds: the arrays are padded): branch-free, so the
-    // compiler keeps all of them in flight together.  The first batch is requested here, ABOVE the barrier: 40 % of the list is
-    // on its way while the bitmap is built.  Waves 0 and 1 too: their prologue loads were issued first (just above), so they
-    // come back first (vector-memory results return in issue order) and the two waves hold their first batch like everybody else
-    // instead of starting their stream a round trip late -- which made them the tail of every block.
-    auto ldg = [&](int g) { return ld_stream(row4 + (g < n4 ? g : n4)); }; // (group indices fit 32 bits: nnz < 2^32)
-    int4 f[G];
-    static_assert(SCAN_PRE == 0 || SCAN_PRE == 4, "");
-    if (SCAN_PRE) {
-#pragma unroll
-        for (int i = 0; i < G; i++) f[i] = ldg(g0 + i * stride);
-    }
+    pre();
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 #ifdef GRAAL_EXP_NOFOLD   // (A/B build, tools/ab.sh: what the fold's one AND per id costs)
     const unsigned wm = 0xffffffffu;
@@ -2664,7 +2630,7 @@ __global__ __launch_bounds__(1024, (G <= 4 ? 8 : 4)) void k_scan(ScanArgs sa, in
         // (all three are first touched by anybody else BEHIND the block's barrier -- wave 1 sets s_keys_ready there -- so this
         // clear is ordered before every use.  LDS keeps what earlier launches left: another engine of this process, or another
         // process on the same GPU, may have left the very same token value behind)
-        if (t == 0) { s_waves_done = 0; s_nrel = 0; s_keys_ready = 0; }
+        if (t == 0) { clear(); s_keys_ready = 0; }
         for (int i = t; i < sa.bitmap_words; i += 64) s_bm[i] = 0;
         WSYNC();
         const bool is_long = t <= K && row0.x == MATES_LONG;
@@ -2727,6 +2693,64 @@ __global__ __launch_bounds__(1024, (G <= 4 ? 8 : 4)) void k_scan(ScanArgs sa, in
         }
         __syncthreads();
     }
+}
+
+// word j (0 .. 4G-1) of G groups held in registers (select chain over constant indices: stays in registers)
+template <int G> __device__ __forceinline__ int sel_words(const int4 (&a)[G], int j)
+{
+    int v = 0;
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+        const int4 q = a[i];
+        const int w = (j & 3) == 0 ? q.x : ((j & 3) == 1 ? q.y : ((j & 3) == 2 ? q.z : q.w));
+        v = (j >> 2) == i ? w : v;
+    }
+    return v;
+}
+
+// G = groups of 4 contacts per thread and iteration.  G = 4 with two 1024-thread blocks per CU (8 waves/SIMD, <= 64 VGPRs);
+// G = 8 with one block per CU (half the waves to launch, the same bytes in flight).
+template <bool SINGLE_SUB, int G>
+__global__ __launch_bounds__(1024, (G <= 4 ? 8 : 4)) void k_scan(ScanArgs sa, int fA, Neigh nb, int K, int max_id,
+                                                int dry /* timing replays: count, do not queue */)
+{
+    extern __shared__ unsigned s_bm[];
+    __shared__ int s_waves_done;
+    __shared__ int s_hitbuf[16][64 * 3];   // per wave: the doubly-affected contacts of one iteration (row id, col id, contact index), dealt one per lane
+    __shared__ unsigned long long s_nrel;
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    if (sa.relabel_seq != 0ull && blockIdx.x == 0 && t == 0)
+        __hip_atomic_store(sa.relabel_flag, sa.relabel_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the relabel's writes were released when it ended)
+    (void)max_id;   // (the candidates' geometry is k_tm's and the consumers' business; kept in the signature for the timing replays)
+    STAMP(8, blockIdx.x == 0 && t == 0 && !dry);
+    STAMP_BLK(0, t == 0 && !dry);
+    // ---- prologue: the affected bitmap (scan_mark_affected), with the first batch of row words requested inside it
+    const long long nnz = sa.nnz;
+    const int n4 = (int)(nnz >> 2);           // groups of 4 contacts: 0 .. n4 (the last one partial or empty; nnz < 2^33)
+    const int4* __restrict__ row4 = sa.row4;
+    const int stride = (int)(gridDim.x * blockDim.x);
+    int g0 = (int)(blockIdx.x * blockDim.x) + t;
+    // unconditional loads with a clamped group index (group n4 is in bounds: the arrays are padded): branch-free, so the
+    // compiler keeps all of them in flight together.  The first batch is requested here, ABOVE the barrier: 40 % of the list is
+    // on its way while the bitmap is built.  Waves 0 and 1 too: their prologue loads were issued first (just above), so they
+    // come back first (vector-memory results return in issue order) and the two waves hold their first batch like everybody else
+    // instead of starting their stream a round trip late -- which made them the tail of every block.
+    auto ldg = [&](int g) { return ld_stream(row4 + (g < n4 ? g : n4)); }; // (group indices fit 32 bits: nnz < 2^32)
+    int4 f[G];
+    static_assert(SCAN_PRE == 0 || SCAN_PRE == 4, "");
+    scan_mark_affected<SINGLE_SUB>(sa, fA, nb, K, [&]() { s_waves_done = 0; s_nrel = 0; },
+                                   [&]() {
+                                       if (SCAN_PRE) {
+#pragma unroll
+                                           for (int i = 0; i < G; i++) f[i] = ldg(g0 + i * stride);
+                                       }
+                                   });
+#ifdef GRAAL_EXP_NOFOLD   // (A/B build, tools/ab.sh: what the fold's one AND per id costs)
+    const unsigned wm = 0xffffffffu;
+#else
+    const unsigned wm = sa.bm_wmask;
+#endif
     const int4* __restrict__ col4 = sa.col4;
     const int* __restrict__ sub2bin = sa.sub2bin;
     QRaw* __restrict__ queue = sa.queue;
@@ -2899,6 +2923,145 @@ __global__ __launch_bounds__(1024, (G <= 4 ? 8 : 4)) void k_scan(ScanArgs sa, in
             if (sa.done) __hip_atomic_fetch_add(sa.done + DONE_STRIDE * (blockIdx.x % sa.n_done), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (result unused: no-return atomic)
             else __hip_atomic_store(sa.flags + FLAG_STRIDE * blockIdx.x, sa.seq32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+    }
+}
+
+// rowptr[s] = the first contact of row >= s (`row` sorted), s = 0 .. S: the row index of a sorted contact list (built at upload for
+// k_scan_rows; graal_insertions builds one over its own sorted copy when the list arrived in another order)
+__global__ void k_rowptr(int S, const int* __restrict__ row, long long nnz, long long* __restrict__ rowptr)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s > S) return;
+    rowptr[s] = row_lower_bound(row, nnz, s);
+}
+
+// k_scan_rows: k_scan's product through the row index.  A contact is queued iff its row id AND its col id are affected, and the list is
+// sorted by row: the affected rows' slices of `col` hold every such contact.  While contigs are short that is a few dozen rows -- tens
+// of KB instead of the whole row array.  Every block builds the bitmap like k_scan (scan_mark_affected), lists its set bits in id order
+// (the same list in every block), and the grid's waves take the rows round robin: the two offsets of the row, then ALL of its col
+// words in flight together (ROWS_U per lane; a longer row takes another pass), tested against the bitmap, the hits appended to the
+// queue in QRaw's format with one slot reservation per wave pass.  Completion, counters[0] / [2] and the relabel announcement are
+// k_scan's: the consumers cannot tell the producers apart (the ORDER of the entries differs; nothing depends on it).
+// Not for a folded bitmap (a folded bit would list rows that are not affected) and not for timing replays: the host streams there.
+// A few dozen blocks of 256 threads with <= 56 KB of LDS: whatever k_tm's K blocks occupy, a CU with room for these is always left.
+// (ROWS_CAP, scan_rows.h: the affected rows a step of this pass may have -- the LDS list; the host's bound keeps steps within it)
+constexpr int ROWS_U = 8;        // col words per lane and pass: 512 contacts of a row in flight together
+constexpr int ROWS_THREADS = 256;
+template <bool SINGLE_SUB>
+__global__ __launch_bounds__(ROWS_THREADS) void k_scan_rows(ScanArgs sa, const long long* __restrict__ rowptr, const int* __restrict__ col,
+                                                            int n_ids, int fA, Neigh nb, int K)
+{
+    extern __shared__ unsigned s_bm[];
+    __shared__ int s_rows[ROWS_CAP];
+    __shared__ int s_wsum[ROWS_THREADS / 64];
+    __shared__ unsigned long long s_nrel;
+    const int t = threadIdx.x;
+    const int lane = t & 63, wave = t >> 6;
+    if (sa.relabel_seq != 0ull && blockIdx.x == 0 && t == 0)
+        __hip_atomic_store(sa.relabel_flag, sa.relabel_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the relabel's writes were released when it ended)
+    STAMP(8, blockIdx.x == 0 && t == 0);
+    STAMP_BLK(0, t == 0);
+    scan_mark_affected<SINGLE_SUB>(sa, fA, nb, K, [&]() { s_nrel = 0; }, []() {});
+    // ---- the affected rows = the set bits, in id order: every thread counts a run of words, a prefix over the block places them
+    const int wpt = (sa.bitmap_words + ROWS_THREADS - 1) / ROWS_THREADS;
+    const int w_lo = min(t * wpt, sa.bitmap_words), w_hi = min(w_lo + wpt, sa.bitmap_words);
+    int mine = 0;
+    for (int w = w_lo; w < w_hi; w++) mine += __popc(s_bm[w]);
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
+    if (lane == 63) s_wsum[wave] = incl;
+    __syncthreads();
+    int at = incl - mine, total = 0;
+#pragma unroll
+    for (int w = 0; w < ROWS_THREADS / 64; w++) { const int c = s_wsum[w]; if (w < wave) at += c; total += c; }
+    for (int w = w_lo; w < w_hi; w++) {
+        unsigned bits = s_bm[w];
+        while (bits) {
+            const int b = __ffs((int)bits) - 1;
+            bits &= bits - 1;
+            if (at < ROWS_CAP) s_rows[at] = (w << 5) + b;
+            at += 1;
+        }
+    }
+    if (total > ROWS_CAP) {   // (cannot happen: the host offers this pass only within its bound on the affected rows; the step ends as failed)
+        if (blockIdx.x == 0 && t == 0) atomicOr(&sa.counters[6], 1ull);
+        total = ROWS_CAP;
+    }
+    __syncthreads();
+    STAMP_BLK(1, t == 0);
+    STAMP(9, blockIdx.x == 0 && t == 0);
+    const int* __restrict__ sub2bin = sa.sub2bin;
+    QRaw* __restrict__ queue = sa.queue;
+    unsigned long long* __restrict__ counters = sa.counters;
+    unsigned long long n_rel = 0;   // (wave-uniform)
+    const int n_waves = (int)gridDim.x * (ROWS_THREADS / 64);
+    for (int i = (int)blockIdx.x * (ROWS_THREADS / 64) + wave; i < total; i += n_waves) {
+        const int r = __builtin_amdgcn_readfirstlane(s_rows[i]);
+        if (r >= n_ids) continue;   // (the bitmap's padding words hold no bits; the offsets end at n_ids)
+        const long long lo = rowptr[r], hi = rowptr[r + 1];
+        int fx = r, sx = 0;
+        if (!SINGLE_SUB) { const int a = sub2bin[r]; fx = a >> 2; sx = a & 3; }
+        for (long long c0 = lo; c0 < hi; c0 += 64 * ROWS_U) {
+            int cj[ROWS_U];
+#pragma unroll
+            for (int u = 0; u < ROWS_U; u++) {   // (clamped, branch-free: every load of the pass is in flight before the first test)
+                const long long c = c0 + u * 64 + lane;
+                cj[u] = col[c < hi ? c : hi - 1];
+            }
+            unsigned long long bal[ROWS_U];
+            unsigned off[ROWS_U], tot = 0;
+#pragma unroll
+            for (int u = 0; u < ROWS_U; u++) {
+                const long long c = c0 + u * 64 + lane;
+                const int id = cj[u];
+                const bool hit = c < hi && (unsigned)id < (unsigned)n_ids && ((s_bm[(unsigned)id >> 5] >> (id & 31)) & 1u) != 0;
+                bal[u] = __ballot(hit);
+                off[u] = tot;
+                tot += (unsigned)__popcll(bal[u]);
+            }
+            if (tot == 0) continue;
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(&counters[2], (unsigned long long)tot);   // one reservation per wave pass
+            const unsigned slot_base = (unsigned)__shfl(base, 0, 64);
+            n_rel += tot;
+#pragma unroll
+            for (int u = 0; u < ROWS_U; u++) {
+                if (!((bal[u] >> lane) & 1ull)) continue;
+                const unsigned slot = slot_base + off[u] + (unsigned)__popcll(bal[u] & ((1ull << lane) - 1ull));
+                const unsigned cidx = (unsigned)(c0 + u * 64 + lane);   // (contact index: < 2^32)
+                int fy = cj[u], q_slots = 0;
+                if (!SINGLE_SUB) { const int b = sub2bin[cj[u]]; fy = b >> 2; q_slots = sx | ((b & 3) << 2); }
+                unsigned long long* qw = reinterpret_cast<unsigned long long*>(queue + slot);
+                const unsigned long long w0 = (unsigned long long)cidx | ((unsigned long long)sa.seq32 << 32);
+                const unsigned long long w1 = (unsigned long long)(unsigned)fx | ((unsigned long long)(unsigned)fy << 20) | ((unsigned long long)(unsigned)q_slots << 40)
+                                              | ((unsigned long long)(sa.seq32 & 0xfffffu) << 44);
+                if (sa.wt_queue) {   // device-scope (write-through) stores: the reader may be a block of k_tm on another XCD
+                    __hip_atomic_store(qw + 0, w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(qw + 1, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+                    typedef unsigned long long v2u __attribute__((ext_vector_type(2)));
+                    v2u a; a.x = w0; a.y = w1;
+                    *reinterpret_cast<v2u*>(qw) = a;
+                }
+            }
+        }
+    }
+#ifdef GRAAL_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the stamp includes this wave's queue stores)
+#endif
+    STAMP(10, blockIdx.x == 0 && t == 0);
+    STAMP_BLK(2, t == 0);
+    // completion, as k_scan signals it: the slot reservations (atomics with return) of every wave have completed in front of the barrier,
+    // so the queue's length is final when the last block has signalled; the entries may still be in flight (the consumers check the tags)
+    if (lane == 0 && n_rel) atomicAdd(&s_nrel, n_rel);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    if (t == 0) {
+        const unsigned long long nr = s_nrel;
+        if (nr) atomicAdd(&counters[0], nr);
+        if (sa.done) __hip_atomic_fetch_add(sa.done + DONE_STRIDE * (blockIdx.x % sa.n_done), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (result unused: no-return atomic)
+        else __hip_atomic_store(sa.flags + FLAG_STRIDE * blockIdx.x, sa.seq32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -4393,7 +4556,16 @@ struct Ctx {
     bool timing_valid = false;
     bool scan_ready = false;
     bool publish = false;         // k_post publishes the sums to pinned host memory (synchronous single-GPU path)
-    bool want_events = true;      // record the per-kernel HIP events (graal_last_timing)
+    bool want_events = false;     // record the per-kernel HIP events (graal_set_timing).  Off unless asked for: an evaluation that carries an
+                                  // event pair streams (the pairs are documented as pairs around k_scan), and a sampler run should not stream every
+                                  // 8th step for a figure nobody reads
+    // the row index of the contact list (k_scan_rows)
+    long long* rowptr = nullptr;  // [n_sub_total + 1] first contact of row >= s; null: the list is not sorted by row (no index: every step streams)
+    long long longest_row = 0;    // contacts of the longest row (host side: the bound on what the indexed pass can visit)
+    int scan_path = getenv("GRAAL_SCAN_PATH") ? std::min(2, std::max(0, atoi(getenv("GRAAL_SCAN_PATH")))) : 0;   // graal_set_scan_path
+    bool step_indexed = false;    // the evaluation being launched takes its contacts through the row index
+    int repeat_producer = 0;      // a step repeated behind events keeps the producer it had: 1 streaming, 2 indexed (0: decide)
+    long long rc_indexed = 0;     // evaluations whose contacts came through the row index (graal_run_counters)
     // problem
     int n = 0, n_bins = 0, n_sub_total = 0;
     long long nnz = 0;
@@ -4694,10 +4866,10 @@ int scan_grid(const Ctx* h)
     return (int)std::max<long long>(1, std::min<long long>((groups + per_block - 1) / per_block, scan_blocks));
 }
 
-// the streaming pass (see k_scan); dry = timing replay that counts relevant contacts but queues nothing
-int launch_scan(Ctx* h, int fA, const Neigh& nb, int K, int max_id, int dry, hipStream_t st, bool finisher_reads = true)
+// ---- which producer a step gets (k_scan: one pass over the list; k_scan_rows: the affected rows through the row index)
+// bitmap of the producers: bytes of LDS and the word mask (all ones: every id has its own bit)
+void scan_bitmap_cfg(const Ctx* h, size_t* shm_out, unsigned* wmask_out)
 {
-    const int nbk = scan_grid(h), scan_threads = scan_threads_cfg(h);
     // one bit per contact-list id while they fit the LDS budget (393,216 ids); beyond that the ids are folded onto 2^18 bits
     // (ScanArgs::bm_wmask): with a' affected ids a fraction a' / 2^18 of the rows takes the second test for nothing and
     // (a' / 2^18)^2 of the contacts is queued for nothing -- dropped by the consumers' membership test, results unchanged.
@@ -4709,6 +4881,54 @@ int launch_scan(Ctx* h, int fA, const Neigh& nb, int K, int max_id, int dry, hip
         const int b = fold_bits ? fold_bits : 18;
         if ((size_t)1 << b < (size_t)h->n_sub_total) { wmask = (1u << (b - 5)) - 1u; shm = ((size_t)1 << (b - 5)) * 4; }
     }
+    *shm_out = shm; *wmask_out = wmask;
+}
+
+// bound on the rows a step can affect: K + 1 contigs of at most the longest contig's fragments (max_lcont is one commit stale in
+// graal_step's flow; lcont_bound = 2 * max + 2 covers what one commit can do to it), every sub-fragment of a bin a row of its own
+long long rows_bound(const Ctx* h, int K)
+{
+    return scan_rows_bound(K, std::max(std::max(h->max_lcont, h->lcont_bound), 1), h->single_sub);
+}
+
+// 0: the step cannot go through the row index; else why not is in *why (static text)
+bool rows_possible(const Ctx* h, int K, const char** why)
+{
+    size_t shm; unsigned wmask;
+    scan_bitmap_cfg(h, &shm, &wmask);
+    if (!h->rowptr) { *why = "the contact list has no row index (it was not uploaded sorted by row)"; return false; }
+    if (wmask != 0xffffffffu) { *why = "the affected bitmap is folded (more ids than LDS bits): no indexed pass"; return false; }
+    if (rows_bound(h, K) > (long long)ROWS_CAP) { *why = "the contigs are too long for the indexed pass (more affected rows than its list holds)"; return false; }
+    return true;
+}
+
+// The switch.  Indexed iff possible and the contacts the pass can visit at worst, B = rows_bound x longest row, are at most nnz / R.
+// R = 16 by default (GRAAL_SCAN_ROWS_R): the indexed pass has at most 256 waves x 8 loads in flight, the streaming pass the whole chip, so
+// per contact visited it is taken to be an order of magnitude slower; B * 16 <= nnz keeps its worst case below the stream's time
+// (reasoned, with the measured points there).  Per step, stateless; ranks may choose for themselves.
+bool scan_use_rows(const Ctx* h, int K)
+{
+    static const long long R = getenv("GRAAL_SCAN_ROWS_R") ? std::max(1, atoi(getenv("GRAAL_SCAN_ROWS_R"))) : 16;
+    const char* why = nullptr;
+    if (!rows_possible(h, K, &why)) return false;
+    return scan_rows_wins(rows_bound(h, K), h->longest_row, h->nnz, R);
+}
+
+// grid of the indexed pass: a wave per row of the bound, four waves per block, a few dozen blocks at most (every block pays the
+// prologue and the listing of the bitmap; beyond 64 blocks the rows go round)
+int rows_grid(const Ctx* h, int K) { return (int)std::max<long long>(1, std::min<long long>((rows_bound(h, K) + 3) / 4, 64)); }
+
+// blocks of the producer the evaluation being launched uses (the completion targets of k_tm's finishing block)
+int producer_grid(const Ctx* h, int K) { return h->step_indexed ? rows_grid(h, K) : scan_grid(h); }
+
+// the streaming pass (see k_scan) or, for a step that goes through the row index, k_scan_rows; dry = timing replay of the streaming pass
+// that counts relevant contacts but queues nothing
+int launch_scan(Ctx* h, int fA, const Neigh& nb, int K, int max_id, int dry, hipStream_t st, bool finisher_reads = true)
+{
+    const bool rows = !dry && h->step_indexed;
+    const int nbk = rows ? rows_grid(h, K) : scan_grid(h), scan_threads = scan_threads_cfg(h);
+    size_t shm; unsigned wmask;
+    scan_bitmap_cfg(h, &shm, &wmask);
     ScanArgs sa;
     sa.geo = h->geo; sa.link = h->link; sa.mates = h->mates; sa.cnt = h->cnt;
     sa.cbase = h->cbase; sa.perm = h->perm; sa.sub_ids = h->d_sub_ids;
@@ -4726,7 +4946,11 @@ int launch_scan(Ctx* h, int fA, const Neigh& nb, int K, int max_id, int dry, hip
     sa.n_done = scan_done_n();
     if (sa.done) for (int c = 0; c < sa.n_done; c++) h->scan_done_total[c] += (unsigned long long)((nbk - c + sa.n_done - 1) / sa.n_done);
     if (nbk > MAX_SCAN_BLOCKS) return fail(h, GRAAL_E_ARG, "GRAAL_SCAN_BLOCKS too large");
-    if (scan_groups_cfg() == 8) {
+    if (rows) {
+        if (h->single_sub) k_scan_rows<true><<<nbk, ROWS_THREADS, shm, st>>>(sa, h->rowptr, h->col, h->n_sub_total, fA, nb, K);
+        else k_scan_rows<false><<<nbk, ROWS_THREADS, shm, st>>>(sa, h->rowptr, h->col, h->n_sub_total, fA, nb, K);
+        h->rc_indexed += 1;
+    } else if (scan_groups_cfg() == 8) {
         if (h->single_sub) k_scan<true, 8><<<nbk, scan_threads, shm, st>>>(sa, fA, nb, K, max_id, dry);
         else k_scan<false, 8><<<nbk, scan_threads, shm, st>>>(sa, fA, nb, K, max_id, dry);
     } else if (scan_groups_cfg() == 2) {
@@ -5258,7 +5482,7 @@ void graal_destroy(graal_ctx* h)
         // ... and whatever this handle's kernels were launched on besides its own streams (graal_eval_candidates_q takes the CALLER'S stream: the
         // torch path of exchange="rccl"): nothing of this process may still touch the buffers, pinned words and the registered segment freed below
         (void)hipDeviceSynchronize();
-        void* ptrs[] = {h->soa_mem[0], h->soa_mem[1], h->geo, h->stat, h->sub_rec, h->sub_rec8, h->sub_lab16, h->d_ubins, h->d_ln_tab, h->sub2bin, h->row, h->col, h->cnt, h->queue, h->d_sub_ids, h->d_acc, h->tm_done, h->d_sync, h->d_done, h->d_wq, h->d_flags, h->d_slist, h->d_uset, h->d_cls, h->d_cls_n, h->stat_frag, h->d_dup_bins, h->d_dup_index,
+        void* ptrs[] = {h->soa_mem[0], h->soa_mem[1], h->geo, h->stat, h->sub_rec, h->sub_rec8, h->sub_lab16, h->d_ubins, h->d_ln_tab, h->sub2bin, h->row, h->col, h->cnt, h->queue, h->rowptr, h->d_sub_ids, h->d_acc, h->tm_done, h->d_sync, h->d_done, h->d_wq, h->d_flags, h->d_slist, h->d_uset, h->d_cls, h->d_cls_n, h->stat_frag, h->d_dup_bins, h->d_dup_index,
                         h->d_dispatcher, h->d_collector, h->d_sub_ids_all, h->d_rep_obs,
                         h->keys, h->keys_sorted, h->o2n, h->len_of2[0], h->len_of2[1], h->contig_off2[0], h->contig_off2[1], h->perm, h->pstart, h->cbase, h->link, h->mates, h->cub_tmp, h->tabs, h->step_hdr, h->d_args, h->d_chg, h->d_part,
                         h->d_scalars, h->d_qout, h->d_dref, h->d_dist};
@@ -5492,8 +5716,10 @@ static int upload_contacts_impl(graal_ctx* h, const int32_t* row, const int32_t*
     long long c_lf_q = 0;
     long long lf_small[16];
     for (int i = 0; i < 16; i++) lf_small[i] = llrint(lf_term((double)i) * Q_SCALE);
+    RowRuns runs;   // `row` non-decreasing: the list gets a row index (k_scan_rows); sorted: a run of equal row ids is a row
     for (int64_t i = 0; i < nnz; i++) {
         if (row[i] < 0 || col[i] >= h->n_sub_total || row[i] >= col[i]) return fail(h, GRAAL_E_ARG, "contacts need 0 <= row < col < n_sub_total");
+        runs.add(row[i]);
         const float c = count[i];
         if (!(c > 0.0f) || !(c < 1.0e30f)) return fail(h, GRAAL_E_ARG, "contact counts must be > 0 and finite");
         if (h->has_rep && (h->h_dup_index[s2b_host(h, row[i])] >= 0 || h->h_dup_index[s2b_host(h, col[i])] >= 0))
@@ -5502,6 +5728,8 @@ static int upload_contacts_impl(graal_ctx* h, const int32_t* row, const int32_t*
         c_lf_q += (c < 16.0f && (float)ci == c) ? lf_small[ci] : llrint(lf_term((double)c) * Q_SCALE);
     }
     if (h->row) { (void)hipFree(h->row); (void)hipFree(h->col); (void)hipFree(h->cnt); (void)hipFree(h->queue); h->row = h->col = h->cnt = nullptr; h->queue = nullptr; }
+    if (h->rowptr) { (void)hipFree(h->rowptr); h->rowptr = nullptr; }
+    h->longest_row = 0;
     const size_t bytes = sizeof(int) * (size_t)(nnz + 8); // +8: int4 tail reads stay in bounds
     CK(hipMalloc(&h->row, bytes)); CK(hipMalloc(&h->col, bytes)); CK(hipMalloc(&h->cnt, bytes));
     CK(hipMemset(h->row, 0, bytes)); CK(hipMemset(h->col, 0, bytes));
@@ -5512,6 +5740,13 @@ static int upload_contacts_impl(graal_ctx* h, const int32_t* row, const int32_t*
         CK(hipMemcpy(h->row, row, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
         CK(hipMemcpy(h->col, col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
         CK(hipMemcpy(h->cnt, count, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice));
+    }
+    if (runs.sorted && nnz > 0) {   // the row index: (ids + 1) 64-bit offsets, one binary search per id over the uploaded list
+        CK(hipMalloc(&h->rowptr, sizeof(long long) * ((size_t)h->n_sub_total + 1)));
+        k_rowptr<<<blocks_for((long long)h->n_sub_total + 1, 256), 256, 0, h->stream>>>(h->n_sub_total, h->row, nnz, h->rowptr);
+        CK(hipGetLastError());
+        CK(hipStreamSynchronize(h->stream));
+        h->longest_row = runs.longest;
     }
     h->nnz = nnz; h->c_lf_q = c_lf_q; h->have_contacts = true;
     // the observed counts of every bin's OWN sub-fragment pairs (own_pixel_q): contacts whose two sub-fragments belong to one bin
@@ -6021,6 +6256,16 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
         nb.fB[k] = k < K ? fB[k] : -1;
         if (k < K && (fB[k] < 0 || fB[k] >= h->n)) return fail(h, GRAAL_E_ARG, "fB out of range");
     }
+    // the step's producer, decided before anything is launched (k_tm's completion targets follow its grid).  An evaluation that carries a
+    // HIP event pair streams: the pairs are pairs around the streaming kernel (graal_scan_times, 4 bytes x contacts / time).  A step
+    // repeated behind events keeps the producer it had.
+    const bool ev = h->want_events && (h->eval_calls % h->event_every == 0);
+    {
+        const char* why = nullptr;
+        const int forced = h->repeat_producer ? h->repeat_producer : h->scan_path;
+        if (forced == 2 && !rows_possible(h, K, &why)) return fail(h, GRAAL_E_STATE, why);
+        h->step_indexed = forced == 2 || (forced == 0 && !ev && scan_use_rows(h, K));
+    }
     CK(hipSetDevice(h->device));
     hipStream_t st = stream_v ? (hipStream_t)stream_v : h->stream;
     const DevArgs* A = h->d_args + h->cur;
@@ -6049,9 +6294,9 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
     ta.perm = h->perm; ta.reach_bp = reach_bp(h); ta.tm_done = h->tm_done;
     static const bool no_finisher = getenv("GRAAL_NO_FINISHER") != nullptr; // always finish with k_fin (diagnostics)
     ta.flags = h->d_flags;
-    ta.sync = h->d_sync; ta.n_scan_blocks = scan_grid(h);
+    ta.sync = h->d_sync; ta.n_scan_blocks = producer_grid(h, K);
     ta.done = scan_done_counter() ? h->d_done : nullptr; ta.n_done = scan_done_n();
-    for (int c = 0; c < N_DONE; c++) ta.done_target[c] = c < ta.n_done ? h->scan_done_total[c] + (unsigned long long)((scan_grid(h) - c + ta.n_done - 1) / ta.n_done) : 0ull;
+    for (int c = 0; c < N_DONE; c++) ta.done_target[c] = c < ta.n_done ? h->scan_done_total[c] + (unsigned long long)((producer_grid(h, K) - c + ta.n_done - 1) / ta.n_done) : 0ull;
     // (late stage -- a few long contigs hold nearly every fragment: nearly every step needs k_fin anyway, so it is launched
     // right behind the scan instead of after k_tm's verdict has made the round trip through the host, ~10 us per step)
     const bool late_stage = h->max_lcont > 128 && (long long)h->n_contigs * 64 < (long long)h->n;
@@ -6065,7 +6310,9 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
     ta.strict_inline_m = strict_dense_cfg() ? -1 : (mid ? 0 : STRICT_INLINE_M);
     // (a long scan -- millions of contacts: the copy is over before the scan is.  A short one -- the C2 / C3 stand-ins -- is complete before the
     // tables are: the copy would stand in front of the contacts, two round trips for a handful of them; C2 stand-in 130 -> 137 us per step)
-    ta.stage_tables = h->nnz >= 4000000 ? 1 : 0;
+    // The indexed pass is always a short scan: no copy.  (GRAAL_STAGE_TABLES = 0 / 1 overrides, for A/B runs)
+    static const int stage_env = getenv("GRAAL_STAGE_TABLES") ? atoi(getenv("GRAAL_STAGE_TABLES")) : -1;
+    ta.stage_tables = stage_env >= 0 ? (stage_env ? 1 : 0) : ((!h->step_indexed && h->nnz >= 4000000) ? 1 : 0);
     ta.host_res = (h->publish && (world == 1 || h->x_host) && !no_finisher && h->finisher_ok && !h->has_rep && !late_stage && !mid && !(strict && strict_dense_cfg())) ? h->res_dev : nullptr;
     ta.wait_ticks = fin_wait_ticks(h);
     ta.counters = (unsigned long long*)(h->d_scalars + 10); ta.queue = h->queue; ta.cnt = h->cnt; ta.multi = h->single_sub ? 0 : 1; ta.stat = h->stat_frag;
@@ -6083,7 +6330,6 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
     CK(hipGetLastError());
     // (the event that orders a chip-filling k_fin / the strict kernels behind k_tm is recorded where they are launched)
     // (2) the streaming pass, with a HIP event pair around it on every event_every-th call
-    const bool ev = h->want_events && (h->eval_calls % h->event_every == 0);
     h->ev_this_call = ev;
     h->eval_calls += 1;
     const size_t slot = (size_t)(h->ring_calls % (long long)(h->ring.size() / 2));
@@ -6276,7 +6522,10 @@ static int eval_sync(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int
         CK(hipMemset(h->d_sync, 0, 32 * sizeof(unsigned long long)));
         CK(hipDeviceSynchronize());
         res[0] = 0;
-        return eval_sync(h, fA, fB, K, max_id, rank, world, q_sum, c_sum);
+        h->repeat_producer = h->step_indexed ? 2 : 1;   // (the repeat keeps the producer the step had)
+        const int rc_rep = eval_sync(h, fA, fB, K, max_id, rank, world, q_sum, c_sum);
+        h->repeat_producer = 0;
+        return rc_rep;
     }
     if (res[0] == -want) return fail(h, GRAAL_E_HIP, "timed out waiting for the candidate tables / the scan (a kernel of the step did not run)");
     __sync_synchronize();
@@ -6513,6 +6762,20 @@ int graal_set_finisher(graal_ctx* h, int32_t enabled)
     if (!h) return GRAAL_E_ARG;
     h->finisher_ok = enabled != 0;
     h->gave_up = 0;
+    return GRAAL_OK;
+}
+
+int graal_set_scan_path(graal_ctx* h, int32_t path)
+{
+    if (!h || path < 0 || path > 2) return GRAAL_E_ARG;
+    if (path == 2) {
+        const char* why = nullptr;
+        if (!h->have_contacts) return fail(h, GRAAL_E_STATE, "upload the contacts first");
+        size_t shm; unsigned wmask;
+        scan_bitmap_cfg(h, &shm, &wmask);
+        if (!h->rowptr || wmask != 0xffffffffu) { (void)rows_possible(h, 1, &why); return fail(h, GRAAL_E_STATE, why ? why : "no indexed pass for this map"); }
+    }
+    h->scan_path = path;
     return GRAAL_OK;
 }
 
@@ -6755,7 +7018,7 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
     if (!h || !out) return GRAAL_E_ARG;
     out[0] = h->rc_evals; out[1] = h->rc_repeats; out[2] = h->spin_ok ? 1 : 0; out[3] = h->rc_gwait; out[4] = h->rc_gevent;
     out[5] = h->rc_flat; out[6] = h->rc_need_fin; out[7] = h->gave_up; out[8] = h->rc_list_grown; out[9] = (int64_t)h->slist_cap;
-    out[10] = h->rc_carry_repairs; out[11] = 0;
+    out[10] = h->rc_carry_repairs; out[11] = h->rc_indexed;
     return GRAAL_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include "frag_ops.h"
 #include "strict_sets.h"
+#include "scan_rows.h"
 
 using namespace graal;
 
@@ -317,5 +318,18 @@ int hc_union_check(int fA, const int32_t* fB, int K, int max_id, int32_t* const*
     for (auto& kv : seen) if (kv.second != 1) bad++;
     return bad;
 }
+
+// ---- the row index's host side (scan_rows.h): out[0] = sorted, out[1] = longest run; rowptr[S + 1] by the kernel's binary search
+void hc_row_index(const int32_t* row, int64_t nnz, int32_t S, int64_t* out, int64_t* rowptr)
+{
+    RowRuns runs;
+    for (int64_t i = 0; i < nnz; i++) runs.add(row[i]);
+    out[0] = runs.sorted ? 1 : 0; out[1] = runs.longest;
+    if (rowptr && runs.sorted) for (int32_t s = 0; s <= S; s++) rowptr[s] = row_lower_bound(row, nnz, s);
+}
+
+int64_t hc_scan_rows_bound(int K, int64_t lc, int single_sub) { return scan_rows_bound(K, lc, single_sub != 0); }
+int hc_scan_rows_wins(int64_t rows, int64_t longest_row, int64_t nnz, int64_t R) { return scan_rows_wins(rows, longest_row, nnz, R) ? 1 : 0; }
+int hc_scan_rows_cap() { return ROWS_CAP; }
 
 } // extern "C"

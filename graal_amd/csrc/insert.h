@@ -17,8 +17,9 @@
 // contacts, a per-(P, T) sum, plus, for each contact inside the window at its junction, Q(term) - Q(far term) -- the same Q-rounded terms.
 // Kernels, all on the engine's stream:
 //   k_jn_count / scan / k_ln_prep(min_frags 1) / k_in_piece -- links.h's slots and records; a contig record's `elig` then marks a piece;
-//   k_in_rowptr -- row offsets of the contact list by row (a binary search per sub-fragment), for k_in_shift.  The upload takes the
-//                 list in any order: k_in_unsorted checks it, and an unsorted list is radix-sorted by row into a permutation first;
+//   row offsets of the contact list by row, for k_in_shift: the engine's own row index when the list was uploaded sorted by row (built
+//                 once per upload, k_rowptr); the upload takes the list in any order: k_in_unsorted checks it, an unsorted list is
+//                 radix-sorted by row into a permutation first and k_rowptr runs over that copy;
 //   k_in_nnz<COUNT> -- streams the contact list, 64 contacts per wave.  For a contact between x of a piece and y of a target the junctions
 //                 that keep it inside the window are a run of slots on each side of y: the wave walks them outward (both pieces of a
 //                 pair, both orientations, both sides) until every lane's inserted gap passed reach_bp, emitting (f << 32 | head << 1 | rev)
@@ -129,19 +130,6 @@ __global__ void k_in_iota(int m, int* __restrict__ v)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < m) v[k] = k;
-}
-
-// rowptr[s] = the first contact of row >= s (`row` sorted), s = 0 .. S
-__global__ void k_in_rowptr(int S, const int* __restrict__ row, long long nnz, long long* __restrict__ rowptr)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s > S) return;
-    long long lo = 0, hi = nnz;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (row[mid] < s) lo = mid + 1; else hi = mid;
-    }
-    rowptr[s] = lo;
 }
 
 __device__ __forceinline__ unsigned long long in_key(int f, int head, int rev)
@@ -684,8 +672,13 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
             rows = B->srow;
             perm = B->perm;
         }
-        k_in_rowptr<<<blocks_for((long long)S + 1, 256), 256, 0, s>>>(S, rows, h->nnz, B->rowptr);
-        IN_CK(hipGetLastError());
+        // (a list uploaded sorted by row has the engine's own row index, built at upload: k_rowptr)
+        const long long* rowptr = B->rowptr;
+        if (!uns && h->rowptr) rowptr = h->rowptr;
+        else {
+            k_rowptr<<<blocks_for((long long)S + 1, 256), 256, 0, s>>>(S, rows, h->nnz, B->rowptr);
+            IN_CK(hipGetLastError());
+        }
         // ---- count pass: upper bounds of the distinct keys of the two tables
         const long long waves = (h->nnz + 63) / 64;
         const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
@@ -806,7 +799,7 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
                                           B->bad);
         IN_CK(hipGetLastError());
         k_in_shift<<<wblocks, 256, 0, s>>>(m, B->lead, B->piece, B->after, B->slot, B->lab, B->ctg, B->fr, B->sub, h->stat_frag, h->d_sub_ids,
-                                           B->rowptr, perm, h->col, h->cnt, h->nfpb, h->par, reach, B->sh, B->shbad);
+                                           rowptr, perm, h->col, h->cnt, h->nfpb, h->par, reach, B->sh, B->shbad);
         IN_CK(hipGetLastError());
         if (mq) {
             k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, B->slot, B->lab, B->ctg, B->fr, h->nfpb, h->par, B->mir, B->mirbad);

@@ -50,7 +50,7 @@ _f64p = ctypes.POINTER(ctypes.c_double)
 SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_error", "graal_set_params",
            "graal_upload_subfrags", "graal_upload_repeats", "graal_upload_contacts", "graal_upload_contacts_f32", "graal_upload_frags", "graal_download_frags",
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
-           "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
+           "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_set_scan_path", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
            "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
@@ -141,6 +141,7 @@ def load():
         L.graal_insertions_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, ctypes.POINTER(ctypes.c_uint8), _i64p, _i64p,
                                              ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+        L.graal_set_scan_path.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_finisher.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_mode.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_scan_times.argtypes = [ctypes.c_void_p, ctypes.c_int32, _f32p]
@@ -628,6 +629,11 @@ class Engine:
     def set_timing(self, enabled):
         self._ck(self._L.graal_set_timing(self._h, int(enabled)), "graal_set_timing")
 
+    def set_scan_path(self, path):
+        """graal_set_scan_path: 0 = the engine chooses per step, 1 = always stream the contact list, 2 = always take the step's contacts
+        through the row index (an error where that is not possible)."""
+        self._ck(self._L.graal_set_scan_path(self._h, int(path)), "graal_set_scan_path")
+
     def last_timing(self):
         t = np.zeros(4, dtype=np.float32)
         self._ck(self._L.graal_last_timing(self._h, t.ctypes.data_as(_f32p)), "graal_last_timing")
@@ -675,13 +681,14 @@ class Engine:
 
     def run_counters(self):
         """include/graal_hip.h: graal_run_counters -- evaluations, repeats behind events (`fallbacks`), in-kernel waits in use,
-        k_strict2 launches behind k_gprep's word / behind the event, k_strict_flat launches, hand-overs to a finishing kernel, finisher give-ups."""
+        k_strict2 launches behind k_gprep's word / behind the event, k_strict_flat launches, hand-overs to a finishing kernel, finisher give-ups,
+        ..., evaluations whose contacts came through the row index (`indexed_passes`)."""
         c = np.zeros(12, dtype=np.int64)
         self._ck(self._L.graal_run_counters(self._h, c.ctypes.data_as(_i64p)), "graal_run_counters")
         return dict(zip(("evaluations", "fallbacks", "in_kernel_waits_in_use", "strict2_behind_the_word", "strict2_behind_the_event",
                          "flat_launches", "handed_to_a_finishing_kernel", "finisher_gave_up", "unit_list_grown", "unit_list_capacity",
-                         "carried_totals_repaired"),
-                        (int(x) for x in c[:11])))
+                         "carried_totals_repaired", "indexed_passes"),
+                        (int(x) for x in c[:12])))
 
     def last_counters(self):
         c = np.zeros(4, dtype=np.int64)

@@ -194,8 +194,17 @@ int graal_upload_distance_ref(graal_ctx* h, const int32_t* init_prev, const int3
 int graal_genome_distance(graal_ctx* h, int64_t* half_units);
 
 /* HIP event pairs around the streaming kernel of graal_eval_candidates*: enabled = n > 0 records a pair on every n-th
- * call (default 8; each pair costs a few microseconds of command-processor gaps on the step's critical path), 0 = off */
+ * call (each pair costs a few microseconds of command-processor gaps on the step's critical path), 0 = off.  Off by default: an
+ * evaluation that carries a pair always STREAMS the contact list (the pair is a pair around the streaming kernel, priced against
+ * 4 bytes x contacts), also where the engine would have taken the step's contacts through the row index. */
 int graal_set_timing(graal_ctx* h, int32_t enabled);
+/* Which producer finds a step's contacts.  A list uploaded sorted by row gets a row index (offsets per id, built once per upload);
+ * while the affected contigs are short, a step then reads only the affected rows' col words (k_scan_rows) instead of streaming the
+ * whole row array (k_scan).  path = 0: the engine chooses per step (indexed iff an index exists, the affected bitmap is not folded and
+ * the bound on the contacts the indexed pass can visit is a small share of the list), 1: always stream, 2: always indexed -- an error
+ * here or at the evaluation where that is not possible (no index, folded bitmap, contigs too long for the pass), never a silent
+ * stream.  The default is read once from GRAAL_SCAN_PATH.  Results do not depend on the producer (integer sums). */
+int graal_set_scan_path(graal_ctx* h, int32_t path);
 /* duration (ms) of the streaming scan kernel of the last graal_eval_candidates* call: a pair of HIP events recorded
  * around it on the stream it ran on; out[1] = k_scan, the other entries are 0 (per-kernel times of k_prep / k_post come
  * from rocprofv3).  graal_scan_times returns the last n calls (a ring of 1024 event pairs). */
@@ -247,7 +256,7 @@ int graal_upload_own_obs(graal_ctx* h, const float* own, int32_t n_bins);
  * out[6] = evaluations the table kernel handed to a finishing kernel through the host, out[7] = times its finisher gave up waiting for
  * the scan, out[8] = evaluations repeated with a longer unit list (the tiled kernel's list starts at a soft cap instead of its quadratic
  * worst case and grows when a step overflows it), out[9] = that list's capacity now (entries of 8 bytes), out[10] = graal_step calls with flag 16 whose own-pixel
- * correction was unknown and that evaluated the layout in full instead (graal_take_carry_correction), out[11] = 0 (reserved).
+ * correction was unknown and that evaluated the layout in full instead (graal_take_carry_correction), out[11] = evaluations whose contacts came through the row index (graal_set_scan_path).
  * bench.py reports out[1] as `fallbacks`. */
 int graal_run_counters(graal_ctx* h, int64_t out[12]);
 
