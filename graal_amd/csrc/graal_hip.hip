@@ -5741,7 +5741,9 @@ static int upload_contacts_impl(graal_ctx* h, const int32_t* row, const int32_t*
         CK(hipMemcpy(h->col, col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
         CK(hipMemcpy(h->cnt, count, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice));
     }
-    if (runs.sorted && nnz > 0) {   // the row index: (ids + 1) 64-bit offsets, one binary search per id over the uploaded list
+    // (an EMPTY list -- a rank whose shard holds nothing -- is a sorted list: its offsets are all zero and every row's slice is empty; the
+    // switch never takes it, 0 contacts are never R times a bound, but a forced indexed pass finds what the streaming pass finds: nothing)
+    if (runs.sorted) {   // the row index: (ids + 1) 64-bit offsets, one binary search per id over the uploaded list
         CK(hipMalloc(&h->rowptr, sizeof(long long) * ((size_t)h->n_sub_total + 1)));
         k_rowptr<<<blocks_for((long long)h->n_sub_total + 1, 256), 256, 0, h->stream>>>(h->n_sub_total, h->row, nnz, h->rowptr);
         CK(hipGetLastError());

@@ -33,13 +33,26 @@ def lf_term(ob):
     return out
 
 
+def _pow32(x, y):
+    """powf as the reference's float32 code sees it: the correctly rounded float32 power (through float64, rounded once).  numpy's own
+    float32 power and exp are vectorised approximations a few ulp off; a C powf / expf is within an ulp of the exact value, and the
+    two roundings agree but for the rare double-rounding case.  Where a layout's cis mass is a large part of |logL| (a ring of a few
+    hundred fragments) those ulps were 2e-7 of the mass -- more than the re-score's tolerance."""
+    return np.power(np.asarray(x, dtype=np.float64), np.float64(y)).astype(np.float32)
+
+
+def _exp32(x):
+    """expf, likewise."""
+    return np.exp(np.asarray(x, dtype=np.float64)).astype(np.float32)
+
+
 def rippe_f32(s, p):
     s = np.asarray(s, dtype=np.float32)
     kuhn, lm, c1, slope, d, d_max, fact, v = [f32(x) for x in p]
     ok = (s > 0) & (s < d_max)
     ss = np.where(ok, s, f32(1.0)).astype(np.float32)
-    inner = (np.power(ss * lm / kuhn, f32(2.0), dtype=np.float32) + d).astype(np.float32)
-    r = (c1 * np.power(ss, slope, dtype=np.float32) * np.exp((d - f32(2)) / inner, dtype=np.float32)) * fact
+    inner = (_pow32(ss * lm / kuhn, f32(2.0)) + d).astype(np.float32)
+    r = (c1 * _pow32(ss, slope) * _exp32((d - f32(2)) / inner)) * fact
     r = np.where(ok, r, f32(0)).astype(np.float32)
     return np.maximum(r, v)
 
@@ -55,12 +68,10 @@ def rippe_circ_f32(s, s_tot, p):
     n = (K * ss * (s_tot - ss) / s_tot).astype(np.float32)
     n = np.where(ok, n, f32(1.0)).astype(np.float32)
     norm_lin = rippe_f32(ss, p)
-    k3 = np.power(kuhn, f32(-3.0), dtype=np.float32)
-    norm_circ = (k3 * np.power(nmax, slope, dtype=np.float32)
-                 * np.exp((d - f32(2.0)) / (np.power(nmax, f32(2.0), dtype=np.float32) + d), dtype=np.float32)) * fact
+    k3 = _pow32(kuhn, f32(-3.0))
+    norm_circ = (k3 * _pow32(nmax, slope) * _exp32((d - f32(2.0)) / (_pow32(nmax, f32(2.0)) + d))) * fact
     with np.errstate(invalid="ignore", divide="ignore"):
-        val = (k3 * np.power(n, slope, dtype=np.float32)
-               * np.exp((d - f32(2.0)) / (np.power(n, f32(2.0), dtype=np.float32) + d), dtype=np.float32)) * fact
+        val = (k3 * _pow32(n, slope) * _exp32((d - f32(2.0)) / (_pow32(n, f32(2.0)) + d))) * fact
         r = (val * norm_lin / norm_circ).astype(np.float32)
     r = np.where(ok, r, f32(0)).astype(np.float32)
     return np.maximum(r, v)

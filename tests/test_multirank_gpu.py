@@ -21,6 +21,10 @@ def _problem(which="sub3"):
         # reference arithmetic (the default)
         # (10 contigs of ~50 bins: not the late stage's direct launch of the tiled kernels -- k_tm sends every rank to k_strict_flat)
         return synth.make_problem(n_bins=500, nnz=15000, n_sub=1, seed=19, contig_weights=(1,) * 10, mean_len_bp=1500.0, accu=1, param=par)
+    if which == "mid6k":
+        # "mid" with a list of between one and two of the 4,096-contact blocks that graal_amd.dist.shard_take deals out: on three ranks, rank 0
+        # holds one block, rank 1 the rest -- the row at the boundary is split between them -- and rank 2 nothing at all
+        return synth.make_problem(n_bins=500, nnz=6000, n_sub=1, seed=19, contig_weights=(1,) * 10, mean_len_bp=1500.0, accu=1, param=par)
     if which == "rep":
         # repeated bins (allow_repeats: simulation_loader.py:182-280): their pixels are priced densely over the active copies -- the candidates'
         # part dealt to the ranks item by item, the full evaluation's part pixel by pixel (k_rep_delta, k_rep_full)
@@ -52,7 +56,7 @@ def _make(P, rng, group, exchange=None):
                    device=0, rng=rng, group=group, param_simu=P["param_simu"], compute_dist=False, exchange=exchange)
 
 
-def _run(group, exchange=None, which="sub3", expect_repeat=False):
+def _run(group, exchange=None, which="sub3", expect_repeat=False, counters=None):
     from graal_amd import em
     P = _problem(which)
     rng = np.random.RandomState(5)
@@ -76,6 +80,8 @@ def _run(group, exchange=None, which="sub3", expect_repeat=False):
         assert g.engine.run_counters()["fallbacks"] >= 1, "no step was repeated on rank %d" % group.rank
     if which == "sub3mix" and g._own_corr:
         assert g.engine.run_counters()["carried_totals_repaired"] > 0, "no commit mirrored a bin of mixed RF counts: the case tests nothing"
+    if counters is not None:
+        counters.update(g.engine.run_counters())
     g.gpu_vect_frags.copy_from_gpu()
     out = (t.mutations(), np.concatenate(scores), {k: np.copy(v) for k, v in g.gpu_vect_frags.as_dict().items()},
            g.eval_likelihood())
@@ -83,11 +89,13 @@ def _run(group, exchange=None, which="sub3", expect_repeat=False):
     return out
 
 
-def _worker(rank, world, port, q, exchange, which="sub3"):
+def _worker(rank, world, port, q, exchange, which="sub3", scan_path=None):
     import torch.distributed as td
     from graal_amd import dist as gdist
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
+    if scan_path is not None:      # (read when the engine is created: 0 the engine's own choice, 1 streaming, 2 through the row index)
+        os.environ["GRAAL_SCAN_PATH"] = str(scan_path)
     expect_repeat = which.endswith("+timeout")
     if which.endswith("+timeout"):
         # ONE rank's in-kernel wait for its scan runs out at once (the engine reads the bound when the handle is created): its step ends as
@@ -97,8 +105,9 @@ def _worker(rank, world, port, q, exchange, which="sub3"):
             os.environ["GRAAL_TM_SPIN_TICKS"] = "1"
     td.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        mut, scores, soa, full = _run(gdist.Group(rank, world), exchange, which, expect_repeat)
-        q.put((rank, mut, scores, soa, full))
+        rc = {}
+        mut, scores, soa, full = _run(gdist.Group(rank, world), exchange, which, expect_repeat, counters=rc)
+        q.put((rank, mut, scores, soa, full, rc))
     finally:
         td.destroy_process_group()
 
@@ -142,12 +151,112 @@ def test_ranks_reproduce_the_single_rank_run_bit_for_bit(world, exchange, which)
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
-    for rank, mut, scores, soa, full in res:
+    for rank, mut, scores, soa, full, _ in res:
         assert np.array_equal(mut, ref_mut), rank
         assert np.array_equal(scores, ref_scores), rank          # bit-identical float64 scores
         for k in ref_soa:
             assert np.array_equal(soa[k], ref_soa[k]), (rank, k)
         assert full == ref_full
+
+
+def _rank_child(rank, world, port, exchange, which, scan_path, out_path):
+    """(one rank as a process of its own, started under `timeout`: what _worker puts into its queue goes to a file)"""
+    import pickle
+
+    class ToFile:
+        def put(self, item):
+            with open(out_path, "wb") as f:
+                pickle.dump(item, f)
+
+    _worker(rank, world, port, ToFile(), exchange, which, scan_path)
+
+
+def _ranks(world, exchange, which, scan_path, tmp_path):
+    """What `world` ranks on this GPU leave behind, by rank; every rank a child under a time limit of its own."""
+    import pickle
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "GRAAL_SCAN_PATH", "GRAAL_SCAN_ROWS_R")}
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    outs = [str(tmp_path / ("rank%d.pkl" % r)) for r in range(world)]
+    procs = [subprocess.Popen(["timeout", "-k", "10", "300", sys.executable, "-c", "import tests.test_multirank_gpu as t; t._rank_child(%d, %d, %d, %r, %r, %r, %r)"
+                               % (r, world, port, exchange, which, scan_path, outs[r])], cwd=root, env=env, stdout=subprocess.PIPE,
+                              stderr=subprocess.STDOUT, text=True) for r in range(world)]
+    said = [p.communicate()[0] for p in procs]
+    for r, p in enumerate(procs):
+        assert p.returncode == 0, (r, p.returncode, said[r][-3000:])
+    res = []
+    for path in outs:
+        with open(path, "rb") as f:
+            res.append(pickle.load(f))
+    return sorted(res, key=lambda r: r[0])
+
+
+def _shards(which, world):
+    """The ranks' shards of a problem's list, from numpy alone: (index arrays, rows split between ranks, per rank the rows it holds nothing of)."""
+    from graal_amd import dist as gdist
+    from tests import scan_rows_reference as R
+    row = _problem(which)["coo_row"]
+    ix = [gdist.shard_take(len(row), r, world) for r in range(world)]
+    split, absent = R.split_rows(row, ix)
+    return ix, split, absent
+
+
+def _same_as_the_anchor(res, ref):
+    ref_mut, ref_scores, ref_soa, ref_full = ref
+    for rank, mut, scores, soa, full, _ in res:
+        assert np.array_equal(mut, ref_mut), rank
+        assert np.array_equal(scores, ref_scores), rank          # bit-identical float64 scores
+        for k in ref_soa:
+            assert np.array_equal(soa[k], ref_soa[k]), (rank, k)
+        assert full == ref_full
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("scan_path", [2, 0])
+@pytest.mark.parametrize("world,exchange,which", [(2, "host", "mid"), (2, "host", "sub3"), (2, "rccl", "mid")])
+def test_ranks_with_a_row_index_over_their_own_shard(world, exchange, which, scan_path, tmp_path):
+    """Every rank indexes ITS shard of the (row, col)-sorted list -- blocks of 4,096 contacts dealt round robin (graal_amd.dist.shard_take): a
+    row can be split between ranks or be absent from one ("mid": tests/test_scan_rows_reference_cpu.py shows both) -- and finds a step's
+    contacts through it: forced (GRAAL_SCAN_PATH=2: every evaluation of every rank is indexed) or by its own choice (0).  Bit for bit the
+    one-rank anchor of the run, which chooses for itself over the whole list."""
+    ix, split, absent = _shards(which, world)
+    if which == "mid":        # 15,000 contacts: rank 0 holds blocks 0 and 2, rank 1 blocks 1 and 3 -- three rows are cut by a block boundary
+        assert all(len(i) > 4096 for i in ix) and len(split) >= 1 and all(len(a) >= 1 for a in absent)
+    else:                     # 2,500 contacts: one block -- rank 1 holds nothing, and its index is the empty list's
+        assert len(ix[0]) == 2500 and len(ix[1]) == 0
+    res = _ranks(world, exchange, which, scan_path, tmp_path)
+    _same_as_the_anchor(res, _ref(which, per_step_evaluation=exchange != "host"))
+    for rank, _, _, _, _, rc in res:
+        assert rc["fallbacks"] == 0, (rank, rc)
+        if exchange == "host":
+            assert rc["evaluations"] >= 50, (rank, rc)
+            if scan_path == 2:
+                assert rc["indexed_passes"] == rc["evaluations"], (rank, rc)
+        elif scan_path == 2:
+            # (`evaluations` counts the synchronous entry point, which the all-reduce flow does not go through: 0 there.  A forced indexed
+            # evaluation is indexed or an error, so the ranks' counts are the steps that evaluated -- the same on every rank)
+            assert rc["indexed_passes"] >= 50 and rc["indexed_passes"] == res[0][5]["indexed_passes"], (rank, rc)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("scan_path", [0, 2])
+def test_a_rank_with_an_empty_shard(scan_path, tmp_path):
+    """Three ranks on a list of 6,000 contacts: rank 0 holds one block of 4,096, rank 1 the rest, rank 2 nothing.  An empty list is a sorted
+    list: its row index is all zeros, every row's slice is empty.  By its own choice the empty rank never takes it (0 contacts are never 16
+    times the bound) and streams over nothing; forced, its indexed pass queues nothing.  Either way the run is the one-rank run."""
+    ix, split, absent = _shards("mid6k", 3)
+    assert [len(i) for i in ix] == [4096, 6000 - 4096, 0] and len(split) == 1      # (the row the block boundary cuts)
+    res = _ranks(3, "host", "mid6k", scan_path, tmp_path)
+    _same_as_the_anchor(res, _ref("mid6k", per_step_evaluation=False))
+    for rank, _, _, _, _, rc in res:
+        assert rc["evaluations"] >= 50 and rc["fallbacks"] == 0, (rank, rc)
+        if scan_path == 2:
+            assert rc["indexed_passes"] == rc["evaluations"], (rank, rc)
+    if scan_path == 0:
+        assert res[2][5]["indexed_passes"] == 0
 
 
 def _rccl_child(out_path, which):

@@ -10,8 +10,8 @@ For every case the SAME evaluations run on ONE engine with graal_set_scan_path(1
 * the indexed run's `indexed_passes` (graal_run_counters) grows by the number of evaluations, the streaming run's by zero;
 * every case's numpy count is >= 1 (neighbours are drawn from the contact map), so no case passes on an empty queue.
 
-Not here: two ranks on shards of the list (tests/test_multirank_gpu.py's set-up) -- every rank indexes its own shard and
-chooses for itself, but that flow has no case in this file."""
+Two and three ranks on shards of the list -- every rank indexes its own shard and chooses for itself -- are in
+tests/test_multirank_gpu.py; the kernel's own branches at mid-size shapes in tests/test_scan_rows_midsize_gpu.py."""
 import json
 import os
 import subprocess
@@ -57,6 +57,36 @@ def layout(P, rng, n_contigs, p_circ=0.2):
         order = m[np.argsort(s["pos"][m])]
         s["start_bp"][order] = np.cumsum(s["len_bp"][order]) - s["len_bp"][order]
         s["l_cont_bp"][order] = s["len_bp"][order].sum()
+    return s
+
+
+def layout_of_groups(P, rng, groups, rest_max=12, p_rev=0.4):
+    """A valid layout of P's fragments in which every array of `groups` is one linear contig of exactly those fragments, in that order;
+    the fragments left over go, shuffled, into contigs of 1 .. rest_max fragments."""
+    from oracle import oracle as O
+    n = P["n_frags"]
+    groups = [np.asarray(g, np.int64) for g in groups]
+    used = np.concatenate(groups) if groups else np.zeros(0, np.int64)
+    assert len(np.unique(used)) == len(used) and (len(used) == 0 or (used.min() >= 0 and used.max() < n))
+    rest = rng.permutation(np.setdiff1d(np.arange(n), used))
+    while len(rest):
+        k = int(rng.randint(1, rest_max + 1))
+        groups.append(rest[:k])
+        rest = rest[k:]
+    s = O.new_state(n)
+    s["len_bp"][:] = P["S_o_A_frags"]["len_bp"]
+    s["ori"][:] = np.where(rng.random_sample(n) < p_rev, -1, 1)
+    s["id"][:] = np.arange(n)
+    s["id_d"][:] = np.arange(n)
+    for lab, g in enumerate(groups):
+        lens = s["len_bp"][g].astype(np.int64)
+        s["pos"][g] = np.arange(len(g))
+        s["id_c"][g] = lab
+        s["start_bp"][g] = np.cumsum(lens) - lens
+        s["l_cont"][g] = len(g)
+        s["l_cont_bp"][g] = lens.sum()
+        s["prev"][g] = np.concatenate([[-1], g[:-1]])
+        s["next"][g] = np.concatenate([g[1:], [-1]])
     return s
 
 
@@ -251,10 +281,20 @@ def sampler_problem():
                               grid_bp=2000)
 
 
-def sampler_run(path, cycles):
-    """cycles x 150 graal_step steps from the exploded layout with one producer; what a run leaves behind."""
+def switch_problem():
+    """3,000 bins, 1,000,000 contacts, longest row 661: with K = 4 the engine's own choice is the indexed pass while the bound on the longest
+    contig is at most 18 fragments and the streaming pass from 19 on (5 x 19 x 661 x 16 > 1,000,000) -- a run from the exploded layout starts
+    indexed and changes producer once a contig of 9 fragments exists (the bound between relabels is 2 x 9 + 2).
+    tests/test_scan_rows_reference_cpu.py checks these figures."""
+    par = synth.make_param_simu(fact=200.0, v_inter=0.02)
+    return synth.make_problem(n_bins=3000, nnz=1_000_000, n_sub=1, seed=88, contig_weights=(5, 4, 3), mean_len_bp=2000.0, accu=1, param=par,
+                              grid_bp=2000)
+
+
+def sampler_run(path, cycles, problem=sampler_problem):
+    """cycles x n_bins graal_step steps from the exploded layout with one producer (0: the engine's own choice); what a run leaves behind."""
     from tests.test_sampler_gpu import make_gpu_sampler
-    P = sampler_problem()
+    P = problem()
     rng = np.random.RandomState(78)
     g = make_gpu_sampler(P, rng)
     g.engine.set_scan_path(path)
@@ -270,6 +310,10 @@ def sampler_run(path, cycles):
 
 def _child_run():
     print("RESULT " + json.dumps(sampler_run(INDEXED, 1)))
+
+
+def _child_switch_run():
+    print("RESULT " + json.dumps(sampler_run(0, 2, switch_problem)))
 
 
 def same_run(a, b):
@@ -304,6 +348,35 @@ def test_forced_time_out_with_the_indexed_producer():
     same_run(a, b)
     assert b["used_c"] and b["fallbacks"] >= 1, "no step was repeated: the case tests nothing"
     assert b["indexed"] == b["evaluations"]     # (a repeated step counts as an evaluation of its own, and stays indexed)
+
+
+def test_the_engines_own_choice_changes_producer_within_a_run(monkeypatch):
+    """Two cycles (6,000 steps) from the exploded layout of switch_problem with nothing forced and the shipped ratio: the run starts with the
+    indexed pass, its contigs grow -- the first contig of 9 fragments appears early in the second cycle --, and it goes over to the
+    streaming pass -- relying on the bound 2 x max + 2 for the longest contig
+    between relabels.  It must equal the run that streams throughout; and so must the same run in a child whose in-kernel wait for the
+    producer runs out at once (GRAAL_TM_SPIN_TICKS=1), where steps are repeated behind events with the producer they had."""
+    for name in ("GRAAL_SCAN_PATH", "GRAAL_SCAN_ROWS_R", "GRAAL_TM_SPIN_TICKS"):
+        monkeypatch.delenv(name, raising=False)
+    auto = sampler_run(0, 2, switch_problem)
+    stream = sampler_run(STREAM, 2, switch_problem)
+    assert auto["used_c"] and stream["used_c"] and len(auto["mutations"]) >= 1
+    same_run(stream, auto)
+    print("own choice: %d evaluations, %d indexed, %d fallbacks" % (auto["evaluations"], auto["indexed"], auto["fallbacks"]))
+    assert stream["indexed"] == 0 and stream["evaluations"] == auto["evaluations"]
+    assert auto["indexed"] >= 50 and auto["evaluations"] - auto["indexed"] >= 50, "the run did not use both producers"
+    assert auto["fallbacks"] == 0
+    env = {k: v for k, v in os.environ.items() if k not in ("GRAAL_NO_TM_SPIN", "GRAAL_PY_STEP")}
+    env["GRAAL_TM_SPIN_TICKS"] = "1"
+    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", "import tests.test_scan_rows_gpu as t; t._child_switch_run()"], cwd=ROOT,
+                       env=env, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
+    b = json.loads(line[len("RESULT "):])
+    same_run(stream, b)
+    print("own choice, waits run out: %d evaluations, %d indexed, %d fallbacks" % (b["evaluations"], b["indexed"], b["fallbacks"]))
+    assert b["used_c"] and b["fallbacks"] >= 1, "no step was repeated: the case tests nothing"
+    assert b["indexed"] >= 1 and b["evaluations"] - b["indexed"] >= 1
 
 
 def test_c5_size_exploded_layout_auto_takes_the_index():
