@@ -1,5 +1,6 @@
 // edit.h -- a batch of cuts and joins applied to the layout in one call (graal_edit_layout).
-// Included by graal_hip.hip after links.h (it uses Ctx, SoaPtr, the F_* field indices, fail, wait_own, refresh and sync_args).
+// Included by graal_hip.hip after insert.h (it uses Ctx, SoaPtr, the F_* field indices, fail, wait_own, refresh, sync_args and
+// score_common.h's free_null).
 //
 // The rules are those of include/graal_hip.h (graal_edit_layout); tests/edit_reference.py restates them in numpy.  Kernels, all on the
 // engine's stream:
@@ -35,18 +36,16 @@ struct EdBuf {
 
 void ed_free_fixed(EdBuf* b)
 {
-    void** p[] = {(void**)&b->cnt, (void**)&b->base, (void**)&b->ncut, (void**)&b->lastcut, (void**)&b->slot, (void**)&b->at, (void**)&b->cutc,
-                  (void**)&b->mark, (void**)&b->hs, (void**)&b->ph, (void**)&b->pp, (void**)&b->pob, (void**)&b->pcnt, (void**)&b->plbp,
-                  (void**)&b->ptail, (void**)&b->plab, (void**)&b->fresh, (void**)&b->frank, (void**)&b->ejc, (void**)&b->ejo,
-                  (void**)&b->agg[0], (void**)&b->agg[1], (void**)&b->scal, &b->tmp};
-    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    free_null({(void**)&b->cnt, (void**)&b->base, (void**)&b->ncut, (void**)&b->lastcut, (void**)&b->slot, (void**)&b->at, (void**)&b->cutc,
+               (void**)&b->mark, (void**)&b->hs, (void**)&b->ph, (void**)&b->pp, (void**)&b->pob, (void**)&b->pcnt, (void**)&b->plbp,
+               (void**)&b->ptail, (void**)&b->plab, (void**)&b->fresh, (void**)&b->frank, (void**)&b->ejc, (void**)&b->ejo,
+               (void**)&b->agg[0], (void**)&b->agg[1], (void**)&b->scal, &b->tmp});
     b->tmp_bytes = 0; b->n = 0;
 }
 
 void ed_free_args(EdBuf* b)
 {
-    void** p[] = {(void**)&b->d_cut, (void**)&b->d_ea, (void**)&b->d_eb, (void**)&b->d_st};
-    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    free_null({(void**)&b->d_cut, (void**)&b->d_ea, (void**)&b->d_eb, (void**)&b->d_st});
     b->ccap = 0; b->jcap = 0;
 }
 

@@ -7030,6 +7030,7 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 } // extern "C"
 
 #include "simulate.h"
+#include "score_common.h"
 #include "junctions.h"
 #include "links.h"
 #include "insert.h"

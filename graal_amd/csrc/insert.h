@@ -1,6 +1,7 @@
 // insert.h -- the likelihood every insertion of a small contig into a junction would add, for every (piece, junction, orientation) the
-// contacts support (graal_insertions).  Included by graal_hip.hip after links.h (it uses k_jn_count, k_ln_prep, the records LnSub / LnFrag
-// / LnCtg, ln_slot, ln_run_sum, ln_pair_mass, ln_quirk_pair, ln_mirror_q, k_ln_mirror, k_ln_flag and k_ln_keys).
+// contacts support (graal_insertions).  Included by graal_hip.hip after links.h (it uses LayoutRecs with recs_reserve / recs_build, the
+// records LnSub / LnFrag / LnCtg, ln_slot, ln_run_sum, ln_pair_mass, ln_quirk_pair, ln_mirror_q, k_ln_mirror, k_ln_flag and k_ln_keys, and
+// score_common.h's score_entry, score_exit, STEP_CK, free_null and CandTable).
 //
 // A PIECE is a linear contig P of 1 .. max_piece_frags fragments; a TARGET junction is a fragment f with next[f] = g != -1 of a linear
 // contig T != P.  The inserted layout cuts T between f and g into T1 (.. f) and T2 (g ..) and writes T1, P, T2 as one contig: T1 and T2
@@ -40,75 +41,49 @@
 namespace {
 
 struct InBuf {
-    int n = 0, S = 0;
-    int *cnt = nullptr, *base = nullptr, *slot = nullptr, *lab = nullptr;
-    LnFrag* fr = nullptr;
-    LnSub* sub = nullptr;
-    LnCtg* ctg = nullptr;
-    long long* mir = nullptr; int* mirbad = nullptr;
-    long long* rowptr = nullptr;
+    LayoutRecs R;                                                    // (its own instance: nothing shared with graal_end_links' calls)
+    CandTable T;
+    long long* rowptr = nullptr; size_t rcap = 0;                    // row offsets (S + 1) when the engine has none for this list
     unsigned* uns = nullptr;                                         // the contact list is not sorted by row
     int *srow = nullptr, *pin = nullptr, *perm = nullptr; void* ptmp = nullptr; size_t pcap = 0, ptmp_bytes = 0;   // its sort by row
-    unsigned* err = nullptr; unsigned long long* ctr = nullptr;      // ctr: [0] records counted, [1] listed keys, [2] linear contigs, [3] pair records
-    void* tmp = nullptr; size_t tmp_bytes = 0;
-    // the candidate table, the (P, T) table and the per-candidate arrays grow to the largest size a call needed (within GRAAL_LINKS_MAX_BYTES)
-    unsigned long long* keys = nullptr; long long *tq = nullptr, *tc = nullptr; int* tf = nullptr; unsigned char* tsel = nullptr; size_t cap = 0;
+    // the candidate table (T), the (P, T) table and the per-candidate arrays grow to the largest size a call needed (within GRAAL_LINKS_MAX_BYTES)
     unsigned long long* keys2 = nullptr; long long *pf = nullptr, *pm = nullptr; int* pb = nullptr; size_t cap2 = 0;
     unsigned long long *ko = nullptr, *ks = nullptr; int *vo = nullptr, *vs = nullptr;
     long long *q = nullptr, *c = nullptr, *sh = nullptr; int *bad = nullptr, *shbad = nullptr, *lead = nullptr, *piece = nullptr, *after = nullptr;
     unsigned char *rev = nullptr, *st = nullptr;
     size_t lcap = 0;
-    void* stmp = nullptr; size_t stmp_bytes = 0;
     long long n_out = -1;                                            // -1: no result to fetch
 };
 
-void in_free_ptrs(void** const* p, size_t k)
+void in_free_rows(InBuf* b)
 {
-    for (size_t i = 0; i < k; i++) { if (*p[i]) (void)hipFree(*p[i]); *p[i] = nullptr; }
-}
-
-void in_free_fixed(InBuf* b)
-{
-    void** p[] = {(void**)&b->cnt, (void**)&b->base, (void**)&b->slot, (void**)&b->lab, (void**)&b->fr, (void**)&b->sub, (void**)&b->ctg,
-                  (void**)&b->mir, (void**)&b->mirbad, (void**)&b->rowptr, (void**)&b->uns, (void**)&b->err, (void**)&b->ctr, &b->tmp};
-    in_free_ptrs(p, sizeof p / sizeof p[0]);
-    b->tmp_bytes = 0; b->n = 0; b->S = 0;
-}
-
-void in_free_tables(InBuf* b)
-{
-    void** p[] = {(void**)&b->keys, (void**)&b->tq, (void**)&b->tc, (void**)&b->tf, (void**)&b->tsel};
-    in_free_ptrs(p, sizeof p / sizeof p[0]);
-    b->cap = 0;
+    free_null({(void**)&b->rowptr, (void**)&b->uns});
+    b->rcap = 0;
 }
 
 void in_free_pairs(InBuf* b)
 {
-    void** p[] = {(void**)&b->keys2, (void**)&b->pf, (void**)&b->pm, (void**)&b->pb};
-    in_free_ptrs(p, sizeof p / sizeof p[0]);
+    free_null({(void**)&b->keys2, (void**)&b->pf, (void**)&b->pm, (void**)&b->pb});
     b->cap2 = 0;
 }
 
 void in_free_cands(InBuf* b)
 {
-    void** p[] = {(void**)&b->ko, (void**)&b->ks, (void**)&b->vo, (void**)&b->vs, (void**)&b->q, (void**)&b->c, (void**)&b->sh, (void**)&b->bad,
-                  (void**)&b->shbad, (void**)&b->lead, (void**)&b->piece, (void**)&b->after, (void**)&b->rev, (void**)&b->st};
-    in_free_ptrs(p, sizeof p / sizeof p[0]);
+    free_null({(void**)&b->ko, (void**)&b->ks, (void**)&b->vo, (void**)&b->vs, (void**)&b->q, (void**)&b->c, (void**)&b->sh, (void**)&b->bad,
+               (void**)&b->shbad, (void**)&b->lead, (void**)&b->piece, (void**)&b->after, (void**)&b->rev, (void**)&b->st});
     b->lcap = 0;
 }
 
 void in_free_sort(InBuf* b)
 {
-    void** p[] = {(void**)&b->srow, (void**)&b->pin, (void**)&b->perm, &b->ptmp};
-    in_free_ptrs(p, sizeof p / sizeof p[0]);
+    free_null({(void**)&b->srow, (void**)&b->pin, (void**)&b->perm, &b->ptmp});
     b->pcap = 0; b->ptmp_bytes = 0;
 }
 
 void in_free(InBuf* b)
 {
     if (!b) return;
-    in_free_fixed(b); in_free_tables(b); in_free_pairs(b); in_free_cands(b); in_free_sort(b);
-    if (b->stmp) (void)hipFree(b->stmp);
+    recs_free(b->R); table_free(b->T); in_free_rows(b); in_free_pairs(b); in_free_cands(b); in_free_sort(b);
     delete b;
 }
 
@@ -571,41 +546,23 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
 {
     if (!h || !n_out) return GRAAL_E_ARG;
     if (max_piece_frags < 1) return fail(h, GRAAL_E_ARG, "graal_insertions: max_piece_frags must be >= 1");
-    if (!(h->have_sub && h->have_par && h->have_frags && h->have_contacts))
-        return fail(h, GRAAL_E_STATE, "graal_insertions: upload sub-fragments, parameters, fragments and contacts first");
-    if (h->has_rep) return fail(h, GRAAL_E_UNSUPPORTED, "graal_insertions: bins with several copies (graal_upload_repeats) are not supported");
-    if (h->x_host || h->nccl_comm) return fail(h, GRAAL_E_STATE, "graal_insertions: one rank only (an exchange or RCCL is attached)");
-    CK(hipSetDevice(h->device));
+    if (const int rc = score_entry(h, "graal_insertions")) return rc;
     *n_out = 0;
     const int n = h->n, S = h->n_sub_total;
     if (!h->ins) h->ins = new InBuf();
     InBuf* B = h->ins;
+    LayoutRecs& R = B->R;
+    CandTable& T = B->T;
     B->n_out = -1;
     if (n < 1) { B->n_out = 0; return GRAAL_OK; }
     hipStream_t s = h->stream;
-    if (B->n != n || B->S != S) {
-        // (every pointer is freed AND nulled, and B->n stays 0 until the whole set is allocated: a failed hipMalloc leaves nothing to free twice)
-        in_free_fixed(B);
-        CK(hipMalloc(&B->cnt, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&B->base, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&B->slot, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&B->lab, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&B->fr, sizeof(LnFrag) * (size_t)n));
-        CK(hipMalloc(&B->sub, sizeof(LnSub) * (size_t)std::max(S, 1)));
-        CK(hipMalloc(&B->ctg, sizeof(LnCtg) * (size_t)(n + 3)));
-        CK(hipMalloc(&B->mir, sizeof(long long) * (size_t)(n + 3)));
-        CK(hipMalloc(&B->mirbad, sizeof(int) * (size_t)(n + 3)));
+    if (const int rc = recs_reserve(h, R)) return rc;
+    if ((size_t)S + 1 != B->rcap) {                                  // (B->rcap stays 0 until both are allocated)
+        in_free_rows(B);
         CK(hipMalloc(&B->rowptr, sizeof(long long) * (size_t)(S + 1)));
         CK(hipMalloc(&B->uns, sizeof(unsigned)));
-        CK(hipMalloc(&B->err, sizeof(unsigned)));
-        CK(hipMalloc(&B->ctr, sizeof(unsigned long long) * 4));
-        size_t b1 = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, B->cnt, B->base, n + 3, s));
-        CK(hipMalloc(&B->tmp, b1));
-        B->tmp_bytes = b1;
-        B->n = n; B->S = S;
+        B->rcap = (size_t)S + 1;
     }
-    const SoaPtr sp = h->soa[h->cur];
     const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     const int mq = quirk && h->n_ubins > 0;
     const int reach = reach_bp(h);
@@ -616,33 +573,19 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
     const char* why = nullptr;
     char msg[320];
     do {
-#define IN_CK(call) { const hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = hipGetErrorString(e_); rc = GRAAL_E_HIP; break; } }
-        // ---- records
-        IN_CK(hipMemsetAsync(B->err, 0, sizeof(unsigned), s));
-        IN_CK(hipMemsetAsync(B->ctr, 0, sizeof(unsigned long long) * 4, s));
-        IN_CK(hipMemsetAsync(B->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
-        IN_CK(hipMemsetAsync(B->ctg, 0, sizeof(LnCtg) * (size_t)(n + 3), s));
-        IN_CK(hipMemsetAsync(B->fr, 0, sizeof(LnFrag) * (size_t)n, s));
-        IN_CK(hipMemsetAsync(B->mir, 0, sizeof(long long) * (size_t)(n + 3), s));
-        IN_CK(hipMemsetAsync(B->mirbad, 0, sizeof(int) * (size_t)(n + 3), s));
-        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, B->cnt, B->err);
-        IN_CK(hipGetLastError());
-        size_t tb = B->tmp_bytes;
-        IN_CK(hipcub::DeviceScan::ExclusiveSum(B->tmp, tb, B->cnt, B->base, n + 3, s));
-        k_ln_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, 1, h->stat_frag, h->d_sub_ids, B->cnt, B->base, B->slot, B->lab, B->fr, B->sub, B->ctg,
-                                                     &B->ctr[2], B->err);
-        IN_CK(hipGetLastError());
-        k_in_piece<<<blocks_for(n + 3, 256), 256, 0, s>>>(n + 3, max_piece_frags, B->ctg);
-        IN_CK(hipGetLastError());
-        IN_CK(hipMemsetAsync(B->uns, 0, sizeof(unsigned), s));
+        // ---- records (min_frags 1: a record's elig = linear), then the pieces among them
+        if ((rc = recs_build(h, R, 1))) break;
+        k_in_piece<<<blocks_for(n + 3, 256), 256, 0, s>>>(n + 3, max_piece_frags, R.ctg);
+        STEP_CK(hipGetLastError());
+        STEP_CK(hipMemsetAsync(B->uns, 0, sizeof(unsigned), s));
         if (h->nnz > 1) {
             k_in_unsorted<<<(unsigned)std::min<long long>(blocks_for(h->nnz, 256), 4096), 256, 0, s>>>(h->row, h->nnz, B->uns);
-            IN_CK(hipGetLastError());
+            STEP_CK(hipGetLastError());
         }
         unsigned uns = 0;
-        IN_CK(hipMemcpyAsync(&err, B->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        IN_CK(hipMemcpyAsync(&uns, B->uns, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        IN_CK(hipStreamSynchronize(s));
+        STEP_CK(hipMemcpyAsync(&err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(&uns, B->uns, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
         if (err) break;   // (a corrupt layout: the slots and the sub-fragment records are not to be trusted, nothing reads them)
         // ---- row offsets: of the list itself when it is sorted by row, else of its radix sort by row (a permutation, kept for k_in_shift)
         const int* rows = h->row;
@@ -656,19 +599,19 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
             }
             const int nz = (int)h->nnz;
             size_t pb = 0;
-            IN_CK(hipcub::DeviceRadixSort::SortPairs(nullptr, pb, (const int*)nullptr, (int*)nullptr, (const int*)nullptr, (int*)nullptr, nz, 0,
+            STEP_CK(hipcub::DeviceRadixSort::SortPairs(nullptr, pb, (const int*)nullptr, (int*)nullptr, (const int*)nullptr, (int*)nullptr, nz, 0,
                                                      32, s));
             sort_bytes = 3 * sizeof(int) * (size_t)nz + pb;
             if ((size_t)nz > B->pcap || pb > B->ptmp_bytes) {
                 in_free_sort(B);
-                IN_CK(hipMalloc(&B->srow, sizeof(int) * (size_t)nz)); IN_CK(hipMalloc(&B->pin, sizeof(int) * (size_t)nz));
-                IN_CK(hipMalloc(&B->perm, sizeof(int) * (size_t)nz)); IN_CK(hipMalloc(&B->ptmp, std::max<size_t>(pb, 1)));
+                STEP_CK(hipMalloc(&B->srow, sizeof(int) * (size_t)nz)); STEP_CK(hipMalloc(&B->pin, sizeof(int) * (size_t)nz));
+                STEP_CK(hipMalloc(&B->perm, sizeof(int) * (size_t)nz)); STEP_CK(hipMalloc(&B->ptmp, std::max<size_t>(pb, 1)));
                 B->pcap = (size_t)nz; B->ptmp_bytes = std::max<size_t>(pb, 1);
             }
             k_in_iota<<<blocks_for(nz, 256), 256, 0, s>>>(nz, B->pin);
-            IN_CK(hipGetLastError());
+            STEP_CK(hipGetLastError());
             pb = B->ptmp_bytes;
-            IN_CK(hipcub::DeviceRadixSort::SortPairs(B->ptmp, pb, h->row, B->srow, B->pin, B->perm, nz, 0, 32, s));
+            STEP_CK(hipcub::DeviceRadixSort::SortPairs(B->ptmp, pb, h->row, B->srow, B->pin, B->perm, nz, 0, 32, s));
             rows = B->srow;
             perm = B->perm;
         }
@@ -677,35 +620,34 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
         if (!uns && h->rowptr) rowptr = h->rowptr;
         else {
             k_rowptr<<<blocks_for((long long)S + 1, 256), 256, 0, s>>>(S, rows, h->nnz, B->rowptr);
-            IN_CK(hipGetLastError());
+            STEP_CK(hipGetLastError());
         }
         // ---- count pass: upper bounds of the distinct keys of the two tables
         const long long waves = (h->nnz + 63) / 64;
         const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
         if (h->nnz > 0) {
-            k_in_nnz<true><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, B->sub, h->stat_frag, B->ctg, B->fr, B->slot, h->nfpb, h->par, quirk,
+            k_in_nnz<true><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, R.fr, R.slot, h->nfpb, h->par, quirk,
                                               mq, reach, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                              nullptr, B->ctr, B->err);
-            IN_CK(hipGetLastError());
+                                              nullptr, R.ctr, R.err);
+            STEP_CK(hipGetLastError());
         }
-        IN_CK(hipMemcpyAsync(&err, B->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        IN_CK(hipMemcpyAsync(ctr, B->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
-        IN_CK(hipStreamSynchronize(s));
+        STEP_CK(hipMemcpyAsync(&err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(ctr, R.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
         if (err) break;
         const unsigned long long bound = ctr[0];
-        const unsigned long long cap = bound + bound / 2 + 64;       // (load factor <= 2/3)
-        const unsigned long long cap2 = mq ? ctr[3] + ctr[3] / 2 + 64 : 0;
+        const unsigned long long cap = table_cap(bound), cap2 = mq ? table_cap(ctr[3]) : 0;
         const unsigned long long L = bound + 1;
         // device memory: the candidate table (key, q, contacts, flags, selection byte per slot), the (P, T) table (key, far sum, mirror
         // sum, flags), the per-candidate arrays sized to the bound (keys x2, indices x2, q, contacts, T1 x T2 term, bad x2, leader,
         // piece, after, rev, status) and the hipCUB temp storage of the selection, the sort
-        unsigned long long need = cap * (unsigned long long)(8 + 8 + 8 + 4 + 1) + cap2 * (unsigned long long)(8 + 8 + 8 + 4)
+        unsigned long long need = cap * TABLE_SLOT_BYTES + cap2 * (unsigned long long)(8 + 8 + 8 + 4)
                                   + L * (unsigned long long)(8 * 2 + 4 * 2 + 8 * 3 + 4 * 5 + 1 * 2) + sort_bytes;
         size_t b_sel = 0, b_sort = 0;
         if (cap < (unsigned long long)INT_MAX) {
-            IN_CK(hipcub::DeviceSelect::Flagged(nullptr, b_sel, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr, (int*)nullptr,
+            STEP_CK(hipcub::DeviceSelect::Flagged(nullptr, b_sel, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr, (int*)nullptr,
                                                 (unsigned long long*)nullptr, (int)cap, s));
-            IN_CK(hipcub::DeviceRadixSort::SortPairs(nullptr, b_sort, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+            STEP_CK(hipcub::DeviceRadixSort::SortPairs(nullptr, b_sort, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
                                                      (const int*)nullptr, (int*)nullptr, (int)L, 0, 64, s));
         }
         const size_t tneed = std::max(b_sel, b_sort);
@@ -716,66 +658,50 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
             why = msg;
             break;
         }
-        if (cap > B->cap) {
-            in_free_tables(B);
-            IN_CK(hipMalloc(&B->keys, sizeof(unsigned long long) * cap));
-            IN_CK(hipMalloc(&B->tq, sizeof(long long) * cap));
-            IN_CK(hipMalloc(&B->tc, sizeof(long long) * cap));
-            IN_CK(hipMalloc(&B->tf, sizeof(int) * cap));
-            IN_CK(hipMalloc(&B->tsel, cap));
-            B->cap = cap;
-        }
+        STEP_CK(table_reserve(T, cap));
         if (cap2 > B->cap2) {
             in_free_pairs(B);
-            IN_CK(hipMalloc(&B->keys2, sizeof(unsigned long long) * cap2));
-            IN_CK(hipMalloc(&B->pf, sizeof(long long) * cap2));
-            IN_CK(hipMalloc(&B->pm, sizeof(long long) * cap2));
-            IN_CK(hipMalloc(&B->pb, sizeof(int) * cap2));
+            STEP_CK(hipMalloc(&B->keys2, sizeof(unsigned long long) * cap2));
+            STEP_CK(hipMalloc(&B->pf, sizeof(long long) * cap2));
+            STEP_CK(hipMalloc(&B->pm, sizeof(long long) * cap2));
+            STEP_CK(hipMalloc(&B->pb, sizeof(int) * cap2));
             B->cap2 = cap2;
         }
         if (L > B->lcap) {
             in_free_cands(B);
-            IN_CK(hipMalloc(&B->ko, sizeof(unsigned long long) * L)); IN_CK(hipMalloc(&B->ks, sizeof(unsigned long long) * L));
-            IN_CK(hipMalloc(&B->vo, sizeof(int) * L)); IN_CK(hipMalloc(&B->vs, sizeof(int) * L));
-            IN_CK(hipMalloc(&B->q, sizeof(long long) * L)); IN_CK(hipMalloc(&B->c, sizeof(long long) * L));
-            IN_CK(hipMalloc(&B->sh, sizeof(long long) * L));
-            IN_CK(hipMalloc(&B->bad, sizeof(int) * L)); IN_CK(hipMalloc(&B->shbad, sizeof(int) * L)); IN_CK(hipMalloc(&B->lead, sizeof(int) * L));
-            IN_CK(hipMalloc(&B->piece, sizeof(int) * L)); IN_CK(hipMalloc(&B->after, sizeof(int) * L));
-            IN_CK(hipMalloc(&B->rev, L)); IN_CK(hipMalloc(&B->st, L));
+            STEP_CK(hipMalloc(&B->ko, sizeof(unsigned long long) * L)); STEP_CK(hipMalloc(&B->ks, sizeof(unsigned long long) * L));
+            STEP_CK(hipMalloc(&B->vo, sizeof(int) * L)); STEP_CK(hipMalloc(&B->vs, sizeof(int) * L));
+            STEP_CK(hipMalloc(&B->q, sizeof(long long) * L)); STEP_CK(hipMalloc(&B->c, sizeof(long long) * L));
+            STEP_CK(hipMalloc(&B->sh, sizeof(long long) * L));
+            STEP_CK(hipMalloc(&B->bad, sizeof(int) * L)); STEP_CK(hipMalloc(&B->shbad, sizeof(int) * L)); STEP_CK(hipMalloc(&B->lead, sizeof(int) * L));
+            STEP_CK(hipMalloc(&B->piece, sizeof(int) * L)); STEP_CK(hipMalloc(&B->after, sizeof(int) * L));
+            STEP_CK(hipMalloc(&B->rev, L)); STEP_CK(hipMalloc(&B->st, L));
             B->lcap = L;
         }
-        if (tneed > B->stmp_bytes) {
-            if (B->stmp) (void)hipFree(B->stmp);
-            B->stmp = nullptr; B->stmp_bytes = 0;
-            IN_CK(hipMalloc(&B->stmp, tneed));
-            B->stmp_bytes = tneed;
-        }
+        STEP_CK(scratch_reserve(T, tneed));
         // (the tables are used at sizes `cap` / `cap2`, whatever their allocations: the probe sequences depend on them)
-        IN_CK(hipMemsetAsync(B->keys, 0xff, sizeof(unsigned long long) * cap, s));
-        IN_CK(hipMemsetAsync(B->tq, 0, sizeof(long long) * cap, s));
-        IN_CK(hipMemsetAsync(B->tc, 0, sizeof(long long) * cap, s));
-        IN_CK(hipMemsetAsync(B->tf, 0, sizeof(int) * cap, s));
+        STEP_CK(table_clear(T, cap, s));
         if (cap2) {
-            IN_CK(hipMemsetAsync(B->keys2, 0xff, sizeof(unsigned long long) * cap2, s));
-            IN_CK(hipMemsetAsync(B->pf, 0, sizeof(long long) * cap2, s));
-            IN_CK(hipMemsetAsync(B->pm, 0, sizeof(long long) * cap2, s));
-            IN_CK(hipMemsetAsync(B->pb, 0, sizeof(int) * cap2, s));
+            STEP_CK(hipMemsetAsync(B->keys2, 0xff, sizeof(unsigned long long) * cap2, s));
+            STEP_CK(hipMemsetAsync(B->pf, 0, sizeof(long long) * cap2, s));
+            STEP_CK(hipMemsetAsync(B->pm, 0, sizeof(long long) * cap2, s));
+            STEP_CK(hipMemsetAsync(B->pb, 0, sizeof(int) * cap2, s));
         }
         // ---- insert pass, selection of the listed slots, sort by key
         if (h->nnz > 0) {
-            k_in_nnz<false><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, B->sub, h->stat_frag, B->ctg, B->fr, B->slot, h->nfpb, h->par, quirk,
-                                               mq, reach, cap, B->keys, B->tq, B->tc, B->tf, cap2, B->keys2, B->pf, B->pm, B->pb, B->mir,
-                                               B->mirbad, B->ctr, B->err);
-            IN_CK(hipGetLastError());
+            k_in_nnz<false><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, R.fr, R.slot, h->nfpb, h->par, quirk,
+                                               mq, reach, cap, T.keys, T.tq, T.tc, T.tf, cap2, B->keys2, B->pf, B->pm, B->pb, R.mir,
+                                               R.mirbad, R.ctr, R.err);
+            STEP_CK(hipGetLastError());
         }
-        k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(B->keys, B->tf, (long long)cap, B->tsel);
-        IN_CK(hipGetLastError());
-        tb = B->stmp_bytes;
-        IN_CK(hipcub::DeviceSelect::Flagged(B->stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)B->tsel, B->vo, &B->ctr[1],
+        k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(T.keys, T.tf, (long long)cap, T.tsel);
+        STEP_CK(hipGetLastError());
+        size_t tb = T.stmp_bytes;
+        STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)T.tsel, B->vo, &R.ctr[1],
                                             (int)cap, s));
-        IN_CK(hipMemcpyAsync(ctr, B->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
-        IN_CK(hipMemcpyAsync(&err, B->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        IN_CK(hipStreamSynchronize(s));
+        STEP_CK(hipMemcpyAsync(ctr, R.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(&err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
         if (err) break;
         m = (long long)ctr[1];
         if (m == 0) break;
@@ -784,42 +710,35 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
             why = msg;
             break;
         }
-        k_ln_keys<<<blocks_for(m, 256), 256, 0, s>>>(m, B->keys, B->vo, B->ko);
-        IN_CK(hipGetLastError());
-        tb = B->stmp_bytes;
-        IN_CK(hipcub::DeviceRadixSort::SortPairs(B->stmp, tb, B->ko, B->ks, B->vo, B->vs, (int)m, 0, 64, s));
-        k_in_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, B->ks, B->vs, B->tq, B->tc, B->tf, B->q, B->c, B->bad, B->sh, B->shbad, B->piece,
+        k_ln_keys<<<blocks_for(m, 256), 256, 0, s>>>(m, T.keys, B->vo, B->ko);
+        STEP_CK(hipGetLastError());
+        tb = T.stmp_bytes;
+        STEP_CK(hipcub::DeviceRadixSort::SortPairs(T.stmp, tb, B->ko, B->ks, B->vo, B->vs, (int)m, 0, 64, s));
+        k_in_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, B->ks, B->vs, T.tq, T.tc, T.tf, B->q, B->c, B->bad, B->sh, B->shbad, B->piece,
                                                        B->after, B->rev);
-        IN_CK(hipGetLastError());
-        k_in_lead<<<blocks_for(m, 256), 256, 0, s>>>(m, B->piece, B->after, B->lab, B->ctg, B->lead);
-        IN_CK(hipGetLastError());
+        STEP_CK(hipGetLastError());
+        k_in_lead<<<blocks_for(m, 256), 256, 0, s>>>(m, B->piece, B->after, R.lab, R.ctg, B->lead);
+        STEP_CK(hipGetLastError());
         // ---- the mass passes, the quirk's passes, the result
         const unsigned wblocks = (unsigned)((m + 3) / 4);            // a wave per candidate, 4 waves per block
-        k_in_mass<<<wblocks, 256, 0, s>>>(m, B->piece, B->after, B->rev, B->slot, B->lab, B->ctg, B->fr, h->nfpb, h->par, quirk, reach, B->q,
+        k_in_mass<<<wblocks, 256, 0, s>>>(m, B->piece, B->after, B->rev, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, quirk, reach, B->q,
                                           B->bad);
-        IN_CK(hipGetLastError());
-        k_in_shift<<<wblocks, 256, 0, s>>>(m, B->lead, B->piece, B->after, B->slot, B->lab, B->ctg, B->fr, B->sub, h->stat_frag, h->d_sub_ids,
+        STEP_CK(hipGetLastError());
+        k_in_shift<<<wblocks, 256, 0, s>>>(m, B->lead, B->piece, B->after, R.slot, R.lab, R.ctg, R.fr, R.sub, h->stat_frag, h->d_sub_ids,
                                            rowptr, perm, h->col, h->cnt, h->nfpb, h->par, reach, B->sh, B->shbad);
-        IN_CK(hipGetLastError());
+        STEP_CK(hipGetLastError());
         if (mq) {
-            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, B->slot, B->lab, B->ctg, B->fr, h->nfpb, h->par, B->mir, B->mirbad);
-            IN_CK(hipGetLastError());
-            k_in_quirk<<<wblocks, 256, 0, s>>>(m, B->piece, B->after, B->rev, B->slot, B->lab, B->ctg, B->fr, h->nfpb, h->par, reach, B->q, B->bad);
-            IN_CK(hipGetLastError());
+            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, R.mir, R.mirbad);
+            STEP_CK(hipGetLastError());
+            k_in_quirk<<<wblocks, 256, 0, s>>>(m, B->piece, B->after, B->rev, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, reach, B->q, B->bad);
+            STEP_CK(hipGetLastError());
         }
-        k_in_out<<<blocks_for(m, 256), 256, 0, s>>>(m, B->piece, B->after, B->rev, B->lead, B->lab, B->sh, B->shbad, mq, B->mir, B->mirbad, cap2,
+        k_in_out<<<blocks_for(m, 256), 256, 0, s>>>(m, B->piece, B->after, B->rev, B->lead, R.lab, B->sh, B->shbad, mq, R.mir, R.mirbad, cap2,
                                                     B->keys2, B->pf, B->pm, B->pb, B->q, B->bad, B->st);
-        IN_CK(hipGetLastError());
-        IN_CK(hipStreamSynchronize(s));
-#undef IN_CK
+        STEP_CK(hipGetLastError());
+        STEP_CK(hipStreamSynchronize(s));
     } while (false);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    if (why) { h->err = why; return GRAAL_E_UNSUPPORTED; }
-    if (err) {
-        snprintf(msg, sizeof msg, "graal_insertions: corrupt layout (contig labels or positions out of range, flags %u)", err);
-        h->err = msg;
-        return GRAAL_E_STATE;
-    }
+    if (const int r = score_exit(h, "graal_insertions", rc, why, err)) return r;
     B->n_out = m;
     *n_out = m;
     return GRAAL_OK;

@@ -1,5 +1,6 @@
 // junctions.h -- the likelihood each join of the current layout carries, for every junction in one pass (graal_junction_scores).
-// Included by graal_hip.hip after the C ABI (it uses Ctx, Stat, centre_kb, rippe, to_q, WAVE_LDS_SYNC and model_math.h).
+// Included by graal_hip.hip after score_common.h (it uses Ctx, Stat, centre_kb, rippe, to_q, WAVE_LDS_SYNC, model_math.h, and
+// score_common.h's score_entry, score_exit, STEP_CK and free_null).
 //
 // J[f] = logL(layout) - logL(layout cut between f and next[f]), for f in a LINEAR contig with next[f] != -1, in the engine's exact
 // arithmetic: pairs on one side of the cut are exactly unchanged, so only the pairs that STRADDLE the cut contribute -- they go from their cis
@@ -45,11 +46,17 @@ struct JnBuf {
     unsigned* err = nullptr;
 };
 
+void jn_free_all(JnBuf* b)
+{
+    free_null({(void**)&b->cnt, (void**)&b->base, (void**)&b->slot, (void**)&b->fr, (void**)&b->sub, (void**)&b->D, (void**)&b->P, (void**)&b->B,
+               (void**)&b->PB, (void**)&b->q, (void**)&b->st, &b->tmp, (void**)&b->err});
+    b->tmp_bytes = 0; b->n = 0; b->S = 0;
+}
+
 void jn_free(JnBuf* b)
 {
     if (!b) return;
-    void* p[] = {b->cnt, b->base, b->slot, b->fr, b->sub, b->D, b->P, b->B, b->PB, b->q, b->st, b->tmp, b->err};
-    for (void* q : p) if (q) (void)hipFree(q);
+    jn_free_all(b);
     delete b;
 }
 
@@ -284,23 +291,14 @@ extern "C" {
 int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status)
 {
     if (!h || !q_out || !status) return GRAAL_E_ARG;
-    if (!(h->have_sub && h->have_par && h->have_frags && h->have_contacts))
-        return fail(h, GRAAL_E_STATE, "graal_junction_scores: upload sub-fragments, parameters, fragments and contacts first");
-    if (h->has_rep) return fail(h, GRAAL_E_UNSUPPORTED, "graal_junction_scores: bins with several copies (graal_upload_repeats) are not supported");
-    if (h->x_host || h->nccl_comm) return fail(h, GRAAL_E_STATE, "graal_junction_scores: one rank only (an exchange or RCCL is attached)");
-    CK(hipSetDevice(h->device));
+    if (const int rc = score_entry(h, "graal_junction_scores")) return rc;
     const int n = h->n, S = h->n_sub_total;
     if (n < 1) return GRAAL_OK;
     if (!h->jn) h->jn = new JnBuf();
     JnBuf* J = h->jn;
     hipStream_t s = h->stream;
     if (J->n != n || J->S != S) {
-        // (every pointer is freed AND nulled, and J->n stays 0 until the whole set is allocated: a failed hipMalloc leaves nothing to free twice)
-        J->n = 0; J->S = 0;
-        void** p[] = {(void**)&J->cnt, (void**)&J->base, (void**)&J->slot, (void**)&J->fr, (void**)&J->sub, (void**)&J->D, (void**)&J->P,
-                                    (void**)&J->B, (void**)&J->PB, (void**)&J->q, (void**)&J->st, &J->tmp, (void**)&J->err};
-        for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
-        J->tmp_bytes = 0;
+        jn_free_all(J);   // (J->n stays 0 until the whole set is allocated: free_null)
         CK(hipMalloc(&J->cnt, sizeof(int) * (size_t)(n + 3)));
         CK(hipMalloc(&J->base, sizeof(int) * (size_t)(n + 3)));
         CK(hipMalloc(&J->slot, sizeof(int) * (size_t)n));
@@ -327,55 +325,46 @@ int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status)
     int rc = GRAAL_OK;
     unsigned err = 0;
     do {
-#define JN_CK(call) { const hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = hipGetErrorString(e_); rc = GRAAL_E_HIP; break; } }
-        JN_CK(hipMemsetAsync(J->err, 0, sizeof(unsigned), s));
-        JN_CK(hipMemsetAsync(J->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
-        JN_CK(hipMemsetAsync(J->D, 0, sizeof(long long) * (size_t)n, s));
-        JN_CK(hipMemsetAsync(J->B, 0, sizeof(int) * (size_t)n, s));
-        JN_CK(hipMemsetAsync(J->fr, 0, sizeof(JnFrag) * (size_t)n, s));   // (a slot no fragment claims -- a corrupt layout -- reads as empty)
+        STEP_CK(hipMemsetAsync(J->err, 0, sizeof(unsigned), s));
+        STEP_CK(hipMemsetAsync(J->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
+        STEP_CK(hipMemsetAsync(J->D, 0, sizeof(long long) * (size_t)n, s));
+        STEP_CK(hipMemsetAsync(J->B, 0, sizeof(int) * (size_t)n, s));
+        STEP_CK(hipMemsetAsync(J->fr, 0, sizeof(JnFrag) * (size_t)n, s));   // (a slot no fragment claims -- a corrupt layout -- reads as empty)
         k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, J->cnt, J->err);
-        JN_CK(hipGetLastError());
+        STEP_CK(hipGetLastError());
         size_t tb = J->tmp_bytes;
-        JN_CK(hipcub::DeviceScan::ExclusiveSum(J->tmp, tb, J->cnt, J->base, n + 3, s));
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(J->tmp, tb, J->cnt, J->base, n + 3, s));
         k_jn_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, h->stat_frag, h->d_sub_ids, J->cnt, J->base, J->slot, J->fr, J->sub, J->err);
-        JN_CK(hipGetLastError());
-        JN_CK(hipMemcpyAsync(&err, J->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        JN_CK(hipStreamSynchronize(s));
+        STEP_CK(hipGetLastError());
+        STEP_CK(hipMemcpyAsync(&err, J->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
         if (err) break;   // (a corrupt layout: the slots are not to be trusted, nothing reads them)
         if (h->nnz > 0) {
             const long long waves = (h->nnz + 63) / 64;
             const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
             k_jn_nnz<<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, J->sub, J->fr, h->nfpb, h->par, quirk, J->D, J->B);
-            JN_CK(hipGetLastError());
+            STEP_CK(hipGetLastError());
         }
         const int lc = std::min(std::max(std::max(h->max_lcont, h->lcont_bound), 1), n);
         const int n_tiles = (n + 63) / 64;
         const int Sw = std::min(16, std::max(1, ((lc + 63) / 64 + 7) / 8));
         k_jn_mass<<<(n_tiles * Sw + 3) / 4, 256, 0, s>>>(n, J->fr, h->nfpb, h->par, quirk, reach_bp(h), Sw, J->D, J->B);
-        JN_CK(hipGetLastError());
+        STEP_CK(hipGetLastError());
         if (quirk && h->n_ubins) {
             k_jn_quirk<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, J->slot, J->fr, h->nfpb, h->par, reach_bp(h), J->D, J->B);
-            JN_CK(hipGetLastError());
+            STEP_CK(hipGetLastError());
         }
         tb = J->tmp_bytes;
-        JN_CK(hipcub::DeviceScan::InclusiveSum(J->tmp, tb, J->D, J->P, n, s));
+        STEP_CK(hipcub::DeviceScan::InclusiveSum(J->tmp, tb, J->D, J->P, n, s));
         tb = J->tmp_bytes;
-        JN_CK(hipcub::DeviceScan::InclusiveSum(J->tmp, tb, J->B, J->PB, n, s));
+        STEP_CK(hipcub::DeviceScan::InclusiveSum(J->tmp, tb, J->B, J->PB, n, s));
         k_jn_out<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, J->slot, J->P, J->PB, J->q, J->st);
-        JN_CK(hipGetLastError());
-        JN_CK(hipMemcpyAsync(q_out, J->q, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, s));
-        JN_CK(hipMemcpyAsync(status, J->st, (size_t)n, hipMemcpyDeviceToHost, s));
-        JN_CK(hipStreamSynchronize(s));
-#undef JN_CK
+        STEP_CK(hipGetLastError());
+        STEP_CK(hipMemcpyAsync(q_out, J->q, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(status, J->st, (size_t)n, hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
     } while (false);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    if (err) {
-        char m[160];
-        snprintf(m, sizeof m, "graal_junction_scores: corrupt layout (contig labels or positions out of range, flags %u)", err);
-        h->err = m;
-        return GRAAL_E_STATE;
-    }
-    return GRAAL_OK;
+    return score_exit(h, "graal_junction_scores", rc, nullptr, err);
 }
 
 } // extern "C"

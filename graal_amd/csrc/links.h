@@ -1,5 +1,6 @@
 // links.h -- the likelihood every join between two contig ends would add, for every pair of ends the contacts support (graal_end_links).
-// Included by graal_hip.hip after junctions.h (it uses Ctx, Stat, centre_kb, rippe, to_q, k_jn_count, jn_trans and model_math.h).
+// Included by graal_hip.hip after junctions.h (it uses Ctx, Stat, centre_kb, rippe, to_q, k_jn_count, jn_trans, model_math.h, and
+// score_common.h's score_entry, score_exit, STEP_CK, free_null and CandTable).  LayoutRecs, below, is shared with insert.h.
 //
 // Ends.  end = 2 * f + side of a LINEAR contig: side 0 its head (position 0), side 1 its tail (position l_cont - 1), f the fragment there.
 // For ends eA < eB of different contigs A, B the joined layout is canonical: A oriented so that eA is its tail (A reversed iff eA is a head),
@@ -42,66 +43,6 @@ struct LnSub { int label, frag, meta, acc, start, len, lbp, pad; };   // meta: s
 struct LnFrag { int frag, start, len, fwd; Stat st; };              // per slot
 struct LnCtg { int head, tail, first, cnt, lbp, elig, nmix, pad; };   // per contig label; nmix: its bins of mixed RF counts
 
-struct LnBuf {
-    int n = 0, S = 0;
-    int *cnt = nullptr, *base = nullptr, *slot = nullptr, *lab = nullptr;
-    LnFrag* fr = nullptr;
-    LnSub* sub = nullptr;
-    LnCtg* ctg = nullptr;
-    long long* mir = nullptr; int* mirbad = nullptr;
-    unsigned* err = nullptr; unsigned long long* ctr = nullptr;       // ctr: [0] records counted, [1] listed keys, [2] eligible contigs
-    void* tmp = nullptr; size_t tmp_bytes = 0;
-    // the key table and the per-link arrays grow to the largest size a call needed (within GRAAL_LINKS_MAX_BYTES)
-    unsigned long long* keys = nullptr; long long *tq = nullptr, *tc = nullptr; int* tf = nullptr; unsigned char* tsel = nullptr; size_t cap = 0;
-    unsigned long long *ko = nullptr, *ks = nullptr; int *vo = nullptr, *vs = nullptr;
-    long long *q = nullptr, *c = nullptr, *ch = nullptr, *choff = nullptr; int* bad = nullptr; unsigned char* st = nullptr;
-    int *ea = nullptr, *eb = nullptr;
-    size_t lcap = 0;
-    void* stmp = nullptr; size_t stmp_bytes = 0;
-    long long n_links = -1;                                          // -1: no result to fetch
-    // graal_end_links_best: per end (2n) the best Q and partner, the mutual flag, and the mutual links compacted
-    long long* bq = nullptr; int* be = nullptr; unsigned char* bflag = nullptr; int *bsel = nullptr, *mea = nullptr, *meb = nullptr;
-    long long* mq = nullptr; size_t bcap = 0;
-    long long n_mutual = -1;                                         // -1: no result to fetch
-};
-
-void ln_free_table(LnBuf* b)
-{
-    void** p[] = {(void**)&b->keys, (void**)&b->tq, (void**)&b->tc, (void**)&b->tf, (void**)&b->tsel};
-    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
-    b->cap = 0;
-}
-
-void ln_free_links(LnBuf* b)
-{
-    void** p[] = {(void**)&b->ko, (void**)&b->ks, (void**)&b->vo, (void**)&b->vs, (void**)&b->q, (void**)&b->c, (void**)&b->bad, (void**)&b->ch,
-                  (void**)&b->choff, (void**)&b->st, (void**)&b->ea, (void**)&b->eb};
-    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
-    b->lcap = 0;
-}
-
-void ln_free_fixed(LnBuf* b)
-{
-    void** p[] = {(void**)&b->cnt, (void**)&b->base, (void**)&b->slot, (void**)&b->lab, (void**)&b->fr, (void**)&b->sub, (void**)&b->ctg,
-                  (void**)&b->mir, (void**)&b->mirbad, (void**)&b->err, (void**)&b->ctr, &b->tmp};
-    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
-    b->tmp_bytes = 0; b->n = 0; b->S = 0;
-}
-
-void ln_free_best(LnBuf* b)
-{
-    void** p[] = {(void**)&b->bq, (void**)&b->be, (void**)&b->bflag, (void**)&b->bsel, (void**)&b->mea, (void**)&b->meb, (void**)&b->mq};
-    for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
-    b->bcap = 0;
-}
-
-void ln_free(LnBuf* b)
-{
-    if (!b) return;
-    ln_free_fixed(b); ln_free_table(b); ln_free_links(b); ln_free_best(b);
-    if (b->stmp) (void)hipFree(b->stmp);
-    delete b;
-}
 
 __global__ __launch_bounds__(256) void k_ln_prep(SoaPtr s, int n, int min_frags, const Stat* __restrict__ stat, const int* __restrict__ sub_ids,
                                                  const int* __restrict__ cnt, const int* __restrict__ base, int* __restrict__ slot_of,
@@ -140,6 +81,113 @@ __global__ __launch_bounds__(256) void k_ln_prep(SoaPtr s, int n, int min_frags,
         u.acc = stat_accu(st, k) | (last << 16);                     // (RF counts are <= 30000)
         sub[sel3(ids.x, ids.y, ids.z, k)] = u;
     }
+}
+
+// The slots and records of a layout (k_jn_count / scan / k_ln_prep) and what is summed per contig label.  links.h and insert.h each own
+// one instance: no state is shared between their calls.
+struct LayoutRecs {
+    int n = 0, S = 0;
+    int *cnt = nullptr, *base = nullptr, *slot = nullptr, *lab = nullptr;
+    LnFrag* fr = nullptr;
+    LnSub* sub = nullptr;
+    LnCtg* ctg = nullptr;
+    long long* mir = nullptr; int* mirbad = nullptr;
+    unsigned* err = nullptr;
+    unsigned long long* ctr = nullptr;   // [0] records counted, [1] listed keys, [2] eligible contigs, [3] insert.h's pair records
+    void* tmp = nullptr; size_t tmp_bytes = 0;
+};
+
+void recs_free(LayoutRecs& R)
+{
+    free_null({(void**)&R.cnt, (void**)&R.base, (void**)&R.slot, (void**)&R.lab, (void**)&R.fr, (void**)&R.sub, (void**)&R.ctg, (void**)&R.mir,
+               (void**)&R.mirbad, (void**)&R.err, (void**)&R.ctr, &R.tmp});
+    R.tmp_bytes = 0; R.n = 0; R.S = 0;
+}
+
+// Sized to the engine's (n, S), reallocated when they change.  R.n stays 0 until the whole set is allocated (free_null).
+int recs_reserve(Ctx* h, LayoutRecs& R)
+{
+    const int n = h->n, S = h->n_sub_total;
+    if (R.n == n && R.S == S) return GRAAL_OK;
+    recs_free(R);
+    CK(hipMalloc(&R.cnt, sizeof(int) * (size_t)(n + 3)));
+    CK(hipMalloc(&R.base, sizeof(int) * (size_t)(n + 3)));
+    CK(hipMalloc(&R.slot, sizeof(int) * (size_t)n));
+    CK(hipMalloc(&R.lab, sizeof(int) * (size_t)n));
+    CK(hipMalloc(&R.fr, sizeof(LnFrag) * (size_t)n));
+    CK(hipMalloc(&R.sub, sizeof(LnSub) * (size_t)std::max(S, 1)));
+    CK(hipMalloc(&R.ctg, sizeof(LnCtg) * (size_t)(n + 3)));
+    CK(hipMalloc(&R.mir, sizeof(long long) * (size_t)(n + 3)));
+    CK(hipMalloc(&R.mirbad, sizeof(int) * (size_t)(n + 3)));
+    CK(hipMalloc(&R.err, sizeof(unsigned)));
+    CK(hipMalloc(&R.ctr, sizeof(unsigned long long) * 4));
+    size_t b1 = 0;
+    CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, R.cnt, R.base, n + 3, h->stream));
+    CK(hipMalloc(&R.tmp, b1));
+    R.tmp_bytes = b1;
+    R.n = n; R.S = S;
+    return GRAAL_OK;
+}
+
+// The records of the current layout, on the engine's stream.  R.err collects the flags of a corrupt layout: the caller reads it back
+// before anything trusts the slots or the sub-fragment records.
+int recs_build(Ctx* h, LayoutRecs& R, int min_frags)
+{
+    const int n = R.n;
+    hipStream_t s = h->stream;
+    int rc = GRAAL_OK;
+    do {
+        STEP_CK(hipMemsetAsync(R.err, 0, sizeof(unsigned), s));
+        STEP_CK(hipMemsetAsync(R.ctr, 0, sizeof(unsigned long long) * 4, s));
+        STEP_CK(hipMemsetAsync(R.cnt, 0, sizeof(int) * (size_t)(n + 3), s));
+        STEP_CK(hipMemsetAsync(R.ctg, 0, sizeof(LnCtg) * (size_t)(n + 3), s));   // (labels no fragment holds: not eligible)
+        STEP_CK(hipMemsetAsync(R.fr, 0, sizeof(LnFrag) * (size_t)n, s));
+        STEP_CK(hipMemsetAsync(R.mir, 0, sizeof(long long) * (size_t)(n + 3), s));
+        STEP_CK(hipMemsetAsync(R.mirbad, 0, sizeof(int) * (size_t)(n + 3), s));
+        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(h->soa[h->cur], n, R.cnt, R.err);
+        STEP_CK(hipGetLastError());
+        size_t tb = R.tmp_bytes;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(R.tmp, tb, R.cnt, R.base, n + 3, s));
+        k_ln_prep<<<blocks_for(n, 256), 256, 0, s>>>(h->soa[h->cur], n, min_frags, h->stat_frag, h->d_sub_ids, R.cnt, R.base, R.slot, R.lab, R.fr,
+                                                     R.sub, R.ctg, &R.ctr[2], R.err);
+        STEP_CK(hipGetLastError());
+    } while (false);
+    return rc;
+}
+
+struct LnBuf {
+    LayoutRecs R;
+    CandTable T;
+    // the table (T) and the per-link arrays grow to the largest size a call needed (within GRAAL_LINKS_MAX_BYTES)
+    unsigned long long *ko = nullptr, *ks = nullptr; int *vo = nullptr, *vs = nullptr;
+    long long *q = nullptr, *c = nullptr, *ch = nullptr, *choff = nullptr; int* bad = nullptr; unsigned char* st = nullptr;
+    int *ea = nullptr, *eb = nullptr;
+    size_t lcap = 0;
+    long long n_links = -1;                                          // -1: no result to fetch
+    // graal_end_links_best: per end (2n) the best Q and partner, the mutual flag, and the mutual links compacted
+    long long* bq = nullptr; int* be = nullptr; unsigned char* bflag = nullptr; int *bsel = nullptr, *mea = nullptr, *meb = nullptr;
+    long long* mq = nullptr; size_t bcap = 0;
+    long long n_mutual = -1;                                         // -1: no result to fetch
+};
+
+void ln_free_links(LnBuf* b)
+{
+    free_null({(void**)&b->ko, (void**)&b->ks, (void**)&b->vo, (void**)&b->vs, (void**)&b->q, (void**)&b->c, (void**)&b->bad, (void**)&b->ch,
+               (void**)&b->choff, (void**)&b->st, (void**)&b->ea, (void**)&b->eb});
+    b->lcap = 0;
+}
+
+void ln_free_best(LnBuf* b)
+{
+    free_null({(void**)&b->bq, (void**)&b->be, (void**)&b->bflag, (void**)&b->bsel, (void**)&b->mea, (void**)&b->meb, (void**)&b->mq});
+    b->bcap = 0;
+}
+
+void ln_free(LnBuf* b)
+{
+    if (!b) return;
+    recs_free(b->R); table_free(b->T); ln_free_links(b); ln_free_best(b);
+    delete b;
 }
 
 __device__ __forceinline__ int ln_k(int meta) { return meta & 3; }
@@ -369,57 +417,83 @@ __device__ __forceinline__ long long ln_wave_sum(long long v)
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_ln_mass(long long m, long long n_groups, const long long* __restrict__ choff, const long long* __restrict__ ch,
-                                                 const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ lab,
-                                                 const LnCtg* __restrict__ ctg, const LnFrag* __restrict__ fr, float nfpb, Par par, int quirk,
-                                                 int reach_bp, long long* __restrict__ q, int* __restrict__ bad)
+__device__ __forceinline__ void ln_block_add(long long v, long long nb, long long* __restrict__ q, int* __restrict__ bad)
 {
-    const int lane = threadIdx.x & 63;
-    const long long W = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (W >= n_groups) return;
-    // the link of group W: the last k with choff[k] <= W (links with no group never match)
+    v = ln_wave_sum(v);
+    nb = ln_wave_sum(nb);
+    if ((threadIdx.x & 63) == 0) {
+        if (v != 0) atomicAdd((unsigned long long*)q, (unsigned long long)v);
+        if (nb != 0) atomicAdd(bad, (int)nb);
+    }
+}
+
+// the link of wave group W: the last k with choff[k] <= W (links with no group never match)
+__device__ __forceinline__ long long ln_link_of_group(const long long* __restrict__ choff, long long m, long long W)
+{
     long long lo = 0, hi = m - 1;
     while (lo < hi) {
         const long long mid = (lo + hi + 1) >> 1;
         if (choff[mid] <= W) lo = mid; else hi = mid - 1;
     }
-    const long long k = lo;
+    return lo;
+}
+
+// A wave's lanes are 8 x 8 fragment pairs.  A lane's fragment of A in group g (8 fragments walked from eA), as the join places it; live
+// while its own gap to the joined end is inside the window.
+struct LnRow { LnFrag x; int gx, nsx; bool fx, live; };
+
+__device__ __forceinline__ void ln_group_row(const LnSide& A, int g, const LnFrag* __restrict__ fr, int reach_bp, LnRow& r)
+{
+    const int i = g * 8 + ((threadIdx.x & 63) >> 3);
+    r.gx = 0; r.nsx = 0; r.fx = false; r.live = i < A.cnt;
+    if (r.live) {
+        r.x = fr[ln_walk(A, i)];
+        r.gx = ln_gap(A, r.x);
+        r.nsx = ln_new_start(r.x.start, r.x.len, A.lbp, A.lbp, true, A.rev);
+        r.fx = (r.x.fwd != 0) != A.rev;
+        r.live = r.gx <= reach_bp;
+    }
+}
+
+// The mass of a group's rows against the window of B: the tile steps along B from eB, a Q-rounded term per fragment pair.  k_ln_mass and
+// k_lb_mass both price through here, so both give every fragment pair the same term.
+__device__ __forceinline__ void ln_group_mass(const LnRow& r, const LnSide& A, const LnSide& B, const LnFrag* __restrict__ fr, float nfpb,
+                                              const Par& par, int quirk, int reach_bp, long long& sum, long long& nb)
+{
+    const int jl = threadIdx.x & 7;
+    for (int j0 = 0; ; j0 += 8) {
+        const int j = j0 + jl;
+        bool in = r.live && j < B.cnt;
+        LnFrag y;
+        int gy = 0;
+        if (in) { y = fr[ln_walk(B, j)]; gy = ln_gap(B, y); in = (long long)r.gx + gy <= reach_bp; }
+        if (__ballot(in) == 0ull) break;                             // (the gap grows along both walks: no later tile is in the window)
+        if (in) {
+            const int nsy = ln_new_start(y.start, y.len, B.lbp, A.lbp, false, B.rev);
+            const long long t = to_q_fast(ln_pair_mass(r.x, r.nsx, r.fx, y, nsy, (y.fwd != 0) != B.rev, nfpb, par, quirk));
+            if (t == Q_BAD) nb++; else sum -= t;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ln_mass(long long m, long long n_groups, const long long* __restrict__ choff, const long long* __restrict__ ch,
+                                                 const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ lab,
+                                                 const LnCtg* __restrict__ ctg, const LnFrag* __restrict__ fr, float nfpb, Par par, int quirk,
+                                                 int reach_bp, long long* __restrict__ q, int* __restrict__ bad)
+{
+    const long long W = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (W >= n_groups) return;
+    const long long k = ln_link_of_group(choff, m, W);
     const long long g = W - choff[k];
     if (g < 0 || g >= ch[k]) return;
     const int e_a = ea[k], e_b = eb[k];
     const LnCtg CA = ctg[lab[e_a >> 1]], CB = ctg[lab[e_b >> 1]];
     const LnSide A = ln_side(CA, e_a & 1, true), B = ln_side(CB, e_b & 1, false);
-    const int i = g * 8 + (lane >> 3), jl = lane & 7;
-    LnFrag x;
-    int gx = 0, nsx = 0;
-    bool fx = false, live = i < A.cnt;
-    if (live) {
-        x = fr[ln_walk(A, i)];
-        gx = ln_gap(A, x);
-        nsx = ln_new_start(x.start, x.len, A.lbp, A.lbp, true, A.rev);
-        fx = (x.fwd != 0) != A.rev;
-        live = gx <= reach_bp;
-    }
+    LnRow r;
+    ln_group_row(A, (int)g, fr, reach_bp, r);
     long long sum = 0, nb = 0;
-    for (int j0 = 0; ; j0 += 8) {
-        const int j = j0 + jl;
-        bool in = live && j < B.cnt;
-        LnFrag y;
-        int gy = 0;
-        if (in) { y = fr[ln_walk(B, j)]; gy = ln_gap(B, y); in = (long long)gx + gy <= reach_bp; }
-        if (__ballot(in) == 0ull) break;                             // (the gap grows along both walks: no later tile is in the window)
-        if (in) {
-            const int nsy = ln_new_start(y.start, y.len, B.lbp, A.lbp, false, B.rev);
-            const long long t = to_q_fast(ln_pair_mass(x, nsx, fx, y, nsy, (y.fwd != 0) != B.rev, nfpb, par, quirk));
-            if (t == Q_BAD) nb++; else sum -= t;
-        }
-    }
-    sum = ln_wave_sum(sum);
-    nb = ln_wave_sum(nb);
-    if (lane == 0) {
-        if (sum != 0) atomicAdd((unsigned long long*)&q[k], (unsigned long long)sum);
-        if (nb != 0) atomicAdd(&bad[k], (int)nb);
-    }
+    ln_group_mass(r, A, B, fr, nfpb, par, quirk, reach_bp, sum, nb);
+    ln_block_add(sum, nb, &q[k], &bad[k]);
 }
 
 // mirror mass term of bins x (mixed, flipped) and y (x < y): -(sum of trans(x flipped) - trans(x as now)), rounded to Q
@@ -437,16 +511,6 @@ __device__ __forceinline__ long long ln_mirror_q(const LnFrag& x, const LnFrag& 
     }
     const long long q = to_q(acc);
     return q == Q_BAD ? Q_BAD : -q;
-}
-
-__device__ __forceinline__ void ln_block_add(long long v, long long nb, long long* __restrict__ q, int* __restrict__ bad)
-{
-    v = ln_wave_sum(v);
-    nb = ln_wave_sum(nb);
-    if ((threadIdx.x & 63) == 0) {
-        if (v != 0) atomicAdd((unsigned long long*)q, (unsigned long long)v);
-        if (nb != 0) atomicAdd(bad, (int)nb);
-    }
 }
 
 // mirror[C], the mass part: one block per mixed bin x of an eligible contig, against every later bin of another contig
@@ -495,50 +559,51 @@ __device__ __forceinline__ void ln_quirk_pair(const LnFrag& x, const LnFrag& y, 
     }
 }
 
-// A wave per (link, group of 8 fragments of A) -- k_ln_mass's groups -- over ALL of B: lanes are 8 x 8 fragment pairs, and a pair is
-// priced when one of its bins is mixed (ln_quirk_pair).  Links whose two contigs hold no mixed bin return at once.
+// Group g of 8 fragments of A over ALL of B: a pair is priced when one of its bins is mixed (ln_quirk_pair)
+__device__ __forceinline__ void ln_group_quirk(const LnSide& A, const LnSide& B, int g, const LnFrag* __restrict__ fr, float nfpb, const Par& par,
+                                               int reach_bp, long long& sum, long long& nb)
+{
+    const int lane = threadIdx.x & 63, i = g * 8 + (lane >> 3);
+    if (i >= A.cnt) return;
+    const LnFrag x = fr[ln_walk(A, i)];
+    const int gx = ln_gap(A, x);
+    const bool mx = !stat_uniform(x.st);
+    for (int j = lane & 7; j < B.cnt; j += 8) {
+        const LnFrag y = fr[ln_walk(B, j)];
+        if (!mx && stat_uniform(y.st)) continue;
+        ln_quirk_pair(x, y, (long long)gx + ln_gap(B, y) > reach_bp, A.rev, B.rev, nfpb, par, sum, nb);
+    }
+}
+
+// A wave per (link, group of 8 fragments of A) -- k_ln_mass's groups -- over ALL of B.  Links whose two contigs hold no mixed bin return at
+// once.
 __global__ __launch_bounds__(256) void k_ln_quirk(long long m, long long n_groups, const long long* __restrict__ choff, const long long* __restrict__ ch,
                                                   const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ lab,
                                                   const LnCtg* __restrict__ ctg, const LnFrag* __restrict__ fr, float nfpb, Par par, int reach_bp,
                                                   long long* __restrict__ q, int* __restrict__ bad)
 {
-    const int lane = threadIdx.x & 63;
     const long long W = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (W >= n_groups) return;
-    long long lo = 0, hi = m - 1;
-    while (lo < hi) {
-        const long long mid = (lo + hi + 1) >> 1;
-        if (choff[mid] <= W) lo = mid; else hi = mid - 1;
-    }
-    const long long k = lo;
+    const long long k = ln_link_of_group(choff, m, W);
     const long long g = W - choff[k];
     if (g < 0 || g >= ch[k]) return;
     const int e_a = ea[k], e_b = eb[k];
     const LnCtg CA = ctg[lab[e_a >> 1]], CB = ctg[lab[e_b >> 1]];
     if (CA.nmix == 0 && CB.nmix == 0) return;
     const LnSide A = ln_side(CA, e_a & 1, true), B = ln_side(CB, e_b & 1, false);
-    const long long i = g * 8 + (lane >> 3);
-    const int jl = lane & 7;
-    const bool live = i < A.cnt;
-    LnFrag x;
-    int gx = 0;
-    bool mx = false;
-    if (live) { x = fr[ln_walk(A, (int)i)]; gx = ln_gap(A, x); mx = !stat_uniform(x.st); }
-    if (__ballot(live) == 0ull) return;
+    if (__ballot(g * 8 + ((threadIdx.x & 63) >> 3) < A.cnt) == 0ull) return;
     long long sum = 0, nb = 0;
-    for (int j0 = 0; j0 < B.cnt; j0 += 8) {
-        const int j = j0 + jl;
-        if (!live || j >= B.cnt) continue;
-        const LnFrag y = fr[ln_walk(B, j)];
-        if (!mx && stat_uniform(y.st)) continue;
-        ln_quirk_pair(x, y, (long long)gx + ln_gap(B, y) > reach_bp, A.rev, B.rev, nfpb, par, sum, nb);
-    }
-    sum = ln_wave_sum(sum);
-    nb = ln_wave_sum(nb);
-    if (lane == 0) {
-        if (sum != 0) atomicAdd((unsigned long long*)&q[k], (unsigned long long)sum);
-        if (nb != 0) atomicAdd(&bad[k], (int)nb);
-    }
+    ln_group_quirk(A, B, (int)g, fr, nfpb, par, reach_bp, sum, nb);
+    ln_block_add(sum, nb, &q[k], &bad[k]);
+}
+
+// the mirrors of the contigs a link (eA, eB) reverses: A when its end is a head, B when its end is a tail
+__device__ __forceinline__ void ln_add_mirrors(int e_a, int e_b, const int* __restrict__ lab, const long long* __restrict__ mir,
+                                               const int* __restrict__ mirbad, long long& v, int& b)
+{
+    const int ca = lab[e_a >> 1], cb = lab[e_b >> 1];
+    if ((e_a & 1) == 0) { v += mir[ca]; b += mirbad[ca]; }
+    if ((e_b & 1) == 1) { v += mir[cb]; b += mirbad[cb]; }
 }
 
 __global__ void k_ln_out(long long m, const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ lab,
@@ -549,18 +614,14 @@ __global__ void k_ln_out(long long m, const int* __restrict__ ea, const int* __r
     if (k >= m) return;
     long long v = q[k];
     int b = bad[k];
-    if (quirk) {
-        const int ca = lab[ea[k] >> 1], cb = lab[eb[k] >> 1];
-        if ((ea[k] & 1) == 0) { v += mir[ca]; b += mirbad[ca]; }      // A reversed (its end is a head)
-        if ((eb[k] & 1) == 1) { v += mir[cb]; b += mirbad[cb]; }      // B reversed (its end is a tail)
-    }
+    if (quirk) ln_add_mirrors(ea[k], eb[k], lab, mir, mirbad, v, b);
     st[k] = b ? GRAAL_LINK_NONFINITE : GRAAL_LINK_VALID;
     q[k] = b ? 0 : v;
 }
 
 // ---- graal_end_links_best: the same scored links without the materialised output.  A wave per slot of the candidate table (unlisted
-// slots return at once) walks the groups of 8 fragments of A from eA that k_ln_mass's waves would cover, so every fragment pair gets the
-// same Q-rounded term and the int64 sums are the same; the final score stays in the table (tq), then two atomic passes per end.
+// slots return at once) walks the groups of 8 fragments of A from eA that k_ln_mass's waves would cover, through the same ln_group_mass /
+// ln_group_quirk, so every fragment pair gets the same Q-rounded term and the int64 sums are the same; the final score stays in the table (tq), then two atomic passes per end.
 __device__ __forceinline__ bool lb_listed(const unsigned long long* __restrict__ keys, const int* __restrict__ tf, long long i)
 {
     return keys[i] != LN_EMPTY && (tf[i] & 2);
@@ -577,34 +638,12 @@ __global__ __launch_bounds__(256) void k_lb_mass(long long cap, const unsigned l
     const int e_a = (int)(key >> 32), e_b = (int)(key & 0xffffffffull);
     const LnCtg CA = ctg[lab[e_a >> 1]], CB = ctg[lab[e_b >> 1]];
     const LnSide A = ln_side(CA, e_a & 1, true), B = ln_side(CB, e_b & 1, false);
-    const int jl = lane & 7;
     long long sum = 0, nb = 0;
     for (int g = 0; g * 8 < A.cnt; g++) {
-        const int i = g * 8 + (lane >> 3);
-        LnFrag x;
-        int gx = 0, nsx = 0;
-        bool fx = false, live = i < A.cnt;
-        if (live) {
-            x = fr[ln_walk(A, i)];
-            gx = ln_gap(A, x);
-            nsx = ln_new_start(x.start, x.len, A.lbp, A.lbp, true, A.rev);
-            fx = (x.fwd != 0) != A.rev;
-            live = gx <= reach_bp;
-        }
-        if (__ballot(live) == 0ull) break;                           // (the gap grows along the walk of A: no later group is in the window)
-        for (int j0 = 0; ; j0 += 8) {
-            const int j = j0 + jl;
-            bool in = live && j < B.cnt;
-            LnFrag y;
-            int gy = 0;
-            if (in) { y = fr[ln_walk(B, j)]; gy = ln_gap(B, y); in = (long long)gx + gy <= reach_bp; }
-            if (__ballot(in) == 0ull) break;
-            if (in) {
-                const int nsy = ln_new_start(y.start, y.len, B.lbp, A.lbp, false, B.rev);
-                const long long t = to_q_fast(ln_pair_mass(x, nsx, fx, y, nsy, (y.fwd != 0) != B.rev, nfpb, par, quirk));
-                if (t == Q_BAD) nb++; else sum -= t;
-            }
-        }
+        LnRow r;
+        ln_group_row(A, g, fr, reach_bp, r);
+        if (__ballot(r.live) == 0ull) break;                         // (the gap grows along the walk of A: no later group is in the window)
+        ln_group_mass(r, A, B, fr, nfpb, par, quirk, reach_bp, sum, nb);
     }
     sum = ln_wave_sum(sum);
     nb = ln_wave_sum(nb);
@@ -626,20 +665,8 @@ __global__ __launch_bounds__(256) void k_lb_quirk(long long cap, const unsigned 
     const LnCtg CA = ctg[lab[e_a >> 1]], CB = ctg[lab[e_b >> 1]];
     if (CA.nmix == 0 && CB.nmix == 0) return;
     const LnSide A = ln_side(CA, e_a & 1, true), B = ln_side(CB, e_b & 1, false);
-    const int jl = lane & 7;
     long long sum = 0, nb = 0;
-    for (int g = 0; g * 8 < A.cnt; g++) {
-        const int i = g * 8 + (lane >> 3);
-        if (i >= A.cnt) continue;
-        const LnFrag x = fr[ln_walk(A, i)];
-        const int gx = ln_gap(A, x);
-        const bool mx = !stat_uniform(x.st);
-        for (int j = jl; j < B.cnt; j += 8) {
-            const LnFrag y = fr[ln_walk(B, j)];
-            if (!mx && stat_uniform(y.st)) continue;
-            ln_quirk_pair(x, y, (long long)gx + ln_gap(B, y) > reach_bp, A.rev, B.rev, nfpb, par, sum, nb);
-        }
-    }
+    for (int g = 0; g * 8 < A.cnt; g++) ln_group_quirk(A, B, g, fr, nfpb, par, reach_bp, sum, nb);
     sum = ln_wave_sum(sum);
     nb = ln_wave_sum(nb);
     if (lane == 0) {
@@ -664,11 +691,7 @@ __global__ void k_lb_out(long long cap, const unsigned long long* __restrict__ k
     const int ea = (int)(keys[i] >> 32), eb = (int)(keys[i] & 0xffffffffull);
     long long v = tq[i];
     int b = tf[i] & 1;
-    if (quirk) {
-        const int ca = lab[ea >> 1], cb = lab[eb >> 1];
-        if ((ea & 1) == 0) { v += mir[ca]; b += mirbad[ca]; }
-        if ((eb & 1) == 1) { v += mir[cb]; b += mirbad[cb]; }
-    }
+    if (quirk) ln_add_mirrors(ea, eb, lab, mir, mirbad, v, b);
     if (b) return;
     tq[i] = v;
     tf[i] |= 4;
@@ -711,6 +734,39 @@ __global__ void k_lb_gather(long long m, const int* __restrict__ sel, const long
     ea[k] = e; eb[k] = be[e]; q[k] = bq[e];
 }
 
+
+// The front half of graal_end_links and graal_end_links_best: the records, the count pass, and the table size `cap` for its upper bound
+// of the distinct keys.  err: the flags of a corrupt layout (the slots and the sub-fragment records are not to be trusted, nothing
+// reads them).
+struct LnCount { unsigned err = 0; unsigned long long ctr[3] = {0, 0, 0}, bound = 0, cap = 0; int nb = 1; };
+
+int ln_count(Ctx* h, LayoutRecs& R, int min_frags, int quirk, LnCount& C)
+{
+    hipStream_t s = h->stream;
+    int rc = GRAAL_OK;
+    do {
+        if ((rc = recs_build(h, R, min_frags))) break;
+        STEP_CK(hipMemcpyAsync(&C.err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
+        if (C.err) break;
+        const long long waves = (h->nnz + 63) / 64;
+        C.nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
+        if (h->nnz > 0) {
+            k_ln_nnz<true><<<C.nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, h->nfpb, h->par, quirk, 0, nullptr,
+                                                nullptr, nullptr, nullptr, nullptr, nullptr, &R.ctr[0], R.err);
+            STEP_CK(hipGetLastError());
+        }
+        STEP_CK(hipMemcpyAsync(&C.err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(C.ctr, R.ctr, sizeof C.ctr, hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
+        if (C.err) break;
+        const unsigned long long E = 2ull * C.ctr[2];
+        C.bound = std::min<unsigned long long>(C.ctr[0], E * (E > 0 ? E - 1 : 0) / 2);
+        C.cap = table_cap(C.bound);
+    } while (false);
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -719,162 +775,89 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
 {
     if (!h || !n_links) return GRAAL_E_ARG;
     if (min_frags < 1) return fail(h, GRAAL_E_ARG, "graal_end_links: min_frags must be >= 1");
-    if (!(h->have_sub && h->have_par && h->have_frags && h->have_contacts))
-        return fail(h, GRAAL_E_STATE, "graal_end_links: upload sub-fragments, parameters, fragments and contacts first");
-    if (h->has_rep) return fail(h, GRAAL_E_UNSUPPORTED, "graal_end_links: bins with several copies (graal_upload_repeats) are not supported");
-    if (h->x_host || h->nccl_comm) return fail(h, GRAAL_E_STATE, "graal_end_links: one rank only (an exchange or RCCL is attached)");
-    CK(hipSetDevice(h->device));
+    if (const int rc = score_entry(h, "graal_end_links")) return rc;
     *n_links = 0;
-    const int n = h->n, S = h->n_sub_total;
+    const int n = h->n;
     if (!h->ln) h->ln = new LnBuf();
     LnBuf* Lb = h->ln;
+    LayoutRecs& R = Lb->R;
+    CandTable& T = Lb->T;
     Lb->n_links = -1;
     if (n < 1) { Lb->n_links = 0; return GRAAL_OK; }
     hipStream_t s = h->stream;
-    if (Lb->n != n || Lb->S != S) {
-        // (every pointer is freed AND nulled, and Lb->n stays 0 until the whole set is allocated: a failed hipMalloc leaves nothing to free twice)
-        ln_free_fixed(Lb);
-        CK(hipMalloc(&Lb->cnt, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->base, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->slot, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&Lb->lab, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&Lb->fr, sizeof(LnFrag) * (size_t)n));
-        CK(hipMalloc(&Lb->sub, sizeof(LnSub) * (size_t)std::max(S, 1)));
-        CK(hipMalloc(&Lb->ctg, sizeof(LnCtg) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->mir, sizeof(long long) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->mirbad, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->err, sizeof(unsigned)));
-        CK(hipMalloc(&Lb->ctr, sizeof(unsigned long long) * 3));
-        size_t b1 = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, Lb->cnt, Lb->base, n + 3, s));
-        CK(hipMalloc(&Lb->tmp, b1));
-        Lb->tmp_bytes = b1;
-        Lb->n = n; Lb->S = S;
-    }
-    const SoaPtr sp = h->soa[h->cur];
+    if (const int rc = recs_reserve(h, R)) return rc;
     const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     const int mq = quirk && h->n_ubins > 0;
     int rc = GRAAL_OK;
-    unsigned err = 0;
-    unsigned long long ctr[3] = {0, 0, 0};
+    LnCount C;
     long long m = 0;
     const char* why = nullptr;
     char msg[320];
     do {
-#define LN_CK(call) { const hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = hipGetErrorString(e_); rc = GRAAL_E_HIP; break; } }
-        // ---- records
-        LN_CK(hipMemsetAsync(Lb->err, 0, sizeof(unsigned), s));
-        LN_CK(hipMemsetAsync(Lb->ctr, 0, sizeof(unsigned long long) * 3, s));
-        LN_CK(hipMemsetAsync(Lb->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
-        LN_CK(hipMemsetAsync(Lb->ctg, 0, sizeof(LnCtg) * (size_t)(n + 3), s));   // (labels no fragment holds: not eligible)
-        LN_CK(hipMemsetAsync(Lb->fr, 0, sizeof(LnFrag) * (size_t)n, s));
-        LN_CK(hipMemsetAsync(Lb->mir, 0, sizeof(long long) * (size_t)(n + 3), s));
-        LN_CK(hipMemsetAsync(Lb->mirbad, 0, sizeof(int) * (size_t)(n + 3), s));
-        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, Lb->cnt, Lb->err);
-        LN_CK(hipGetLastError());
-        size_t tb = Lb->tmp_bytes;
-        LN_CK(hipcub::DeviceScan::ExclusiveSum(Lb->tmp, tb, Lb->cnt, Lb->base, n + 3, s));
-        k_ln_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, min_frags, h->stat_frag, h->d_sub_ids, Lb->cnt, Lb->base, Lb->slot, Lb->lab, Lb->fr,
-                                                     Lb->sub, Lb->ctg, &Lb->ctr[2], Lb->err);
-        LN_CK(hipGetLastError());
-        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        LN_CK(hipStreamSynchronize(s));
-        if (err) break;   // (a corrupt layout: the slots and the sub-fragment records are not to be trusted, nothing reads them)
-        // ---- count pass: an upper bound of the distinct keys
-        const long long waves = (h->nnz + 63) / 64;
-        const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
-        if (h->nnz > 0) {
-            k_ln_nnz<true><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, Lb->sub, h->stat_frag, Lb->ctg, h->nfpb, h->par, quirk, 0, nullptr,
-                                              nullptr, nullptr, nullptr, nullptr, nullptr, &Lb->ctr[0], Lb->err);
-            LN_CK(hipGetLastError());
-        }
-        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        LN_CK(hipMemcpyAsync(ctr, Lb->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
-        LN_CK(hipStreamSynchronize(s));
-        if (err) break;
-        const unsigned long long E = 2ull * ctr[2];
-        const unsigned long long bound = std::min<unsigned long long>(ctr[0], E * (E > 0 ? E - 1 : 0) / 2);
-        const unsigned long long cap = bound + bound / 2 + 64;       // (load factor <= 2/3)
-        const unsigned long long L = bound + 1;
+        if ((rc = ln_count(h, R, min_frags, quirk, C)) || C.err) break;
+        const unsigned long long cap = C.cap, L = C.bound + 1;
         // device memory: the table (key, q, contacts, flags, selection byte per slot), the per-link arrays sized to the bound (keys x2,
         // indices x2, q, contacts, groups x2, bad, ends x2, status) and the hipCUB temp storage of the selection, the sort and the scan
-        unsigned long long need = cap * (unsigned long long)(8 + 8 + 8 + 4 + 1) + L * (unsigned long long)(8 * 2 + 4 * 2 + 8 + 8 + 8 * 2 + 4 + 4 * 2 + 1);
+        unsigned long long need = cap * TABLE_SLOT_BYTES + L * (unsigned long long)(8 * 2 + 4 * 2 + 8 + 8 + 8 * 2 + 4 + 4 * 2 + 1);
         size_t b_sel = 0, b_sort = 0, b_scan = 0;
         if (cap < (unsigned long long)INT_MAX) {
-            LN_CK(hipcub::DeviceSelect::Flagged(nullptr, b_sel, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr, (int*)nullptr,
-                                                (unsigned long long*)nullptr, (int)cap, s));
-            LN_CK(hipcub::DeviceRadixSort::SortPairs(nullptr, b_sort, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                                     (const int*)nullptr, (int*)nullptr, (int)L, 0, 64, s));
-            LN_CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b_scan, (const long long*)nullptr, (long long*)nullptr, (int)L, s));
+            STEP_CK(hipcub::DeviceSelect::Flagged(nullptr, b_sel, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr, (int*)nullptr,
+                                                  (unsigned long long*)nullptr, (int)cap, s));
+            STEP_CK(hipcub::DeviceRadixSort::SortPairs(nullptr, b_sort, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                                       (const int*)nullptr, (int*)nullptr, (int)L, 0, 64, s));
+            STEP_CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b_scan, (const long long*)nullptr, (long long*)nullptr, (int)L, s));
         }
         const size_t tneed = std::max(b_sel, std::max(b_sort, b_scan));
         need += tneed;
         if (cap >= (unsigned long long)INT_MAX || need > (unsigned long long)GRAAL_LINKS_MAX_BYTES) {
             snprintf(msg, sizeof msg, "graal_end_links: the candidate table needs %llu bytes (%llu records counted), over the budget of %llu bytes "
-                     "(GRAAL_LINKS_MAX_BYTES): use a larger min_frags", need, ctr[0], (unsigned long long)GRAAL_LINKS_MAX_BYTES);
+                     "(GRAAL_LINKS_MAX_BYTES): use a larger min_frags", need, C.ctr[0], (unsigned long long)GRAAL_LINKS_MAX_BYTES);
             why = msg;
             break;
         }
-        if (cap > Lb->cap) {
-            ln_free_table(Lb);
-            LN_CK(hipMalloc(&Lb->keys, sizeof(unsigned long long) * cap));
-            LN_CK(hipMalloc(&Lb->tq, sizeof(long long) * cap));
-            LN_CK(hipMalloc(&Lb->tc, sizeof(long long) * cap));
-            LN_CK(hipMalloc(&Lb->tf, sizeof(int) * cap));
-            LN_CK(hipMalloc(&Lb->tsel, cap));
-            Lb->cap = cap;
-        }
-        // (the table is used at size `cap`, whatever its allocation: the probe sequence depends on it)
-        LN_CK(hipMemsetAsync(Lb->keys, 0xff, sizeof(unsigned long long) * cap, s));
-        LN_CK(hipMemsetAsync(Lb->tq, 0, sizeof(long long) * cap, s));
-        LN_CK(hipMemsetAsync(Lb->tc, 0, sizeof(long long) * cap, s));
-        LN_CK(hipMemsetAsync(Lb->tf, 0, sizeof(int) * cap, s));
+        STEP_CK(table_reserve(T, cap));
+        STEP_CK(table_clear(T, cap, s));
         if (L > Lb->lcap) {
             ln_free_links(Lb);
-            LN_CK(hipMalloc(&Lb->ko, sizeof(unsigned long long) * L)); LN_CK(hipMalloc(&Lb->ks, sizeof(unsigned long long) * L));
-            LN_CK(hipMalloc(&Lb->vo, sizeof(int) * L)); LN_CK(hipMalloc(&Lb->vs, sizeof(int) * L));
-            LN_CK(hipMalloc(&Lb->q, sizeof(long long) * L)); LN_CK(hipMalloc(&Lb->c, sizeof(long long) * L));
-            LN_CK(hipMalloc(&Lb->ch, sizeof(long long) * L)); LN_CK(hipMalloc(&Lb->choff, sizeof(long long) * L));
-            LN_CK(hipMalloc(&Lb->bad, sizeof(int) * L));
-            LN_CK(hipMalloc(&Lb->ea, sizeof(int) * L)); LN_CK(hipMalloc(&Lb->eb, sizeof(int) * L)); LN_CK(hipMalloc(&Lb->st, L));
+            STEP_CK(hipMalloc(&Lb->ko, sizeof(unsigned long long) * L)); STEP_CK(hipMalloc(&Lb->ks, sizeof(unsigned long long) * L));
+            STEP_CK(hipMalloc(&Lb->vo, sizeof(int) * L)); STEP_CK(hipMalloc(&Lb->vs, sizeof(int) * L));
+            STEP_CK(hipMalloc(&Lb->q, sizeof(long long) * L)); STEP_CK(hipMalloc(&Lb->c, sizeof(long long) * L));
+            STEP_CK(hipMalloc(&Lb->ch, sizeof(long long) * L)); STEP_CK(hipMalloc(&Lb->choff, sizeof(long long) * L));
+            STEP_CK(hipMalloc(&Lb->bad, sizeof(int) * L));
+            STEP_CK(hipMalloc(&Lb->ea, sizeof(int) * L)); STEP_CK(hipMalloc(&Lb->eb, sizeof(int) * L)); STEP_CK(hipMalloc(&Lb->st, L));
             Lb->lcap = L;
         }
-        if (tneed > Lb->stmp_bytes) {
-            if (Lb->stmp) (void)hipFree(Lb->stmp);
-            Lb->stmp = nullptr; Lb->stmp_bytes = 0;
-            LN_CK(hipMalloc(&Lb->stmp, tneed));
-            Lb->stmp_bytes = tneed;
-        }
+        STEP_CK(scratch_reserve(T, tneed));
         // ---- insert pass, selection of the listed slots, sort by key
         if (h->nnz > 0) {
-            k_ln_nnz<false><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, Lb->sub, h->stat_frag, Lb->ctg, h->nfpb, h->par, quirk, cap, Lb->keys,
-                                               Lb->tq, Lb->tc, Lb->tf, Lb->mir, Lb->mirbad, &Lb->ctr[0], Lb->err);
-            LN_CK(hipGetLastError());
+            k_ln_nnz<false><<<C.nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, h->nfpb, h->par, quirk, cap, T.keys,
+                                                 T.tq, T.tc, T.tf, R.mir, R.mirbad, &R.ctr[0], R.err);
+            STEP_CK(hipGetLastError());
         }
-        k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(Lb->keys, Lb->tf, (long long)cap, Lb->tsel);
-        LN_CK(hipGetLastError());
-        tb = Lb->stmp_bytes;
-        LN_CK(hipcub::DeviceSelect::Flagged(Lb->stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)Lb->tsel, Lb->vo, &Lb->ctr[1],
-                                            (int)cap, s));
-        LN_CK(hipMemcpyAsync(ctr, Lb->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
-        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        LN_CK(hipStreamSynchronize(s));
-        if (err) break;
-        m = (long long)ctr[1];
+        k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(T.keys, T.tf, (long long)cap, T.tsel);
+        STEP_CK(hipGetLastError());
+        size_t tb = T.stmp_bytes;
+        STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)T.tsel, Lb->vo, &R.ctr[1],
+                                              (int)cap, s));
+        STEP_CK(hipMemcpyAsync(C.ctr, R.ctr, sizeof C.ctr, hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(&C.err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
+        if (C.err) break;
+        m = (long long)C.ctr[1];
         if (m == 0) break;
-        k_ln_keys<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->keys, Lb->vo, Lb->ko);
-        LN_CK(hipGetLastError());
-        tb = Lb->stmp_bytes;
-        LN_CK(hipcub::DeviceRadixSort::SortPairs(Lb->stmp, tb, Lb->ko, Lb->ks, Lb->vo, Lb->vs, (int)m, 0, 64, s));
-        k_ln_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->ks, Lb->vs, Lb->tq, Lb->tc, Lb->tf, Lb->lab, Lb->ctg, Lb->q, Lb->c, Lb->bad, Lb->ch,
-                                                       Lb->ea, Lb->eb);
-        LN_CK(hipGetLastError());
-        tb = Lb->stmp_bytes;
-        LN_CK(hipcub::DeviceScan::ExclusiveSum(Lb->stmp, tb, Lb->ch, Lb->choff, (int)m, s));
+        k_ln_keys<<<blocks_for(m, 256), 256, 0, s>>>(m, T.keys, Lb->vo, Lb->ko);
+        STEP_CK(hipGetLastError());
+        tb = T.stmp_bytes;
+        STEP_CK(hipcub::DeviceRadixSort::SortPairs(T.stmp, tb, Lb->ko, Lb->ks, Lb->vo, Lb->vs, (int)m, 0, 64, s));
+        k_ln_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->ks, Lb->vs, T.tq, T.tc, T.tf, R.lab, R.ctg, Lb->q, Lb->c, Lb->bad, Lb->ch, Lb->ea,
+                                                       Lb->eb);
+        STEP_CK(hipGetLastError());
+        tb = T.stmp_bytes;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(T.stmp, tb, Lb->ch, Lb->choff, (int)m, s));
         long long last[2] = {0, 0};
-        LN_CK(hipMemcpyAsync(&last[0], Lb->choff + (m - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
-        LN_CK(hipMemcpyAsync(&last[1], Lb->ch + (m - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
-        LN_CK(hipStreamSynchronize(s));
+        STEP_CK(hipMemcpyAsync(&last[0], Lb->choff + (m - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(&last[1], Lb->ch + (m - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
         const long long groups = last[0] + last[1];
         if ((groups + 3) / 4 > (long long)INT_MAX) {
             snprintf(msg, sizeof msg, "graal_end_links: %lld wave groups exceed one launch: use a larger min_frags", groups);
@@ -883,30 +866,23 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
         }
         // ---- the mass pass, the quirk's passes, the result
         if (groups > 0) {
-            k_ln_mass<<<(unsigned)((groups + 3) / 4), 256, 0, s>>>(m, groups, Lb->choff, Lb->ch, Lb->ea, Lb->eb, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par,
+            k_ln_mass<<<(unsigned)((groups + 3) / 4), 256, 0, s>>>(m, groups, Lb->choff, Lb->ch, Lb->ea, Lb->eb, R.lab, R.ctg, R.fr, h->nfpb, h->par,
                                                                  quirk, reach_bp(h), Lb->q, Lb->bad);
-            LN_CK(hipGetLastError());
+            STEP_CK(hipGetLastError());
         }
         if (mq) {
-            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, Lb->slot, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par, Lb->mir, Lb->mirbad);
-            LN_CK(hipGetLastError());
+            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, R.mir, R.mirbad);
+            STEP_CK(hipGetLastError());
             if (groups > 0)
-                k_ln_quirk<<<(unsigned)((groups + 3) / 4), 256, 0, s>>>(m, groups, Lb->choff, Lb->ch, Lb->ea, Lb->eb, Lb->lab, Lb->ctg, Lb->fr, h->nfpb,
+                k_ln_quirk<<<(unsigned)((groups + 3) / 4), 256, 0, s>>>(m, groups, Lb->choff, Lb->ch, Lb->ea, Lb->eb, R.lab, R.ctg, R.fr, h->nfpb,
                                                                       h->par, reach_bp(h), Lb->q, Lb->bad);
-            LN_CK(hipGetLastError());
+            STEP_CK(hipGetLastError());
         }
-        k_ln_out<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->ea, Lb->eb, Lb->lab, Lb->mir, Lb->mirbad, mq, Lb->q, Lb->bad, Lb->st);
-        LN_CK(hipGetLastError());
-        LN_CK(hipStreamSynchronize(s));
-#undef LN_CK
+        k_ln_out<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->ea, Lb->eb, R.lab, R.mir, R.mirbad, mq, Lb->q, Lb->bad, Lb->st);
+        STEP_CK(hipGetLastError());
+        STEP_CK(hipStreamSynchronize(s));
     } while (false);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    if (why) { h->err = why; return GRAAL_E_UNSUPPORTED; }
-    if (err) {
-        snprintf(msg, sizeof msg, "graal_end_links: corrupt layout (contig labels or positions out of range, flags %u)", err);
-        h->err = msg;
-        return GRAAL_E_STATE;
-    }
+    if (const int r = score_exit(h, "graal_end_links", rc, why, C.err)) return r;
     Lb->n_links = m;
     *n_links = m;
     return GRAAL_OK;
@@ -935,168 +911,91 @@ int graal_end_links_best(graal_ctx* h, int32_t min_frags, int32_t* best_end, int
 {
     if (!h || !best_end || !best_q || !n_mutual) return GRAAL_E_ARG;
     if (min_frags < 1) return fail(h, GRAAL_E_ARG, "graal_end_links_best: min_frags must be >= 1");
-    if (!(h->have_sub && h->have_par && h->have_frags && h->have_contacts))
-        return fail(h, GRAAL_E_STATE, "graal_end_links_best: upload sub-fragments, parameters, fragments and contacts first");
-    if (h->has_rep) return fail(h, GRAAL_E_UNSUPPORTED, "graal_end_links_best: bins with several copies (graal_upload_repeats) are not supported");
-    if (h->x_host || h->nccl_comm) return fail(h, GRAAL_E_STATE, "graal_end_links_best: one rank only (an exchange or RCCL is attached)");
-    CK(hipSetDevice(h->device));
+    if (const int rc = score_entry(h, "graal_end_links_best")) return rc;
     *n_mutual = 0;
-    const int n = h->n, S = h->n_sub_total;
+    const int n = h->n;
     const long long n2 = 2ll * n;
     if (!h->ln) h->ln = new LnBuf();
     LnBuf* Lb = h->ln;
+    LayoutRecs& R = Lb->R;
+    CandTable& T = Lb->T;
     Lb->n_mutual = -1;
     if (n < 1) { Lb->n_mutual = 0; return GRAAL_OK; }
     hipStream_t s = h->stream;
-    if (Lb->n != n || Lb->S != S) {   // (graal_end_links' fixed buffers, allocated the same way)
-        ln_free_fixed(Lb);
-        CK(hipMalloc(&Lb->cnt, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->base, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->slot, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&Lb->lab, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&Lb->fr, sizeof(LnFrag) * (size_t)n));
-        CK(hipMalloc(&Lb->sub, sizeof(LnSub) * (size_t)std::max(S, 1)));
-        CK(hipMalloc(&Lb->ctg, sizeof(LnCtg) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->mir, sizeof(long long) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->mirbad, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&Lb->err, sizeof(unsigned)));
-        CK(hipMalloc(&Lb->ctr, sizeof(unsigned long long) * 3));
-        size_t b1 = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, Lb->cnt, Lb->base, n + 3, s));
-        CK(hipMalloc(&Lb->tmp, b1));
-        Lb->tmp_bytes = b1;
-        Lb->n = n; Lb->S = S;
-    }
-    const SoaPtr sp = h->soa[h->cur];
+    if (const int rc = recs_reserve(h, R)) return rc;
     const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     const int mq = quirk && h->n_ubins > 0;
     int rc = GRAAL_OK;
-    unsigned err = 0;
-    unsigned long long ctr[3] = {0, 0, 0};
+    LnCount C;
     long long m = 0;
     const char* why = nullptr;
     char msg[320];
     do {
-#define LN_CK(call) { const hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = hipGetErrorString(e_); rc = GRAAL_E_HIP; break; } }
-        // ---- records, as graal_end_links
-        LN_CK(hipMemsetAsync(Lb->err, 0, sizeof(unsigned), s));
-        LN_CK(hipMemsetAsync(Lb->ctr, 0, sizeof(unsigned long long) * 3, s));
-        LN_CK(hipMemsetAsync(Lb->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
-        LN_CK(hipMemsetAsync(Lb->ctg, 0, sizeof(LnCtg) * (size_t)(n + 3), s));
-        LN_CK(hipMemsetAsync(Lb->fr, 0, sizeof(LnFrag) * (size_t)n, s));
-        LN_CK(hipMemsetAsync(Lb->mir, 0, sizeof(long long) * (size_t)(n + 3), s));
-        LN_CK(hipMemsetAsync(Lb->mirbad, 0, sizeof(int) * (size_t)(n + 3), s));
-        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, Lb->cnt, Lb->err);
-        LN_CK(hipGetLastError());
-        size_t tb = Lb->tmp_bytes;
-        LN_CK(hipcub::DeviceScan::ExclusiveSum(Lb->tmp, tb, Lb->cnt, Lb->base, n + 3, s));
-        k_ln_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, min_frags, h->stat_frag, h->d_sub_ids, Lb->cnt, Lb->base, Lb->slot, Lb->lab, Lb->fr,
-                                                     Lb->sub, Lb->ctg, &Lb->ctr[2], Lb->err);
-        LN_CK(hipGetLastError());
-        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        LN_CK(hipStreamSynchronize(s));
-        if (err) break;
-        // ---- count pass
-        const long long waves = (h->nnz + 63) / 64;
-        const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
-        if (h->nnz > 0) {
-            k_ln_nnz<true><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, Lb->sub, h->stat_frag, Lb->ctg, h->nfpb, h->par, quirk, 0, nullptr,
-                                              nullptr, nullptr, nullptr, nullptr, nullptr, &Lb->ctr[0], Lb->err);
-            LN_CK(hipGetLastError());
-        }
-        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        LN_CK(hipMemcpyAsync(ctr, Lb->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
-        LN_CK(hipStreamSynchronize(s));
-        if (err) break;
-        const unsigned long long E = 2ull * ctr[2];
-        const unsigned long long bound = std::min<unsigned long long>(ctr[0], E * (E > 0 ? E - 1 : 0) / 2);
-        const unsigned long long cap = bound + bound / 2 + 64;
+        if ((rc = ln_count(h, R, min_frags, quirk, C)) || C.err) break;
+        const unsigned long long cap = C.cap;
         // device memory: the table (key, q, contacts, flags, selection byte per slot), the per-end arrays (best q, best partner, flag,
         // selected end, mutual end_a / end_b / q) and the hipCUB temp storage of the selection over the ends -- no per-link arrays
-        unsigned long long need = cap * (unsigned long long)(8 + 8 + 8 + 4 + 1) + (unsigned long long)n2 * (8 + 4 + 1 + 4 + 4 + 4 + 8);
+        unsigned long long need = cap * TABLE_SLOT_BYTES + (unsigned long long)n2 * (8 + 4 + 1 + 4 + 4 + 4 + 8);
         size_t b_sel = 0;
-        LN_CK(hipcub::DeviceSelect::Flagged(nullptr, b_sel, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr, (int*)nullptr,
-                                            (unsigned long long*)nullptr, (int)n2, s));
+        STEP_CK(hipcub::DeviceSelect::Flagged(nullptr, b_sel, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr, (int*)nullptr,
+                                              (unsigned long long*)nullptr, (int)n2, s));
         need += b_sel;
         if (cap >= (unsigned long long)INT_MAX || (cap + 3) / 4 >= (unsigned long long)INT_MAX || need > (unsigned long long)GRAAL_LINKS_MAX_BYTES) {
             snprintf(msg, sizeof msg, "graal_end_links_best: the candidate table needs %llu bytes (%llu records counted), over the budget of %llu "
-                     "bytes (GRAAL_LINKS_MAX_BYTES): use a larger min_frags", need, ctr[0], (unsigned long long)GRAAL_LINKS_MAX_BYTES);
+                     "bytes (GRAAL_LINKS_MAX_BYTES): use a larger min_frags", need, C.ctr[0], (unsigned long long)GRAAL_LINKS_MAX_BYTES);
             why = msg;
             break;
         }
-        if (cap > Lb->cap) {
-            ln_free_table(Lb);
-            LN_CK(hipMalloc(&Lb->keys, sizeof(unsigned long long) * cap));
-            LN_CK(hipMalloc(&Lb->tq, sizeof(long long) * cap));
-            LN_CK(hipMalloc(&Lb->tc, sizeof(long long) * cap));
-            LN_CK(hipMalloc(&Lb->tf, sizeof(int) * cap));
-            LN_CK(hipMalloc(&Lb->tsel, cap));
-            Lb->cap = cap;
-        }
+        STEP_CK(table_reserve(T, cap));
         if ((size_t)n2 > Lb->bcap) {
             ln_free_best(Lb);
-            LN_CK(hipMalloc(&Lb->bq, sizeof(long long) * (size_t)n2)); LN_CK(hipMalloc(&Lb->be, sizeof(int) * (size_t)n2));
-            LN_CK(hipMalloc(&Lb->bflag, (size_t)n2)); LN_CK(hipMalloc(&Lb->bsel, sizeof(int) * (size_t)n2));
-            LN_CK(hipMalloc(&Lb->mea, sizeof(int) * (size_t)n2)); LN_CK(hipMalloc(&Lb->meb, sizeof(int) * (size_t)n2));
-            LN_CK(hipMalloc(&Lb->mq, sizeof(long long) * (size_t)n2));
+            STEP_CK(hipMalloc(&Lb->bq, sizeof(long long) * (size_t)n2)); STEP_CK(hipMalloc(&Lb->be, sizeof(int) * (size_t)n2));
+            STEP_CK(hipMalloc(&Lb->bflag, (size_t)n2)); STEP_CK(hipMalloc(&Lb->bsel, sizeof(int) * (size_t)n2));
+            STEP_CK(hipMalloc(&Lb->mea, sizeof(int) * (size_t)n2)); STEP_CK(hipMalloc(&Lb->meb, sizeof(int) * (size_t)n2));
+            STEP_CK(hipMalloc(&Lb->mq, sizeof(long long) * (size_t)n2));
             Lb->bcap = (size_t)n2;
         }
-        if (b_sel > Lb->stmp_bytes) {
-            if (Lb->stmp) (void)hipFree(Lb->stmp);
-            Lb->stmp = nullptr; Lb->stmp_bytes = 0;
-            LN_CK(hipMalloc(&Lb->stmp, b_sel));
-            Lb->stmp_bytes = b_sel;
-        }
-        LN_CK(hipMemsetAsync(Lb->keys, 0xff, sizeof(unsigned long long) * cap, s));
-        LN_CK(hipMemsetAsync(Lb->tq, 0, sizeof(long long) * cap, s));
-        LN_CK(hipMemsetAsync(Lb->tc, 0, sizeof(long long) * cap, s));
-        LN_CK(hipMemsetAsync(Lb->tf, 0, sizeof(int) * cap, s));
+        STEP_CK(scratch_reserve(T, b_sel));
+        STEP_CK(table_clear(T, cap, s));
         // ---- insert pass, then the scores in place: mass, the quirk's passes, mirrors and status
         if (h->nnz > 0) {
-            k_ln_nnz<false><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, Lb->sub, h->stat_frag, Lb->ctg, h->nfpb, h->par, quirk, cap, Lb->keys,
-                                               Lb->tq, Lb->tc, Lb->tf, Lb->mir, Lb->mirbad, &Lb->ctr[0], Lb->err);
-            LN_CK(hipGetLastError());
+            k_ln_nnz<false><<<C.nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, h->nfpb, h->par, quirk, cap, T.keys,
+                                                 T.tq, T.tc, T.tf, R.mir, R.mirbad, &R.ctr[0], R.err);
+            STEP_CK(hipGetLastError());
         }
         const unsigned wblocks = (unsigned)((cap + 3) / 4);          // a wave per slot, 4 waves per block
-        k_lb_mass<<<wblocks, 256, 0, s>>>((long long)cap, Lb->keys, Lb->tf, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par, quirk, reach_bp(h), Lb->tq);
-        LN_CK(hipGetLastError());
+        k_lb_mass<<<wblocks, 256, 0, s>>>((long long)cap, T.keys, T.tf, R.lab, R.ctg, R.fr, h->nfpb, h->par, quirk, reach_bp(h), T.tq);
+        STEP_CK(hipGetLastError());
         if (mq) {
-            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, Lb->slot, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par, Lb->mir, Lb->mirbad);
-            LN_CK(hipGetLastError());
-            k_lb_quirk<<<wblocks, 256, 0, s>>>((long long)cap, Lb->keys, Lb->tf, Lb->lab, Lb->ctg, Lb->fr, h->nfpb, h->par, reach_bp(h), Lb->tq);
-            LN_CK(hipGetLastError());
+            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, R.mir, R.mirbad);
+            STEP_CK(hipGetLastError());
+            k_lb_quirk<<<wblocks, 256, 0, s>>>((long long)cap, T.keys, T.tf, R.lab, R.ctg, R.fr, h->nfpb, h->par, reach_bp(h), T.tq);
+            STEP_CK(hipGetLastError());
         }
         // ---- per end: the highest Q, then the lowest partner that reaches it, then the mutual links
         k_lb_init<<<blocks_for(n2, 256), 256, 0, s>>>(n2, Lb->bq, Lb->be);
-        k_lb_out<<<blocks_for((long long)cap, 256), 256, 0, s>>>((long long)cap, Lb->keys, Lb->tf, Lb->lab, Lb->mir, Lb->mirbad, mq, Lb->tq, Lb->bq);
-        k_lb_arg<<<blocks_for((long long)cap, 256), 256, 0, s>>>((long long)cap, Lb->keys, Lb->tf, Lb->tq, Lb->bq, Lb->be);
+        k_lb_out<<<blocks_for((long long)cap, 256), 256, 0, s>>>((long long)cap, T.keys, T.tf, R.lab, R.mir, R.mirbad, mq, T.tq, Lb->bq);
+        k_lb_arg<<<blocks_for((long long)cap, 256), 256, 0, s>>>((long long)cap, T.keys, T.tf, T.tq, Lb->bq, Lb->be);
         k_lb_norm<<<blocks_for(n2, 256), 256, 0, s>>>(n2, Lb->bq, Lb->be);
         k_lb_flag<<<blocks_for(n2, 256), 256, 0, s>>>(n2, Lb->bq, Lb->be, Lb->bflag);
-        LN_CK(hipGetLastError());
-        tb = Lb->stmp_bytes;
-        LN_CK(hipcub::DeviceSelect::Flagged(Lb->stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)Lb->bflag, Lb->bsel,
-                                            &Lb->ctr[1], (int)n2, s));
-        LN_CK(hipMemcpyAsync(ctr, Lb->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
-        LN_CK(hipMemcpyAsync(&err, Lb->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        LN_CK(hipStreamSynchronize(s));
-        if (err) break;
-        m = (long long)ctr[1];
+        STEP_CK(hipGetLastError());
+        size_t tb = T.stmp_bytes;
+        STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)Lb->bflag, Lb->bsel,
+                                              &R.ctr[1], (int)n2, s));
+        STEP_CK(hipMemcpyAsync(C.ctr, R.ctr, sizeof C.ctr, hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(&C.err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
+        if (C.err) break;
+        m = (long long)C.ctr[1];
         if (m > 0) {
             k_lb_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->bsel, Lb->bq, Lb->be, Lb->mea, Lb->meb, Lb->mq);
-            LN_CK(hipGetLastError());
+            STEP_CK(hipGetLastError());
         }
-        LN_CK(hipMemcpyAsync(best_end, Lb->be, sizeof(int) * (size_t)n2, hipMemcpyDeviceToHost, s));
-        LN_CK(hipMemcpyAsync(best_q, Lb->bq, sizeof(long long) * (size_t)n2, hipMemcpyDeviceToHost, s));
-        LN_CK(hipStreamSynchronize(s));
-#undef LN_CK
+        STEP_CK(hipMemcpyAsync(best_end, Lb->be, sizeof(int) * (size_t)n2, hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(best_q, Lb->bq, sizeof(long long) * (size_t)n2, hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
     } while (false);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    if (why) { h->err = why; return GRAAL_E_UNSUPPORTED; }
-    if (err) {
-        snprintf(msg, sizeof msg, "graal_end_links_best: corrupt layout (contig labels or positions out of range, flags %u)", err);
-        h->err = msg;
-        return GRAAL_E_STATE;
-    }
+    if (const int r = score_exit(h, "graal_end_links_best", rc, why, C.err)) return r;
     Lb->n_mutual = m;
     *n_mutual = m;
     return GRAAL_OK;

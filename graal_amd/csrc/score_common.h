@@ -1,0 +1,94 @@
+// score_common.h -- what the whole-layout scorers (junctions.h, links.h, insert.h, edit.h) share on the host side: the entry refusals and the
+// common exits, the step check of their do { ... } while (false) frames, the free-and-null of a pointer list, and the open-addressing candidate table.
+// Included by graal_hip.hip before junctions.h (it uses Ctx, fail and CK).
+#pragma once
+
+namespace {
+
+// One step of a scorer's `do { ... } while (false)` frame: a HIP error is recorded in h->err, `rc` becomes GRAAL_E_HIP and the frame is left
+// (the caller drains the stream and returns rc).  Needs `h` and an `int rc` in scope.
+#define STEP_CK(call) { const hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = hipGetErrorString(e_); rc = GRAAL_E_HIP; break; } }
+
+// Every pointer is freed AND nulled: with the owner's size field at 0 until its whole set is allocated, a failed hipMalloc leaves nothing
+// to free twice.
+void free_null(std::initializer_list<void**> ptrs)
+{
+    for (void** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
+}
+
+// What every scorer `fn` refuses before it touches the device; then the device is selected.
+int score_entry(Ctx* h, const char* fn)
+{
+    const char* why = nullptr;
+    int code = GRAAL_E_STATE;
+    if (!(h->have_sub && h->have_par && h->have_frags && h->have_contacts)) why = "upload sub-fragments, parameters, fragments and contacts first";
+    else if (h->has_rep) { why = "bins with several copies (graal_upload_repeats) are not supported"; code = GRAAL_E_UNSUPPORTED; }
+    else if (h->x_host || h->nccl_comm) why = "one rank only (an exchange or RCCL is attached)";
+    if (why) return fail(h, code, (std::string(fn) + ": " + why).c_str());
+    CK(hipSetDevice(h->device));
+    return GRAAL_OK;
+}
+
+// How a scorer's frame ends: a HIP error (the stream is drained first), a refusal `why`, the flags `err` of a corrupt layout, or GRAAL_OK.
+int score_exit(Ctx* h, const char* fn, int rc, const char* why, unsigned err)
+{
+    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+    if (why) return fail(h, GRAAL_E_UNSUPPORTED, why);
+    if (!err) return GRAAL_OK;
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: corrupt layout (contig labels or positions out of range, flags %u)", fn, err);
+    return fail(h, GRAAL_E_STATE, msg);
+}
+
+// The candidate table: open addressing keyed by a 64-bit key (ln_slot), per slot a Q sum, a contact count, flags and the selection byte of
+// DeviceSelect::Flagged; and the hipCUB scratch of the passes behind it.  Both grow to the largest size a call needed.
+struct CandTable {
+    unsigned long long* keys = nullptr; long long *tq = nullptr, *tc = nullptr; int* tf = nullptr; unsigned char* tsel = nullptr; size_t cap = 0;
+    void* stmp = nullptr; size_t stmp_bytes = 0;
+};
+constexpr unsigned long long TABLE_SLOT_BYTES = 8 + 8 + 8 + 4 + 1;   // key, q, contacts, flags, selection byte
+
+// slots for an upper bound of the distinct keys (load factor <= 2/3)
+inline unsigned long long table_cap(unsigned long long bound) { return bound + bound / 2 + 64; }
+
+void table_free(CandTable& T)
+{
+    free_null({(void**)&T.keys, (void**)&T.tq, (void**)&T.tc, (void**)&T.tf, (void**)&T.tsel, &T.stmp});
+    T.cap = 0; T.stmp_bytes = 0;
+}
+
+hipError_t table_reserve(CandTable& T, unsigned long long cap)
+{
+    if (cap <= T.cap) return hipSuccess;
+    free_null({(void**)&T.keys, (void**)&T.tq, (void**)&T.tc, (void**)&T.tf, (void**)&T.tsel});
+    T.cap = 0;
+    hipError_t e = hipMalloc(&T.keys, sizeof(unsigned long long) * cap);
+    if (e == hipSuccess) e = hipMalloc(&T.tq, sizeof(long long) * cap);
+    if (e == hipSuccess) e = hipMalloc(&T.tc, sizeof(long long) * cap);
+    if (e == hipSuccess) e = hipMalloc(&T.tf, sizeof(int) * cap);
+    if (e == hipSuccess) e = hipMalloc(&T.tsel, cap);
+    if (e == hipSuccess) T.cap = cap;
+    return e;
+}
+
+hipError_t scratch_reserve(CandTable& T, size_t bytes)
+{
+    if (bytes <= T.stmp_bytes) return hipSuccess;
+    free_null({&T.stmp});
+    T.stmp_bytes = 0;
+    const hipError_t e = hipMalloc(&T.stmp, bytes);
+    if (e == hipSuccess) T.stmp_bytes = bytes;
+    return e;
+}
+
+// (the table is used at size `cap`, whatever its allocation: the probe sequence depends on it)
+hipError_t table_clear(CandTable& T, unsigned long long cap, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(T.keys, 0xff, sizeof(unsigned long long) * cap, s);
+    if (e == hipSuccess) e = hipMemsetAsync(T.tq, 0, sizeof(long long) * cap, s);
+    if (e == hipSuccess) e = hipMemsetAsync(T.tc, 0, sizeof(long long) * cap, s);
+    if (e == hipSuccess) e = hipMemsetAsync(T.tf, 0, sizeof(int) * cap, s);
+    return e;
+}
+
+} // namespace

@@ -1,0 +1,103 @@
+"""The whole-layout scorers (graal_junction_scores, graal_end_links, graal_end_links_best, graal_insertions) keep their buffers on the
+handle between calls: the layout records are reallocated when (n, S) changes, the candidate table and the hipCUB scratch grow to the
+largest size a call needed and are then used at a smaller size than their allocation.  Every call on a handle that served other calls
+must return exactly what the same call returns as the FIRST call on a fresh handle with the same uploads.  Nothing here is compared with
+stored numbers: the other GPU tests tie the fresh-handle results to the numpy restatements.
+
+Problem A is window_cases.small_cut("w3") under ref_trans_accu: 160 bins at n_sub 3 with mixed RF counts (the mirror sums, both quirk
+kernels and the insertions' second table are live), pieces of 1-4 and 25-60 bins.  Problem B is small_cut("w1"): 240 fragments at n_sub
+1, the quirk off.  The uncut layouts have the same n and far fewer contigs: the tables shrink in use, not in allocation.  The last test
+loads problem B into a handle that served problem A (a second upload_subfrags / upload_contacts / upload_frags on a live handle is
+accepted), so the records are reallocated for another (n, S)."""
+import numpy as np
+import pytest
+
+from tests import window_cases
+from tests.test_scaffold_gpu import engine_for
+
+pytestmark = pytest.mark.gpu
+
+QUIRK = {"w3": True, "w1": False}
+CALLS = {
+    "links1": lambda e: e.end_links_q(1),
+    "links3": lambda e: e.end_links_q(3),
+    "best1": lambda e: e.end_links_best(1),
+    "best3": lambda e: e.end_links_best(3),
+    "ins1": lambda e: e.insertions_q(1),
+    "ins4": lambda e: e.insertions_q(4),
+    "junctions": lambda e: e.junction_scores_q(),
+}
+# links1 after links3: the table grows; links3 after it: the allocation is larger than the `cap` in use
+SEQUENCE = ("links3", "best1", "links1", "links3", "ins4", "ins1", "junctions", "best3")
+UNCUT = ("links1", "best1", "ins4")
+
+_PROBLEMS, _FRESH = {}, {}
+
+
+def problem(name):
+    if name not in _PROBLEMS:
+        _PROBLEMS[name] = (window_cases.small_cut(name), window_cases.small(name)["S_o_A_frags"])
+    return _PROBLEMS[name]
+
+
+def flat(result):
+    out = []
+    for x in result:
+        out.extend(flat(x) if isinstance(x, tuple) else [np.asarray(x)])
+    return out
+
+
+def fresh(name, layout, call):
+    """`call` as the first call on a fresh handle loaded with problem `name` in layout 'cut' or 'uncut' (computed once)."""
+    key = (name, layout, call)
+    if key not in _FRESH:
+        P, uncut = problem(name)
+        e = engine_for(P, state=uncut if layout == "uncut" else None, quirk=QUIRK[name])
+        try:
+            _FRESH[key] = flat(CALLS[call](e))
+        finally:
+            e.close()
+    return _FRESH[key]
+
+
+def check(e, name, layout, call, step):
+    got, want = flat(CALLS[call](e)), fresh(name, layout, call)
+    assert len(got) == len(want)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g.dtype == w.dtype and np.array_equal(g, w), (name, layout, call, step, i)
+
+
+@pytest.mark.parametrize("name", ["w3", "w1"])
+def test_reused_handle_equals_fresh_handle(name):
+    P, uncut = problem(name)
+    assert len(fresh(name, "cut", "links1")[0]) > len(fresh(name, "cut", "links3")[0]) > len(fresh(name, "uncut", "links1")[0]) > 0
+    assert len(fresh(name, "cut", "ins4")[0]) > len(fresh(name, "cut", "ins1")[0]) > 0
+    e = engine_for(P, quirk=QUIRK[name])
+    try:
+        for step, call in enumerate(SEQUENCE):
+            check(e, name, "cut", call, step)
+        e.upload_frags(uncut)
+        for step, call in enumerate(UNCUT):
+            check(e, name, "uncut", call, len(SEQUENCE) + step)
+    finally:
+        e.close()
+
+
+def test_another_problem_on_a_used_handle():
+    A, _ = problem("w3")
+    B, _ = problem("w1")
+    assert len(A["S_o_A_frags"]["pos"]) != len(B["S_o_A_frags"]["pos"])
+    e = engine_for(A, quirk=True)
+    try:
+        for step, call in enumerate(("links1", "best1", "ins4", "junctions")):
+            check(e, "w3", "cut", call, step)
+        e.upload_subfrags(B["np_sub_frags_id"], B["np_sub_frags_len_bp"], B["np_sub_frags_accu"], B["init_n_sub_frags"],
+                          B["mean_squared_frags_per_bin"])
+        e.upload_contacts(B["coo_row"], B["coo_col"], B["coo_val"])
+        e.set_params(B["param_simu"])
+        e.upload_frags(B["S_o_A_frags"])
+        e.set_mode(ref_trans_accu=False)
+        for step, call in enumerate(("links1", "best1", "ins4", "junctions", "links3")):
+            check(e, "w1", "cut", call, 4 + step)
+    finally:
+        e.close()
