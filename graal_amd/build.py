@@ -32,7 +32,7 @@ def build_hip(force=False, verbose=False):
     srcs = [os.path.join(CSRC, "graal_hip.hip"), os.path.join(CSRC, "frag_ops.h"), os.path.join(CSRC, "host_step.h"),
             os.path.join(CSRC, "model_math.h"), os.path.join(CSRC, "strict_sets.h"), os.path.join(CSRC, "strict2.h"),
             os.path.join(CSRC, "host_fit.h"), os.path.join(CSRC, "simulate.h"), os.path.join(CSRC, "junctions.h"), os.path.join(CSRC, "links.h"), os.path.join(CSRC, "edit.h"),
-            os.path.join(CSRC, "insert.h"), os.path.join(CSRC, "score_common.h"), os.path.join(CSRC, "scan_rows.h"),
+            os.path.join(CSRC, "insert.h"), os.path.join(CSRC, "flips.h"), os.path.join(CSRC, "score_common.h"), os.path.join(CSRC, "scan_rows.h"),
             os.path.join(ROOT, "include", "graal_hip.h")]
     if force or _newer(HIP_LIB, srcs):
         cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",

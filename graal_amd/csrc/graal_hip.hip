@@ -4490,6 +4490,8 @@ struct EdBuf;                  // edit.h: graal_edit_layout's buffers
 void ed_free(EdBuf* b);
 struct InBuf;                  // insert.h: graal_insertions' buffers and results
 void in_free(InBuf* b);
+struct FlBuf;                  // flips.h: graal_block_flips' buffers
+void fl_free(FlBuf* b);
 
 struct Ctx {
     int device = 0;
@@ -4698,6 +4700,7 @@ struct Ctx {
     LnBuf* ln = nullptr;          // graal_end_links' buffers and its last result (links.h; allocated by its first call)
     EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
     InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
+    FlBuf* fl = nullptr;          // graal_block_flips' buffers (flips.h; allocated by its first call)
 };
 
 #define CK(call)                                                                                     \
@@ -5494,6 +5497,7 @@ void graal_destroy(graal_ctx* h)
         ln_free(h->ln); h->ln = nullptr;
         ed_free(h->ed); h->ed = nullptr;
         in_free(h->ins); h->ins = nullptr;
+        fl_free(h->fl); h->fl = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
         if (h->h_stats) (void)hipHostFree(h->h_stats);
@@ -7034,4 +7038,5 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "junctions.h"
 #include "links.h"
 #include "insert.h"
+#include "flips.h"
 #include "edit.h"

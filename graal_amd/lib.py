@@ -52,13 +52,14 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_set_scan_path", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
-           "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch",
+           "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
 STEP_DONE, STEP_PAUSED, STEP_FALLBACK, STEP_SELECT = 0, 1, 2, 3
 JUNCTION_VALID, JUNCTION_END, JUNCTION_CIRCULAR, JUNCTION_NONFINITE = 0, 1, 2, 3   # graal_junction_scores' status bytes
 LINK_VALID, LINK_NONFINITE = 0, 1   # graal_end_links' status bytes
 INSERT_VALID, INSERT_NONFINITE = 0, 1   # graal_insertions' status bytes
+FLIP_VALID, FLIP_WHOLE, FLIP_CIRCULAR, FLIP_NONFINITE = 0, 1, 2, 3   # graal_block_flips' status bytes
 # graal_edit_layout's status words
 EDIT_OK, EDIT_BAD_CUT, EDIT_DUP_CUT, EDIT_BAD_END, EDIT_CIRCULAR, EDIT_END_TWICE, EDIT_SAME_CONTIG, EDIT_CYCLE = range(8)
 STEPS_ROW = 10   # GRAAL_STEPS_ROW: doubles per step in graal_steps' rows
@@ -140,6 +141,7 @@ def load():
         L.graal_insertions.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i64p]
         L.graal_insertions_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, ctypes.POINTER(ctypes.c_uint8), _i64p, _i64p,
                                              ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
+        L.graal_block_flips.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_scan_path.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_finisher.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -244,6 +246,7 @@ class Engine:
     def set_params(self, param8):
         p = _c(np.asarray(param8, dtype=np.float32).reshape(8), np.float32)
         self._ck(self._L.graal_set_params(self._h, p.ctypes.data_as(_f32p)), "graal_set_params")
+        self.param = p.copy()   # a host copy of the parameters in force, nothing else changes (graal_amd.flips derives its window from d_max)
 
     def upload_subfrags(self, sub_id, sub_len_kb, sub_accu, n_sub_total, n_frags_per_bins):
         sid = _c(np.asarray(sub_id).reshape(-1, 4), np.int32)
@@ -338,6 +341,8 @@ class Engine:
                                             q.ctypes.data_as(_i64p))
         if rc != 0:
             self._ck(rc, "graal_eval_full_params")
+        if p is not None:
+            self.param = p.copy()
         return q, self._st_buf.copy(), int(self._max_id.value)
 
     def eval_full(self):
@@ -467,6 +472,31 @@ class Engine:
                                                 q.ctypes.data_as(_i64p), c.ctypes.data_as(_i64p), st.ctypes.data_as(u8), m),
                  "graal_insertions_fetch")
         return p, f, r, q, c, st
+
+    def block_flips(self, first, last):
+        """graal_block_flips: for the disjoint blocks (first[k] .. last[k], two fragments of one contig in position order) the score
+        F = logL(layout with the block reversed in place) - logL(layout) in the exact arithmetic, as (F float64, contacts int64, status
+        uint8) in the caller's order; F is NaN unless status is FLIP_VALID (FLIP_WHOLE: the block is its whole contig, FLIP_CIRCULAR: it
+        lies in a ring, FLIP_NONFINITE).  contacts = the summed count between the block and the rest of its contig inside the window of
+        the flipped layout.  Same preconditions and refusals as junction_scores; blocks that overlap, span two contigs, run backwards or
+        name no fragment raise GraalError.  Leaves the step state alone."""
+        q, c, st = self.block_flips_q(first, last)
+        return np.where(st == FLIP_VALID, q.astype(np.float64) / Q_SCALE, np.nan), c, st
+
+    def block_flips_q(self, first, last):
+        """The same with the score as int64 Q: (q, contacts, status)."""
+        first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        last = np.ascontiguousarray(last, dtype=np.int32).reshape(-1)
+        if len(first) != len(last):
+            raise ValueError("first and last must have the same length")
+        m = len(first)
+        q = np.zeros(m, dtype=np.int64)
+        c = np.zeros(m, dtype=np.int64)
+        st = np.zeros(m, dtype=np.uint8)
+        self._ck(self._L.graal_block_flips(self._h, m, first.ctypes.data_as(_i32p), last.ctypes.data_as(_i32p), q.ctypes.data_as(_i64p),
+                                           c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+                 "graal_block_flips")
+        return q, c, st
 
     def edit_layout(self, cuts=(), joins=()):
         """graal_edit_layout: cut the junction after every fragment of `cuts`, then apply `joins` (pairs of ends, end = 2 * fragment +

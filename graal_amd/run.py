@@ -60,6 +60,14 @@ def main(argv=None):
                                                           "(graal_amd.scaffold with insertions); writes insert.tsv")
     ap.add_argument("--insert-max-frags", type=int, default=3, help="with --insert / --insertions: the largest piece, in fragments (default 3)")
     ap.add_argument("--insert-min-score", type=float, default=0.0, help="with --insert: only insertions scoring above this (default 0)")
+    ap.add_argument("--flip", action="store_true", help="after --scaffold, --polish and --insert, before the outputs: flip the blocks of up to "
+                                                        "--flip-max-frags fragments, and the runs between weak junctions, that the data "
+                                                        "prefer the other way round, round by round (graal_amd.flips); writes flip.tsv")
+    ap.add_argument("--flip-max-frags", type=int, default=8, help="with --flip / --flips: the longest run of fragments tried (default 8)")
+    ap.add_argument("--flip-min-score", type=float, default=0.0, help="with --flip: only flips scoring above this (default 0)")
+    ap.add_argument("--flips", action="store_true", help="write flips.tsv into the output folder: every run of up to --flip-max-frags "
+                                                         "fragments of the final layout with the log-likelihood its reversal in place "
+                                                         "would add, the contacts behind it and a status (graal_amd.flips)")
     ap.add_argument("--insertions", action="store_true", help="write insertions.tsv into the output folder: every insertion of a piece of "
                                                               "up to --insert-max-frags fragments into a junction of the final layout that the "
                                                               "contacts support, with the log-likelihood it would add (graal_amd.insert)")
@@ -128,6 +136,10 @@ def main(argv=None):
         from . import scaffold
         scaffold.write_scaffold_tsv(os.path.join(out, "insert.tsv"),
                                     scaffold.scaffold(smp, insert_max_frags=args.insert_max_frags, insert_min_score=args.insert_min_score))
+    if args.flip:
+        from . import flips
+        flips.write_flip_rounds_tsv(os.path.join(out, "flip.tsv"),
+                                    flips.flip_rounds(smp, max_frags=args.flip_max_frags, min_score=args.flip_min_score))
     lev = P.get_level(args.level)
     if args.fasta:
         P.load_reference_sequence(args.fasta)
@@ -144,6 +156,11 @@ def main(argv=None):
         table, _ = insert.fitting_insertion_table(smp, args.insert_max_frags)   # (a smaller piece size when over the device budget)
         if table is not None:
             insert.write_insertions_tsv(os.path.join(out, "insertions.tsv"), table)
+    if args.flips:
+        from . import flips, scaffold
+        eng = scaffold._engine(smp)
+        soa = eng.download_frags()
+        flips.write_flips_tsv(os.path.join(out, "flips.tsv"), flips.score_table(eng, soa, flips.tilings(soa, None, args.flip_max_frags)))
     n_steps = len(trace.likelihood)
     print("%d bins (%d fragments, %d sub-fragments), %d MCMC steps in %.1f s (%.0f us/step): %d contigs, logL %.6e, "
           "distance to the initial genome %.4f; traces in %s" % (inp["n_frags"], inp["n_new_frags"], inp["init_n_sub_frags"], n_steps,

@@ -1,7 +1,8 @@
 """Greedy scaffolding and polishing of a layout on the GPU: join mutual-best contig ends, cut the junctions the data reject, round by round.
 
     scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None,
-             insert_max_frags=None, insert_min_score=0.0)                             -- the rounds; returns their record
+             insert_max_frags=None, insert_min_score=0.0,
+             flip_max_frags=None, flip_min_score=0.0)                                 -- the rounds; returns their record
     break_cycles(ea, eb, score, contig_of_end)                                            -- drop the weakest join of every cycle
     write_scaffold_tsv(path, record)                                                      -- one tab-separated row per round
 
@@ -20,6 +21,11 @@ graal_edit_layout call), then the full evaluation; its row counts those cuts and
 large is over the device budget, the step uses the largest smaller piece size that fits (down to 1, else it is skipped).
 Scaffolding stops when a round has no join (and no insertion) left.  Joins are scored one at a time and combined joins are not additive: a round that lowers
 logL is undone (the layout from before the round is uploaded again) and scaffolding stops there.
+With flip_max_frags set, once a round finds no join, cut or insertion left (not when `rounds` ran out first, and not behind a round that
+was undone), graal_amd.flips.flip_rounds runs over the result with its own default number of rounds (fragment runs of up to
+flip_max_frags fragments scoring above flip_min_score; its unit tilings are delimited by the weak junctions and by the joins made since
+the layout scaffold() started from: a piece joined the wrong way round is one unit).  Its rounds follow in the record, numbered on, their
+cuts and joins those of the flips' edits.
 """
 import numpy as np
 
@@ -90,14 +96,17 @@ def plan_joins(mutual, min_score, contig_of_end):
     return a[keep], b[keep], score[keep]
 
 
-def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None, insert_max_frags=None, insert_min_score=0.0):
+def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None, insert_max_frags=None, insert_min_score=0.0,
+             flip_max_frags=None, flip_min_score=0.0):
     """Scaffold (and with cut_below, polish; with insert_max_frags, insert pieces) the engine's current layout; see the module's
     docstring.  Returns the record: a list of dicts with the keys COLUMNS, round 0 the layout as it came (kept 0 marks a round that was
     undone)."""
     obj = sampler_or_engine
     e = _engine(obj)
+    start = e.download_frags() if flip_max_frags is not None else None
     logl, nc = _evaluate(e)
     record = [{"round": 0, "cuts": 0, "joins": 0, "contigs": nc, "logL": logl, "kept": 1}]
+    settled = False                # a round found no join, cut or insertion left
     for r in range(1, int(rounds) + 1):
         before = e.download_frags()
         cuts = np.zeros(0, dtype=np.int64)
@@ -119,6 +128,7 @@ def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below
             if len(icuts):
                 _edit(obj, e, icuts, ijoins)
         if len(a) == 0 and len(cuts) == 0 and len(icuts) == 0:
+            settled = True
             break
         if len(a):
             _edit(obj, e, [], np.stack([a, b], axis=1))
@@ -134,7 +144,15 @@ def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below
         record.append(row)
         logl = new_logl
         if len(a) == 0 and len(icuts) == 0:
+            settled = True             # (only cuts: no join and no insertion was on offer behind them)
             break
+    if flip_max_frags is not None and settled:
+        from . import flips
+        last = record[-1]["round"]
+        for row in flips.flip_rounds(obj, max_frags=flip_max_frags, min_score=flip_min_score,
+                                     extra_marks=lambda now: flips.joined_marks(start, now))[1:]:
+            record.append({"round": last + row["round"], "cuts": row["cuts"], "joins": row["joins"], "contigs": row["contigs"],
+                           "logL": row["logL"], "kept": row["kept"]})
     return record
 
 

@@ -404,6 +404,41 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out);
 int graal_insertions_fetch(graal_ctx* h, int32_t* piece, int32_t* after, uint8_t* rev, int64_t* q, int64_t* contacts, uint8_t* status,
                            int64_t cap);
 
+/* Block flips: the likelihood each in-place reversal of a block of fragments would add, for a set of disjoint blocks in one pass
+ * (graal_amd/csrc/flips.h).  Block k holds the fragments of ONE contig at positions pos[first[k]] .. pos[last[k]] (pos[first[k]] <=
+ * pos[last[k]]; a one-fragment block has first == last); the blocks of a call are pairwise disjoint and come in any order.  Anything else
+ * -- an index out of range, two contigs, reversed order, overlap -- returns GRAAL_E_ARG, the message names the first offending block, and
+ * nothing is written.  n_blocks == 0 returns GRAAL_OK.
+ * The FLIPPED layout of block k is the current layout with the block reversed in place: the block keeps its bp interval [s0, e1), a
+ * fragment of it with start_bp s and len_bp l gets start_bp s0 + e1 - (s + l), its ori changes sign, positions are mirrored inside the
+ * block and prev / next follow; everything else keeps every field; the float32 centres through centre_kb from the integer starts in the
+ * new orientation.  It is the layout graal_edit_layout writes when the block is cut out and joined back the other way round, up to the
+ * reversal of the whole chain its canonical order may apply (see graal_insertions).
+ *   F(k) = logL(flipped layout) - logL(current layout)
+ * in the exact arithmetic under the current mode flags, with graal_junction_scores' / graal_end_links' roundings:
+ *   - pairs inside the block and pairs with no fragment in the block count as unchanged;
+ *   - every sub-fragment pair of (block) x (rest of the same contig) moves from its cis price to its cis price in the flipped layout: a
+ *     contact's term ob * (ln ex_new - ln ex_old) is rounded to Q once per contact, a fragment pair's mass -(sum of ex_new - sum of
+ *     ex_old), summed in float64 over its sub-fragment pairs with the block's fragment outer, once per fragment pair; a pair beyond the
+ *     window (reach_bp, as for the junction scores) both before and after is v_inter * norm both times and is skipped;
+ *   - under GRAAL_MODE_REF_TRANS_ACCU with bins of mixed RF counts, the changed trans prices of the block's mixed bins against the
+ *     higher-id bins of OTHER contigs (graal_end_links' mirror term, summed per block); cis prices do not use the indexing.
+ * int64 sums: bit-identical from call to call, for any grid and for any order of the blocks in the call.  A block is scored alone: two
+ * blocks of one call with contacts between them each carry their own term, priced with only that block flipped.
+ * Outputs, n_blocks entries each in the caller's order: q[k] = F in Q; contacts[k] = the summed count of the contacts between the block
+ * and the rest of its contig whose centre distance in the flipped layout is below d_max (the evidence behind the score); status[k] one of
+ * the codes below (q = 0 unless VALID).  A one-fragment block of a one-sub-fragment bin is VALID with q = 0: its centre does not move.
+ * The contact list may come in any order.  Needs sub-fragments, parameters, fragments and contacts.  Does not relabel and leaves the step
+ * state alone (ranked layout, carried total, a pending commit's correction, the proposal tables).  Device memory is O(fragments +
+ * sub-fragments + n_blocks).  GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats); GRAAL_E_STATE with an exchange or RCCL
+ * attached (one rank only). */
+#define GRAAL_FLIP_VALID 0
+#define GRAAL_FLIP_WHOLE 1      /* the block is its whole contig: nothing moves, q = 0 */
+#define GRAAL_FLIP_CIRCULAR 2   /* the block lies in a circular contig: no score, q = 0 */
+#define GRAAL_FLIP_NONFINITE 3  /* a term was not finite, q = 0 */
+int graal_block_flips(graal_ctx* h, int32_t n_blocks, const int32_t* first, const int32_t* last, int64_t* q, int64_t* contacts,
+                      uint8_t* status);
+
 /* ---- the sampler's per-step HOST logic behind the boundary (graal_amd/csrc/host_step.h) --------------------------------
  * What cuda_lib_gl.sampler.step_max_likelihood does on the host between its launches: return_neighbours
  * (cuda_lib_gl.py:2295-2331: RandomState.choice(xk, n, p=pk, replace=False), expansion to the copies of repeated bins,
