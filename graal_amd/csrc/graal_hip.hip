@@ -1438,7 +1438,7 @@ struct NbTables {        // everything the finishing kernel needs about one neig
     // candidates of that class
     unsigned char crep[N_PAIRS][N_OPS];
     unsigned short cmask[N_PAIRS][N_OPS];
-    int set_m;                         // strict: fragments of contig(fA) u contig(fB) that are left to k_strict (0: priced by k_tm, or fB == fA)
+    int set_m;                         // strict: fragments of contig(fA) u contig(fB) that are left to k_strict_flat / k_strict2 (0: priced by k_tm, or fB == fA)
     UEnd endA, endB;                   // the contigs of fA and fB as the union set's builder wants them (k_gprep: one round trip instead of three)
     Task task[MAX_TASKS];
 };
@@ -2217,7 +2217,7 @@ struct TmArgs { // first-needed pointers by value (see ScanArgs)
     int n_done;
     unsigned long long done_target[N_DONE];
     int wait_ticks;                // how long that block waits for k_scan (100 MHz ticks)
-    int strict;                    // GRAAL_MODE_STRICT: reference arithmetic (same_inputs classes; small sets priced here, the rest by k_strict)
+    int strict;                    // GRAAL_MODE_STRICT: reference arithmetic (same_inputs classes; small sets priced here, the rest by k_strict_flat / k_strict2)
     int quirk;                     // GRAAL_MODE_REF_TRANS_ACCU
     const long long* nc;           // number of contigs of the ranked layout, on the device (max_id < 0: read it here)
     // graal_step's deferred flow: the kernel is launched right behind the relabel WITHOUT an event in between (a cross-stream
@@ -2439,7 +2439,7 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
     __syncthreads();
     if (s_fin == 0) return;
     if (s_fin == 2) {
-        // some neighbour's work is left to k_fin / k_strict whatever the scan finds: say so AT ONCE -- the host's launches then
+        // some neighbour's work is left to k_fin / k_strict_flat / k_strict2 whatever the scan finds: say so AT ONCE -- the host's launches then
         // queue up behind the scan on its stream while it is still running, instead of starting their trip when it has ended
         // (contigs of 20-100 bins, the middle of a run: ~10 us of a 130 us step)
         if (t == 0) { ta.sync[0] = 0; __threadfence_system(); ta.host_res[0] = seq | NEED_FIN | NEED_GEOM; __threadfence_system(); }
@@ -3434,7 +3434,7 @@ struct StrictArgs {
     int quirk;
     int reach_bp;
     unsigned long long list_cap;
-    int seg;                      // fragments y per work unit (a power of two <= 64: the y tile of a unit is cut into 64 / seg segments)
+    int pad;                      // (read by nobody: without these bytes the arguments behind the struct move and k_strict2 spills 4 more SGPRs)
 };
 
 // correction of the layout independent all-trans mass T_all for the reference's trans-branch RF-count indexing: pairs of
@@ -3662,7 +3662,7 @@ __global__ __launch_bounds__(256) void k_strict_dense(FinArgs fa, StrictArgs sa,
     hand_out(fa.acc, counters, fa.sync, K, d_q_out, host_res, seq);
 }
 
-// ------------------------------------------------------------------ reference arithmetic, windowed (k_strict_cull + k_strict)
+// ------------------------------------------------------------------ reference arithmetic, windowed (k_strict_flat; k_gprep + k_strict2)
 // The same sums as k_strict_dense -- every term it adds that is not exactly zero -- without its O(m^2) evaluations:
 //   * a fragment pair that is beyond the window (or in two contigs) both before and under a candidate has the trans value both
 //     times, slot by slot: the difference is exactly 0 and the pair is skipped (unless the reference's trans-branch RF-count
@@ -3670,11 +3670,10 @@ __global__ __launch_bounds__(256) void k_strict_dense(FinArgs fa, StrictArgs sa,
 //   * the 13 candidates of a neighbour fall into classes of equal contact-model inputs per piece pair (same_inputs, built by
 //     k_tm): a class is priced once, under its first candidate, and its value added to every candidate of the class; the class
 //     of the current layout's own inputs is never priced.
-// Work unit = (neighbour, tile of 64 fragments x, tile of 64 fragments y) of the affected set, tiles never straddling the two
-// contigs.  k_strict_cull lists the units that can hold a pair inside the window under some layout (interval arithmetic on
-// the tiles' and pieces' bp extents: one thread per candidate unit); k_strict takes the listed units round robin, one wave
-// each: lane = fragment x, the y tile staged in LDS, every (x, y) rounded to Q once per class.  Then the queued contacts (the
-// scan queued every contact with both ends in a neighbour's set): lane = contact, one evaluation per class.
+// Small affected sets go to k_strict_flat (below): one lane per (fragment pair, class slot), straight from k_tm's tables.  The
+// others go to the tiled kernels over the step's union set, k_gprep + k_strict2 (strict2.h, included behind k_strict_flat), which
+// build their classes per pair of global pieces and list the tile pairs within the window's reach themselves.  Both price the
+// queued contacts too (the scan queued every contact with both ends in a neighbour's set), one evaluation per class.
 struct SetGeo { int m, lenA, lenB, baseA, baseB, tilesA, nt, lbpA, lbpB, cA, cB, pad; };   // one neighbour's affected set
 
 // (the layout's part: needs nothing of k_tm's tables; `live` = the set is left to the strict kernels, NbTables::set_m > 0)
@@ -3694,381 +3693,18 @@ __device__ __forceinline__ SetGeo set_geo_of(int fA, int fB, bool live, const Ge
     g.pad = 0;
     return g;
 }
-__device__ __forceinline__ SetGeo set_geo(const NbTables& T, const Geo* __restrict__ geo, const Link* __restrict__ link,
-                                          const int* __restrict__ cbase, int fA)
-{
-    return set_geo_of(fA, T.fB, T.set_m > 0, geo, link, cbase);
-}
 
-// old bp interval [lo, hi) of piece p of the neighbour and its contig (0 = contig(fA), 1 = contig(fB)); lo >= hi: empty
-__device__ __forceinline__ void piece_extent(const PieceKey& key, const Geo& gA, const Geo& gB, const SetGeo& sg, int p, int& lo, int& hi, int& side)
-{
-    lo = 0; hi = 0; side = 0;
-    if (key.cA != key.cB) {
-        const Geo& g = p <= 3 ? gA : gB;
-        side = p <= 3 ? 0 : 1;
-        const int lbp = p <= 3 ? sg.lbpA : sg.lbpB, w = p <= 3 ? p : p - 3;
-        if (w == 1) { lo = 0; hi = g.start_bp; } else if (w == 2) { lo = g.start_bp; hi = g.start_bp + g.len_bp; } else { lo = g.start_bp + g.len_bp; hi = lbp; }
-        return;
-    }
-    const bool a_first = key.a < key.b;
-    const Geo& L = a_first ? gA : gB;
-    const Geo& H = a_first ? gB : gA;
-    if (p == 1) { lo = 0; hi = L.start_bp; }
-    else if (p == 2) { lo = L.start_bp; hi = L.start_bp + L.len_bp; }
-    else if (p == 3) { lo = L.start_bp + L.len_bp; hi = H.start_bp; }
-    else if (p == 4) { lo = H.start_bp; hi = H.start_bp + H.len_bp; }
-    else if (p == 5) { lo = H.start_bp + H.len_bp; hi = sg.lbpA; }
-}
-
-
-__global__ __launch_bounds__(256) void k_strict_cull(const NbTables* __restrict__ tabs, const Geo* __restrict__ geo, const Link* __restrict__ link,
-                                                      const int* __restrict__ cbase, const int* __restrict__ perm, int fA, int K, int rank, int world,
-                                                      int reach_bp, int no_window, int seg_fixed /* 0: chosen here */, int seg_min,
-                                                      unsigned long long target_units, unsigned long long* __restrict__ list,
-                                                      unsigned long long* __restrict__ list_n, unsigned long long cap,
-                                                      unsigned long long* __restrict__ counters)
-{
-    __shared__ SetGeo s_sg[MAXK];
-    __shared__ int s_plo[MAXK][NP], s_phi[MAXK][NP], s_pside[MAXK][NP];
-    __shared__ Xf s_xf[MAXK][N_OPS][NP];
-    __shared__ unsigned char s_crep[MAXK][N_PAIRS][N_OPS];
-    __shared__ int s_rbase[MAXK + 1];
-    __shared__ int s_row[4];      // the row's x tile: lo, hi (old bp), side
-    const int t = threadIdx.x;
-    STAMP(29, blockIdx.x == 0 && t == 0);
-    if (t < K) {
-        const SetGeo sg = set_geo(tabs[t], geo, link, cbase, fA);
-        s_sg[t] = sg;
-        const Geo gA = geo[fA], gB = geo[tabs[t].fB];
-        for (int p = 0; p < NP; p++) { int lo, hi, side; piece_extent(tabs[t].key, gA, gB, sg, p, lo, hi, side); s_plo[t][p] = p ? lo : 0; s_phi[t][p] = p ? hi : 0; s_pside[t][p] = side; }
-    }
-    for (int i = t; i < K * N_OPS * NP; i += blockDim.x) { const int k = i / (N_OPS * NP), r = i - k * (N_OPS * NP); s_xf[k][r / NP][r % NP] = tabs[k].xf[r / NP][r % NP]; }
-    for (int i = t; i < K * N_PAIRS * N_OPS; i += blockDim.x) { const int k = i / (N_PAIRS * N_OPS), r = i - k * (N_PAIRS * N_OPS); s_crep[k][r / N_OPS][r % N_OPS] = tabs[k].crep[r / N_OPS][r % N_OPS]; }
-    __syncthreads();
-    if (t == 0) { s_rbase[0] = 0; for (int k = 0; k < K; k++) s_rbase[k + 1] = s_rbase[k] + s_sg[k].nt; }
-    __syncthreads();
-    const int n_rows = s_rbase[K];
-    // fragments y per unit (a power of two): the y tiles are cut so that the step has ~target_units units -- from the sets of THIS step
-    // (every block finds the same value).  (The host used to choose it from the longest contig of the layout: a step between two
-    // contigs of 400 bins in a layout that also holds one of 2,000 got units of 32 fragments y x ~5 classes, a few hundred units
-    // for 2,048 waves.)
-    int seg = seg_fixed;
-    if (seg <= 0) {
-        unsigned long long est = 0;
-        for (int k = 0; k < K; k++) { const unsigned long long nt = (unsigned long long)s_sg[k].nt; est += nt * (nt + 1ull) / 2ull; }
-        seg = 64;
-        while (seg > seg_min && est * (unsigned long long)(64 / seg) < target_units) seg >>= 1;
-    }
-    const unsigned long long lg_seg = (unsigned long long)(31 - __clz(seg));
-    // old bp extent of tile tt of neighbour k
-    auto tile_extent = [&](int k, int tt, int& lo, int& hi, int& side) {
-        const SetGeo& sg = s_sg[k];
-        side = tt < sg.tilesA ? 0 : 1;
-        const int t0 = side ? tt - sg.tilesA : tt, len = side ? sg.lenB : sg.lenA, base = side ? sg.baseB : sg.baseA;
-        const int first = t0 * 64, next = first + 64;
-        lo = geo[perm[base + first]].start_bp;
-        hi = next >= len ? (side ? sg.lbpB : sg.lbpA) : geo[perm[base + next]].start_bp;
-    };
-    for (int row = blockIdx.x; row < n_rows; row += gridDim.x) {
-        int k = 0;
-        for (int j = 1; j < K; j++) k += row >= s_rbase[j] ? 1 : 0;
-        const int ti = row - s_rbase[k];
-        const SetGeo sg = s_sg[k];
-        __syncthreads();
-        if (t == 0) { int lo, hi, side; tile_extent(k, ti, lo, hi, side); s_row[0] = lo; s_row[1] = hi; s_row[2] = side; }
-        __syncthreads();
-        const int xlo = s_row[0], xhi = s_row[1], xside = s_row[2];
-        for (int tj0 = ti; tj0 < sg.nt; tj0 += blockDim.x) {
-            const int tj = tj0 + t;
-            bool alive = false;
-            if (tj < sg.nt && ((ti + tj + k) % world) == rank) {
-                int ylo, yhi, yside;
-                tile_extent(k, tj, ylo, yhi, yside);
-                for (int p = 1; p < NP && !alive; p++) {
-                    if (s_pside[k][p] != xside) continue;
-                    const int xs = max(xlo, s_plo[k][p]), xe = min(xhi, s_phi[k][p]);
-                    if (xs >= xe) continue;
-                    for (int q = 1; q < NP && !alive; q++) {
-                        if (s_pside[k][q] != yside) continue;
-                        const int ys = max(ylo, s_plo[k][q]), ye = min(yhi, s_phi[k][q]);
-                        if (ys >= ye) continue;
-                        const int pr = pair_index(p, q);
-                        // the current layout
-                        const bool near_old = xside == yside && max(ys - xe, xs - ye) <= reach_bp;
-                        for (int op = 0; op < N_OPS && !alive; op++) {
-                            if (s_crep[k][pr][op] != op) continue;   // a class is priced under its first candidate only
-                            if (no_window || near_old) { alive = true; break; }
-                            const Xf a = s_xf[k][op][p], b = s_xf[k][op][q];
-                            if (a.label != b.label) continue;
-                            const int xs2 = a.sigma > 0 ? xs + a.off : a.off - xe, xe2 = a.sigma > 0 ? xe + a.off : a.off - xs;
-                            const int ys2 = b.sigma > 0 ? ys + b.off : b.off - ye, ye2 = b.sigma > 0 ? ye + b.off : b.off - ys;
-                            if (max(ys2 - xe2, xs2 - ye2) <= reach_bp) alive = true;
-                        }
-                    }
-                }
-            }
-            // an alive tile pair is listed as ceil(count of its y tile / seg) units: (k, ti, tj, segment)
-            int ne = 0;
-            if (alive) {
-                const int side = tj < sg.tilesA ? 0 : 1, t0 = side ? tj - sg.tilesA : tj;
-                const int cnt_y = min(64, (side ? sg.lenB : sg.lenA) - t0 * 64);
-                ne = (cnt_y + seg - 1) / seg;
-            }
-            if (__ballot(alive)) {
-                const int lane = t & 63;
-                int incl = ne;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
-                const int total = __shfl(incl, 63, 64);
-                unsigned long long base = 0;
-                if (lane == 0) base = atomicAdd(list_n, (unsigned long long)total);
-                base = __shfl(base, 0, 64);
-                for (int e = 0; e < ne; e++) {
-                    const unsigned long long at = base + (unsigned long long)(incl - ne + e);
-                    if (at < cap) list[at] = ((unsigned long long)k << 56) | (lg_seg << 52) | ((unsigned long long)ti << 32) | ((unsigned long long)tj << 8) | (unsigned long long)e;
-                    else atomicOr(&counters[6], 2ull);   // (cannot happen: the host sizes the list for the longest contig)
-                }
-            }
-        }
-    }
-}
-
-struct STileW { Geo g; int lbp, piece, frag, nonuni; Stat st; };   // one staged fragment y, 64 bytes
 constexpr int STRICT_ACC_COPIES = 8;   // copies of the block's K*13 sums (lane & 7 picks one): LDS atomics of a wave spread over them
 
-// dynamic LDS of k_strict for K neighbours: the transforms, the classes and their candidate masks
-__host__ __device__ constexpr size_t strict_dyn_lds(int K) { return (size_t)K * (N_OPS * NP * sizeof(Xf) + N_PAIRS * N_OPS * sizeof(unsigned short) + ((N_PAIRS * N_OPS + 3) & ~3)); }
-
-template <bool MULTI>
-__global__ __launch_bounds__(256) void k_strict(FinArgs fa, StrictArgs sa, int fA, int K, const unsigned long long* __restrict__ list,
-                                                 unsigned long long* __restrict__ list_n, long long* __restrict__ d_q_out,
-                                                 volatile long long* host_res, long long seq)
-{
-    const NbTables* __restrict__ tabs = fa.tabs;
-    const Geo* __restrict__ geo = fa.geo;
-    const Stat* __restrict__ stat = fa.stat;
-    unsigned long long* __restrict__ counters = fa.counters;
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    const int wave = blockIdx.x * 4 + wib, n_waves = gridDim.x * 4;
-    __shared__ STileW s_tile[4][64];
-    __shared__ long long s_accb[STRICT_ACC_COPIES][MAXK * N_OPS];
-    __shared__ SetGeo s_sg[MAXK];
-    extern __shared__ long long s_dyn_strict[];
-    Xf* const s_xf = reinterpret_cast<Xf*>(s_dyn_strict);                                          // [K][N_OPS][NP]
-    unsigned short* const s_cmask = reinterpret_cast<unsigned short*>(s_xf + K * N_OPS * NP);     // [K][N_PAIRS][N_OPS]
-    unsigned char* const s_crep = reinterpret_cast<unsigned char*>(s_cmask + K * N_PAIRS * N_OPS); // [K][N_PAIRS][N_OPS]
-#define XF_(k_, op_, p_) s_xf[((k_) * N_OPS + (op_)) * NP + (p_)]
-#define CREP_(k_, pr_, op_) s_crep[((k_) * N_PAIRS + (pr_)) * N_OPS + (op_)]
-#define CMASK_(k_, pr_, op_) s_cmask[((k_) * N_PAIRS + (pr_)) * N_OPS + (op_)]
-    STAMP(16, blockIdx.x == 0 && threadIdx.x == 0);
-    for (int i = threadIdx.x; i < STRICT_ACC_COPIES * MAXK * N_OPS; i += 256u) (&s_accb[0][0])[i] = 0;
-    // (the tables are complete: the launch is ordered behind k_tm by an event)
-    for (int i = threadIdx.x; i < K * N_OPS * NP; i += 256u) { const int k = i / (N_OPS * NP), r = i - k * (N_OPS * NP); s_xf[i] = tabs[k].xf[r / NP][r % NP]; }
-    for (int i = threadIdx.x; i < K * N_PAIRS * N_OPS; i += 256u) {
-        const int k = i / (N_PAIRS * N_OPS), r = i - k * (N_PAIRS * N_OPS);
-        s_crep[i] = tabs[k].crep[r / N_OPS][r % N_OPS]; s_cmask[i] = tabs[k].cmask[r / N_OPS][r % N_OPS];
-    }
-    __shared__ PieceKey s_qkeys[MAXK];   // what expands the queue's entries (q_fetch + q_codes)
-    __shared__ unsigned s_qlive;
-    if (threadIdx.x == 255) s_qlive = 0;
-    __syncthreads();
-    if ((int)threadIdx.x < K) {
-        s_sg[threadIdx.x] = set_geo(tabs[threadIdx.x], geo, sa.link, sa.cbase, fA);
-        s_qkeys[threadIdx.x] = tabs[threadIdx.x].key;
-        if (tabs[threadIdx.x].fB != fA) atomicOr(&s_qlive, 1u << threadIdx.x);
-    }
-    __syncthreads();
-    const unsigned long long nq_total = counters[2];          // written by k_scan, an earlier kernel on the stream
-    const unsigned long long n_units = min(*list_n, sa.list_cap); // written by k_strict_cull, the previous kernel on the stream
-    const float nfpb = sa.nfpb;
-    const Par par = sa.par;
-    const bool quirk = sa.quirk != 0;
-    const int reach_bp = sa.reach_bp;
-    long long* const my_acc = s_accb[lane & (STRICT_ACC_COPIES - 1)];
-    auto add_ops = [&](int k, unsigned ops, long long v) {
-        while (ops) { const int b = __ffs((int)ops) - 1; ops &= ops - 1; atomicAdd((unsigned long long*)&my_acc[k * N_OPS + b], (unsigned long long)v); }
-    };
-    STAMP(17, blockIdx.x == 0 && threadIdx.x == 0);
-    // ---- (1) the listed units
-    STileW* tile = s_tile[wib];
-    for (unsigned long long u = (unsigned long long)wave; u < n_units; u += (unsigned long long)n_waves) {
-        const unsigned long long ent = list[u];
-        const int seg = 1 << (int)((ent >> 52) & 7ull);   // (fragments y of this unit: chosen per step by k_strict_cull)
-        const int k = (int)(ent >> 56), ti = (int)((ent >> 32) & 0xfffffull), tj = (int)((ent >> 8) & 0xffffffull), j0 = (int)(ent & 0xffull) * seg;
-        const SetGeo sg = s_sg[k];
-        const PieceKey key = tabs[k].key;
-        auto frag_at = [&](int tt, int l, bool& ok) {
-            const int side = tt < sg.tilesA ? 0 : 1, t0 = side ? tt - sg.tilesA : tt, pos = t0 * 64 + l;
-            ok = l < 64 && pos < (side ? sg.lenB : sg.lenA);
-            return ok ? sa.perm[(side ? sg.baseB : sg.baseA) + pos] : 0;
-        };
-        bool has_x;
-        const int fx = frag_at(ti, lane, has_x);
-        Geo gx = {0, 0, 0, 0};
-        Stat sx = {0.0f, 0.0f, 0.0f, 0, 0, 0, 0, 0};
-        int px = 0, lbpx = 0;
-        if (has_x) {
-            gx = geo[fx]; sx = stat[fx];
-            px = piece_of(key, gx.id_c, geo_pos(gx.flags));
-            lbpx = ((gx.flags >> 1) & 1) ? (gx.id_c == sg.cA ? sg.lbpA : sg.lbpB) : 0;
-        }
-        const bool nonuni_x = !stat_uniform(sx);
-        int cnt = 0;
-        {   // the unit's segment of the y tile: fragments j0 .. j0 + seg of it
-            bool has_y;
-            const int fy = frag_at(tj, j0 + lane, has_y);
-            has_y = has_y && lane < seg;
-            if (has_y) {
-                STileW y; y.frag = fy; y.g = geo[fy]; y.st = stat[fy];
-                y.piece = piece_of(key, y.g.id_c, geo_pos(y.g.flags));
-                y.lbp = ((y.g.flags >> 1) & 1) ? (y.g.id_c == sg.cA ? sg.lbpA : sg.lbpB) : 0;
-                y.nonuni = stat_uniform(y.st) ? 0 : 1;
-                tile[lane] = y;
-            }
-            cnt = __popcll(__ballot(has_y));
-        }
-        WAVE_LDS_SYNC();
-        const End X0 = end_old(gx, lbpx);
-        long long accq[N_OPS];
-#pragma unroll
-        for (int op = 0; op < N_OPS; op++) accq[op] = 0;
-        unsigned bad = 0;
-        int cur_pr = -1;
-        auto flush = [&]() {
-            if (cur_pr < 0) return;
-#pragma unroll
-            for (int op = 0; op < N_OPS; op++)
-                if (accq[op] != 0) { add_ops(k, CMASK_(k, cur_pr, op), accq[op]); accq[op] = 0; }
-        };
-        const bool live_x = has_x && sx.n > 0;
-        for (int j = 0; j < cnt; j++) {
-            if (!live_x || (ti == tj && j0 + j <= lane)) continue;  // every unordered pair once; never a bin with itself
-            const STileW& y = tile[j];
-            const Stat sy = y.st;
-            if (sy.n == 0) continue;                                  // (a copy of a repeated bin: priced by k_rep_delta)
-            const int py = y.piece, pr = pair_index(px, py);
-            if (pr != cur_pr) { flush(); cur_pr = pr; }
-            const End Y0 = end_old(y.g, y.lbp);
-            const bool near_old = X0.label == Y0.label && gap_bp(X0, gx.len_bp, Y0, y.g.len_bp) <= reach_bp;
-            const bool always = quirk && (nonuni_x || y.nonuni != 0);
-            bool have_old = false;
-            float exo[3][3];
-#pragma unroll
-            for (int a = 0; a < 3; a++)
-#pragma unroll
-                for (int b = 0; b < 3; b++) exo[a][b] = 0.0f;
-            for (int op = 0; op < N_OPS; op++) {
-                if (CREP_(k, pr, op) != op) continue;
-                const End X = end_xf(gx, XF_(k, op, px)), Y = end_xf(y.g, XF_(k, op, py));
-                const bool near_new = X.label == Y.label && gap_bp(X, gx.len_bp, Y, y.g.len_bp) <= reach_bp;
-                if (!near_old && !near_new && !always) continue;      // the trans value both times, slot by slot: exactly zero
-                if (!have_old) {
-                    have_old = true;
-                    if (MULTI) {
-#pragma unroll
-                        for (int a = 0; a < 3; a++)
-#pragma unroll
-                            for (int b = 0; b < 3; b++)
-                                if (a < sx.n && b < sy.n) exo[a][b] = ex_pair_ref(X0, sx, a, fx, Y0, sy, b, y.frag, nfpb, par, quirk);
-                    } else exo[0][0] = ex_pair_ref(X0, sx, 0, fx, Y0, sy, 0, y.frag, nfpb, par, quirk);
-                }
-                double acc = 0.0;
-                if (MULTI) {
-#pragma unroll
-                    for (int a = 0; a < 3; a++)
-#pragma unroll
-                        for (int b = 0; b < 3; b++)
-                            if (a < sx.n && b < sy.n) acc += (double)exo[a][b] - (double)ex_pair_ref(X, sx, a, fx, Y, sy, b, y.frag, nfpb, par, quirk);
-                } else acc += (double)exo[0][0] - (double)ex_pair_ref(X, sx, 0, fx, Y, sy, 0, y.frag, nfpb, par, quirk);
-                const long long q1 = to_q(acc);
-                if (q1 == Q_BAD) coarse_add_ops(fa.acc, counters + NF_OFF, k, (unsigned)CMASK_(k, pr, op), acc);
-                else {
-                    // (`op` is wave-uniform -- the loop counter -- so this is a scalar jump to one 64-bit add, not 13 selects)
-                    switch (op) {
-                    case 0: accq[0] += q1; break; case 1: accq[1] += q1; break; case 2: accq[2] += q1; break; case 3: accq[3] += q1; break;
-                    case 4: accq[4] += q1; break; case 5: accq[5] += q1; break; case 6: accq[6] += q1; break; case 7: accq[7] += q1; break;
-                    case 8: accq[8] += q1; break; case 9: accq[9] += q1; break; case 10: accq[10] += q1; break; case 11: accq[11] += q1; break;
-                    default: accq[12] += q1; break;
-                    }
-                }
-            }
-        }
-        flush();
-        for (int o = 32; o > 0; o >>= 1) bad |= __shfl_down(bad, o, 64);
-        if (lane == 0 && bad) nf_flag_ops(counters + NF_OFF, k, bad & 0xffffu);
-        WAVE_LDS_SYNC();   // (the next unit stages its tile over this one)
-    }
-    STAMP_MAX(18, lane == 0);
-    // ---- (2) the queued contacts: lane = contact, one evaluation per class
-    QSrc qs;
-    qs.queue = fa.queue; qs.geo2 = reinterpret_cast<const int2*>(geo); qs.cnt = fa.cnt; qs.keys = s_qkeys; qs.live = s_qlive; qs.K = K;
-    qs.seq = (unsigned)seq; qs.concurrent = 0; qs.multi = fa.multi;
-    for (unsigned long long b0 = (unsigned long long)(n_waves - 1 - wave) * 64ull; b0 < nq_total; b0 += (unsigned long long)n_waves * 64ull) {
-        const unsigned long long e = b0 + (unsigned long long)lane;
-        if (e >= nq_total) continue;
-        QEntry qe = q_fetch(qs, e, counters + 6);
-        if (qe.fx < 0) continue;
-        const int fx = qe.fx, fy = qe.fy, slx = qe.slots & 3, sly = (qe.slots >> 2) & 3;
-        const Geo gx = geo[fx], gy = geo[fy];
-        const Stat sx = stat[fx], sy = stat[fy];
-        q_codes(qs, qe, gx, gy, qs.cnt[qe.idx]);
-        if (qe.rel == 0) continue;
-        const End X0 = end_old(gx, ((gx.flags >> 1) & 1) ? sa.lcontbp[fx] : 0), Y0 = end_old(gy, ((gy.flags >> 1) & 1) ? sa.lcontbp[fy] : 0);
-        const float ex_old = ex_pair_ref(X0, sx, slx, fx, Y0, sy, sly, fy, nfpb, par, quirk);
-        const double ln_old = mm_ln(ex_old), ob = (double)__int_as_float(qe.cnt);
-        unsigned rel = qe.rel;
-        while (rel) {
-            const int k = (__ffs((int)rel) - 1) / CODE_BITS;
-            rel &= rel - 1;
-            const int p = (qe.ci >> (CODE_BITS * k)) & 7, q = (qe.cj >> (CODE_BITS * k)) & 7;
-            const int pr = pair_index(p, q);
-            for (int op = 0; op < N_OPS; op++) {
-                if (CREP_(k, pr, op) != op) continue;
-                const End X = end_xf(gx, XF_(k, op, p)), Y = end_xf(gy, XF_(k, op, q));
-                const float ex_new = ex_pair_ref(X, sx, slx, fx, Y, sy, sly, fy, nfpb, par, quirk);
-                if (ex_new == ex_old) continue;
-                const long long qv = to_q(ob * (mm_ln(ex_new) - ln_old));
-                if (qv == Q_BAD) nf_flag_ops(counters + NF_OFF, k, CMASK_(k, pr, op));
-                else if (qv != 0) add_ops(k, CMASK_(k, pr, op), qv);
-            }
-        }
-    }
-    STAMP_MAX(19, lane == 0);
-    __syncthreads();
-    for (int i = threadIdx.x; i < K * N_OPS; i += 256u) {
-        long long v = 0;
-#pragma unroll
-        for (int c = 0; c < STRICT_ACC_COPIES; c++) v += s_accb[c][i];
-        if (v != 0) atomicAdd((unsigned long long*)&fa.acc[i], (unsigned long long)v);
-    }
-    if (threadIdx.x == 255 && blockIdx.x == 0) atomicAdd(&counters[1], n_units);
-    __shared__ int s_last;
-    ATOMICS_DONE();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long ticket = atomicAdd(&counters[5], 1ull);
-        s_last = (ticket == (unsigned long long)gridDim.x - 1ull);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    if (threadIdx.x == 0) *list_n = 0;   // (every block has read it: the list is empty again for the next step)
-    hand_out(fa.acc, counters, fa.sync, K, d_q_out, host_res, seq);
-    STAMP(20, threadIdx.x == 0);
-#undef XF_
-#undef CREP_
-#undef CMASK_
-}
-
-// k_strict_flat: the same sums as k_strict_cull + k_strict for SMALL affected sets -- the middle of a run, contigs of 20-100 bins:
-// a step there has a handful of tile-pair units and a few hundred queued contacts, and k_strict spends 40 us on each part with
-// one wave walking 4 fragments y x ~9 classes, or 5 neighbours x ~9 classes of one contact, one evaluation after the other
-// (tools/stamps_c4.py).  Here every (fragment pair, class) and every (contact, neighbour, class) is a LANE: two evaluations deep,
-// whatever the set's size; no unit list, no culling kernel, no event -- the kernel sits behind the scan on its stream and waits for
-// k_tm's tables by itself (its grid cannot fill the chip: k_tm always finds room).  Sets with more than FLAT_CAP_PAIRS pairs
-// are left to the tiled kernels: the step's last block then publishes NEED_FIN and touches nothing.
-// Same per-pair / per-contact terms, rounded to Q the same way: bit-identical to k_strict (tests/test_strict_windowed_gpu.py).
+// k_strict_flat: these sums for SMALL affected sets -- the middle of a run, contigs of 20-100 bins: a step there has a handful of
+// tile pairs and a few hundred queued contacts, too few for a tiled kernel (one wave walking a unit's fragments and classes, or
+// a contact's neighbours and classes, one evaluation after the other: tools/stamps_c4.py).  Here every (fragment pair, class) and
+// every (contact, neighbour, class) is a LANE: two evaluations deep, whatever the set's size; no unit list, no culling blocks, no
+// event -- the kernel sits behind the scan on its stream and waits for k_tm's tables by itself (its grid cannot fill the chip:
+// k_tm always finds room).  Sets with more than FLAT_CAP_PAIRS pairs are left to the tiled kernels: the step's last block then
+// publishes NEED_FIN and touches nothing.
+// Same per-pair / per-contact terms, rounded to Q the same way: bit-identical to k_strict_dense and to k_strict2
+// (tests/test_strict_windowed_gpu.py).
 constexpr long long FLAT_CAP_PAIRS = 40000;     // x 13 class slots = 520 k lanes = ~11 rounds of the grid
 constexpr int FLAT_BLOCKS = 192;                // < 256 CUs: blocks that wait for k_tm can never keep it off the chip
 template <bool MULTI>
@@ -4087,7 +3723,7 @@ __global__ __launch_bounds__(256) void k_strict_flat(FinArgs fa, StrictArgs sa, 
     __shared__ unsigned s_qlive;
     __shared__ int s_ok, s_last;
     // (the transforms and classes are read where they are needed, from k_tm's tables in L2: a lane wants two transforms and one
-    // class entry -- staging all K x 13 x 6 of them in LDS first, as k_strict does for its long loops, was 6 us of a 30 us kernel)
+    // class entry -- staging all K x 13 x 6 of them in LDS first was 6 us of a 30 us kernel)
 #define XF_(k_, op_, p_) tabs[k_].xf[op_][p_]
 #define CREP_(k_, pr_, op_) tabs[k_].crep[pr_][op_]
 #define CMASK_(k_, pr_, op_) tabs[k_].cmask[pr_][op_]
@@ -4552,7 +4188,7 @@ struct Ctx {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> ring; // pairs of events around k_scan, one pair per call (graal_scan_times)
     long long ring_calls = 0;
-    std::vector<hipEvent_t> sring; // pairs of events around the tiled reference-arithmetic kernel of a call (k_strict2 / k_strict; graal_strict_times)
+    std::vector<hipEvent_t> sring; // pairs of events around the tiled reference-arithmetic kernel of a call (k_strict2; graal_strict_times)
     long long sring_calls = 0;
     bool ev_this_call = false;     // the evaluation being launched carries the event pairs
     bool timing_valid = false;
@@ -4638,8 +4274,8 @@ struct Ctx {
     unsigned long long* d_done = nullptr;    // the N_DONE completion counters of k_scan, DONE_STRIDE words apart
     unsigned long long* d_wq = nullptr;      // k_fin's work-queue counters (2 x N_WQ, WQ_STRIDE words apart), zero at rest
     int mode = 0;                 // GRAAL_MODE_* flags (graal_set_mode)
-    unsigned long long* d_slist = nullptr;   // k_strict's unit list (k_strict_cull fills it), slist_cap entries
-    unsigned long long* d_slist_n = nullptr; // its length, a word of d_scalars (zero at rest: k_strict's last block clears it)
+    unsigned long long* d_slist = nullptr;   // k_strict2's unit list (k_gprep fills it), slist_cap entries
+    unsigned long long* d_slist_n = nullptr; // its length, a word of d_scalars (zero at rest: k_strict2's last block clears it)
     unsigned long long slist_cap = 0;
     unsigned long long slist_floor = 0;      // entries the list holds at least: raised when a step's list overflowed (eval_sync grows it and repeats the step)
     unsigned long long slist_worst = 0;      // the last launch's worst case (every tile pair of the union set listed)
@@ -4822,7 +4458,7 @@ int refresh(Ctx* h)
 
 constexpr int MAX_SCAN_BLOCKS = 4096;
 constexpr int FULL_BAD = 27; // d_scalars[FULL_BAD]: a term of the last full evaluation was not finite / out of range
-constexpr int SLIST_N = 28;  // d_scalars[SLIST_N]: length of k_strict's unit list (zero at rest)
+constexpr int SLIST_N = 28;  // d_scalars[SLIST_N]: length of k_strict2's unit list (zero at rest)
 constexpr int RELABEL_FLAG = 30; // d_scalars[RELABEL_FLAG]: sequence number of the last relabel k_scan has announced as complete (k_tm spins on it)
 constexpr int SCAN_LDS_MAX = 48 * 1024; // affected bitmap of k_scan: 1 bit per contact-list id up to 393,216 ids, folded beyond (launch_scan)
 
@@ -5039,29 +4675,33 @@ int launch_fin(Ctx* h, int K, int rank, int world, long long* d_q_out, bool publ
     return GRAAL_OK;
 }
 
-// GRAAL_STRICT_DENSE=1: the O(m^2) validation kernel (k_strict_dense) instead of k_strict_cull + k_strict (tests compare the two)
+// GRAAL_STRICT_DENSE=1: the O(m^2) validation kernel (k_strict_dense) instead of k_strict_flat / k_gprep + k_strict2 (tests compare them)
 bool strict_dense_cfg()
 {
     static const bool v = getenv("GRAAL_STRICT_DENSE") != nullptr && atoi(getenv("GRAAL_STRICT_DENSE")) != 0;
     return v;
 }
 
-// reference arithmetic: what k_tm left (sets larger than STRICT_INLINE_M, the queued contacts when there are many), hand-out
-int launch_strict(Ctx* h, int fA, int K, int rank, int world, long long* d_q_out, bool publish, hipStream_t st)
+// what the reference-arithmetic kernels are handed alike: the step's buffers (none of k_fin's options) and the layout's constants
+void strict_args(Ctx* h, FinArgs& fa, StrictArgs& sx)
 {
-    // k_strict_cull needs k_tm's tables and nothing of the scan: it goes out on the AUXILIARY stream, behind k_tm, and runs under
-    // the scan; k_strict waits for both (the event on the auxiliary stream, the scan in front of it on its own)
-    FinArgs fa;
     fa.tm_done = h->tm_done; fa.step_hdr = h->step_hdr; fa.counters = (unsigned long long*)(h->d_scalars + 10); fa.queue = h->queue;
     fa.cnt = h->cnt; fa.multi = h->single_sub ? 0 : 1;
     fa.tabs = h->tabs; fa.geo = h->geo; fa.stat = h->stat_frag; fa.acc = h->d_acc; fa.sync = h->d_sync;
     fa.ln_tab = nullptr; fa.lut_n = 0; fa.skip = 0; fa.seg = 0; fa.norm_u = -1.0f; fa.upw = 4; fa.wq = nullptr;
-    StrictArgs sx;
     sx.perm = h->perm; sx.cbase = h->cbase; sx.lcontbp = h->soa[h->cur].p[F_LCONTBP]; sx.link = h->link; sx.nfpb = h->nfpb; sx.par = h->par;
     sx.quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     sx.reach_bp = reach_bp(h);
     sx.list_cap = 0;
-    sx.seg = 64;
+    sx.pad = 0;
+}
+
+// reference arithmetic: what k_tm left (sets larger than STRICT_INLINE_M, the queued contacts when there are many), hand-out
+int launch_strict(Ctx* h, int fA, int K, int rank, int world, long long* d_q_out, bool publish, hipStream_t st)
+{
+    FinArgs fa;
+    StrictArgs sx;
+    strict_args(h, fa, sx);
     if (strict_dense_cfg()) {
         CK(hipEventRecord(h->ev_tm, h->aux));      // (k_tm is on the auxiliary stream, done or not: the event completes behind it)
         CK(hipStreamWaitEvent(st, h->ev_tm, 0));   // the tables are complete before the kernel starts: nobody spins for them
@@ -5069,182 +4709,124 @@ int launch_strict(Ctx* h, int fA, int K, int rank, int world, long long* d_q_out
         CK(hipGetLastError());
         return GRAAL_OK;
     }
-    static const bool v1 = getenv("GRAAL_STRICT_V1") != nullptr && atoi(getenv("GRAAL_STRICT_V1")) != 0;   // (A/B: the per-neighbour kernels of round 3)
-    if (!v1) {
-        // the union set's kernels (strict2.h): k_gprep (classes per pair of global pieces + the unit list) on the auxiliary stream behind
-        // k_tm, under the scan; k_strict2 waits for both
-        if (!h->d_uset) {
-            CK(hipMalloc(&h->d_uset, sizeof(USet)));
-            CK(hipMalloc(&h->d_cls, sizeof(GClass) * (size_t)US_MAXPAIRS * US_NCAND));
-            CK(hipMalloc(&h->d_cls_n, sizeof(int) * US_MAXPAIRS + 1024));   // (+ the units' draw counter, k_gprep's ticket and completion word: a line of its own each)
-            CK(hipMemset(h->d_cls_n, 0, sizeof(int) * US_MAXPAIRS + 1024));
-            CK(hipDeviceSynchronize());
-        }
-        const int lc = std::max(std::max(h->max_lcont, h->lcont_bound), 1);
-        static const int blocks_env = getenv("GRAAL_STRICT_BLOCKS") ? atoi(getenv("GRAAL_STRICT_BLOCKS")) : 0;
-        // (the GRID by the longest contig as last seen -- one commit stale: a performance choice; everything that must HOLD the step is sized by
-        // the bound `lc`, twice that + 2.  By the bound, contigs of 130-256 bins went to the 1,024-block grid behind an event instead of the
-        // 512-block one that follows k_gprep through its word: GRAAL_S2_GRID_BY_BOUND=1 for A/B)
-        static const bool grid_by_bound = getenv("GRAAL_S2_GRID_BY_BOUND") != nullptr;
-        const int lg = grid_by_bound ? lc : std::max(h->max_lcont, 1);
-        const int blocks = blocks_env > 0 ? blocks_env : (lg <= 64 ? 32 : (lg <= 256 ? 512 : 1024));
-        // fragments per tile: 64 (one per lane); with several sub-fragments per bin 32 -- the halves of a wave hold the same 32 fragments and
-        // take two fragments of the segment at a time (k_strict2): a unit is a 32 x 4 block instead of a 64 x 2 strip, which wastes fewer lanes
-        // on pieces of a few dozen bins and at the window's edge (GRAAL_S2_TILE=64: the strips, for A/B)
-        static const int tile_env = getenv("GRAAL_S2_TILE") ? atoi(getenv("GRAAL_S2_TILE")) : 0;
-        const int TILE = tile_env == 64 ? 64 : (tile_env == 32 ? 32 : (h->single_sub ? 64 : 32));
-        // tiles of the union: at most K + 1 contigs, at most every fragment; + one partial tile per global piece
-        const unsigned long long nt = std::min<unsigned long long>((unsigned long long)(K + 1) * (unsigned long long)((lc + TILE - 1) / TILE),
-                                                                   (unsigned long long)((h->n + TILE - 1) / TILE + K + 1)) + (unsigned long long)US_MAXP;
-        if (nt >= 65536ull) return fail(h, GRAAL_E_STATE, "reference arithmetic: more than 65,535 tiles in a step's union set");
-        // the unit list's entries: 4 fragments of the segment side (one sub-fragment per bin; k_strict2 merges up to 4 of them) or 1 (several:
-        // up to 2); GRAAL_STRICT_SEG fixes the entry size (entries of one fragment at one sub-fragment per bin: the list's traffic cost the C4
-        // stand-in 20 % of its run), GRAAL_STRICT_REP the waves that may share one unit's classes (1, 2, 4, 8)
-        static const int seg_env = getenv("GRAAL_STRICT_SEG") ? atoi(getenv("GRAAL_STRICT_SEG")) : 0;
-        const int seg_max = h->single_sub ? 16 : (TILE == 32 ? 4 : 2);   // (k_strict2's segment: SEG, seg_cap)
-        // (one sub-fragment per bin: entries of 4 fragments -- of 16, a whole unit, once a contig may exceed 512 bins: a unit of 64 x 4 pairs is
-        // 13 us of set-up for ~1 us per class, and the kernel merges neighbouring entries only from 49,000 of them on; C4 stand-in, 4 cycles:
-        // 214 us per step against 224, the late stage unchanged)
-        // (tiles of 32: entries of TWO fragments, one per half of the wave -- FOUR once the longest contig may hold more than 512 bins (the bound,
-        // one commit stale: twice the longest + 2): a step there has a few thousand units, more than half the grid's waves, so no two waves share
-        // one; with half as many, twice as long, every unit is shared by two waves and none idles.  C3 stand-in (contigs of 350 bins): 142 us
-        // per step against 157; C2 stand-in (contigs of 150-220): 108 against 99)
-        const int seg_unit = ((seg_env == 1 || seg_env == 2 || seg_env == 4 || seg_env == 8 || seg_env == 16) && seg_env <= seg_max) ? seg_env
-                                                                                                 : (h->single_sub ? (lc > 512 ? 16 : 4) : (TILE == 32 ? (lc > 512 ? 4 : 2) : 1));
-        static const int rep_env = getenv("GRAAL_STRICT_REP") ? atoi(getenv("GRAAL_STRICT_REP")) : 8;
-        const int rep_max = rep_env >= 16 ? 16 : (rep_env >= 8 ? 8 : (rep_env >= 4 ? 4 : (rep_env >= 2 ? 2 : 1)));
-        // units the grid wants before k_strict2 merges neighbouring entries into longer units (per wave: 6 at one sub-fragment per bin; with
-        // several, a unit's fragment pairs are nine evaluations each -- GRAAL_S2_TARGET_X4: the figure in quarters, for A/B)
-        static const int target_env = getenv("GRAAL_S2_TARGET_X4") ? atoi(getenv("GRAAL_S2_TARGET_X4")) : 0;
-        const unsigned long long target_x4 = target_env > 0 ? (unsigned long long)target_env : (h->single_sub ? 24ull : 24ull);
-        const unsigned long long target = std::max<unsigned long long>(1ull, target_x4 * 4ull * (unsigned long long)blocks / 4ull);
-        const unsigned long long pairs_max = nt * (nt + 1ull) / 2ull;
-        // The list's worst case -- EVERY tile pair of the union listed -- is quadratic in the union's size (2e9 entries for 1e6 fragments in a few
-        // contigs), while the interval cull lists the pairs within reach of each other under some candidate: orders of magnitude fewer.
-        // It is sized ONCE per layout size, for the largest union n fragments and MAXK neighbours can form -- not for this step's longest
-        // contig: growing it with the contigs meant a hipFree / hipMalloc behind two stream synchronizes in the middle of a run, again and
-        // again while an assembly's contigs grow.  One rank: SLIST_SOFT_CAP entries at most to begin with; if a step's list overflows,
-        // k_gprep says so (counters[6] bit 1), the step ends as failed, eval_sync raises the floor and repeats it.  Several ranks: the worst
-        // case (a repeated step on ONE rank would leave the ranks out of step).
-        const unsigned long long nt_n = (unsigned long long)((h->n + TILE - 1) / TILE + MAXK + 1) + (unsigned long long)US_MAXP;
-        const unsigned long long worst = (nt_n * (nt_n + 1ull) / 2ull) * (unsigned long long)(TILE / seg_unit) + 64ull;
-        (void)pairs_max;
-        const unsigned long long SLIST_SOFT_CAP = h->slist_soft_cap;   // (GRAAL_SLIST_SOFT_CAP, read when the handle is created)
-        h->slist_worst = worst;
-        const unsigned long long need = (world == 1 && publish) ? std::min(worst, std::max(SLIST_SOFT_CAP, h->slist_floor)) : worst;
-        if (need > h->slist_cap) {
-            CK(hipDeviceSynchronize());   // (rare: the first tiled step of a layout size, or a list that has just overflowed)
-            if (h->d_slist) CK(hipFree(h->d_slist));
-            h->d_slist = nullptr;
-            h->slist_cap = 0;
-            const unsigned long long cap = std::max<unsigned long long>(need, 64ull);
-            CK(hipMalloc(&h->d_slist, cap * sizeof(unsigned long long)));
-            h->slist_cap = cap;
-        }
-        h->d_slist_n = (unsigned long long*)(h->d_scalars + SLIST_N);
-        sx.list_cap = h->slist_cap;
-        sx.seg = 0;
-        fa.norm_u = h->uniform_accu > 0 ? (float)(h->uniform_accu * h->uniform_accu) / h->nfpb : -1.0f;
-        static const int s2_skip = getenv("GRAAL_S2_SKIP") ? atoi(getenv("GRAAL_S2_SKIP")) : 0;   // (diagnostics: wrong sums.  1 = no units, 2 = no queued contacts)
-        fa.skip = s2_skip;
-        const int no_window = (sx.quirk && h->n_ubins > 0) ? 1 : 0;
-        S2Args s2;
-        s2.uset = h->d_uset; s2.cls = h->d_cls; s2.cls_n = h->d_cls_n; s2.seg_unit = seg_unit; s2.rep_max = rep_max; s2.target = target;
-        static const int draw_env = getenv("GRAAL_STRICT_DRAW") ? atoi(getenv("GRAAL_STRICT_DRAW")) : 8;
-        s2.draw_min = draw_env > 0 ? draw_env : 8;
-        s2.next = reinterpret_cast<unsigned long long*>(h->d_cls_n + US_MAXPAIRS + (US_MAXPAIRS & 1));
-        // k_strict2 behind k_gprep WITHOUT an event (S2Args::gp): a kernel behind an event of another stream starts ~11 us after the event
-        // completes (tools/stamps_s2.py, C2 stand-in: k_gprep done 23 us, k_strict2 started 37; without any ordering -- GRAAL_DEBUG runs -- 26, as
-        // soon as the host has submitted it).  k_gprep's results go out as device-scope stores, its last block stores the step's number, and
-        // k_strict2's blocks wait for that word.  Only a grid that leaves room for k_gprep's blocks on every CU may wait for them in the kernel
-        // (512 blocks: two per CU; cf. fin_blocks_no_wait), only one rank (a repeated step must not leave the ranks out of step), only while
-        // the engine's streams are known to run side by side (spin_ok).  (768 blocks -- three per CU, still room -- with the wait instead of 1,024
-        // behind the event: C3 / C4 stand-ins 214-221 / 238-243 us per step against 200-203 / 222-225.)
-        // (round 5 tried the word with the 1,024-block grids too: the wait ran out in every run -- C3 and C4 stand-ins -- and the engine went back to
-        // events, as the argument above predicts)
-        const bool gwait = h->gwait_env && publish && world == 1 && h->spin_ok && blocks <= 512;
-        s2.gp = gwait ? s2.next + 32 : nullptr;   // (ticket: 256 bytes behind the draw counter; the completion word 256 bytes behind the ticket: GP_DONE)
-        s2.gp_seq = (unsigned long long)h->seq;
-        s2.gp_wait_ticks = h->gp_wait_ticks;
-        s2.gp_acquire = h->gp_acquire;
-        if (gwait) { h->spin_used = true; h->rc_gwait += 1; } else h->rc_gevent += 1;
-        const int cull_blocks = (int)std::min<unsigned long long>(1024ull, std::max<unsigned long long>(1ull, nt));
-        // Where k_gprep goes.  A long scan (millions of contacts): on the auxiliary stream behind k_tm, under the scan; k_strict2 waits for both
-        // through an event.  A short one (a map of a few thousand bins: the scan is over before k_tm's tables are): on the MAIN stream, behind
-        // the scan and an event of k_tm that has long completed when the stream gets there -- k_strict2 then follows k_gprep in stream order,
-        // without the ~10 us a kernel waits behind an event that completes right in front of it (tools/stamps_s2.py, C2 stand-in:
-        // k_gprep done 27 us, k_strict2 started 38.7 us)
-        static const int inorder_env = getenv("GRAAL_STRICT_INORDER") ? atoi(getenv("GRAAL_STRICT_INORDER")) : -1;
-        const bool inorder = inorder_env > 0;   // (measured: no gain -- the event in front of k_gprep costs what the one in front of k_strict2 did; kept as a switch)
-        if (inorder) {
-            CK(hipEventRecord(h->ev_tm, h->aux));
-            CK(hipStreamWaitEvent(st, h->ev_tm, 0));
-        }
-        k_gprep<<<GPREP_CLS_BLOCKS + cull_blocks, 256, 0, inorder ? st : h->aux>>>(h->tabs, h->pstart, fA, K, rank, world, sx.reach_bp, no_window, sx.quirk,
-                                                                     seg_unit, TILE, h->d_slist, h->d_slist_n, h->slist_cap,
-                                                                     (unsigned long long*)(h->d_scalars + 10), s2);
-        CK(hipGetLastError());
-        // (k_strict2 on the auxiliary stream right behind k_gprep -- stream order instead of the event, next to the scan, its waves waiting for the
-        // scan's completion counters before the queued contacts -- was tried: it starts 9 us earlier (a kernel behind an event of another stream
-        // starts ~10 us late whether the event completes right in front of it or has long completed), but full runs gained nothing (C2 stand-in,
-        // 100 cycles: 130 us per step without, 134-146 with) and on the C4 stand-in the waiting waves once kept the scan off the CUs until their
-        // bound ran out.  Not kept.)
-        if (!inorder && !gwait) {
-            CK(hipEventRecord(h->ev_tm, h->aux));      // (behind k_tm and k_gprep: tables, classes and unit list complete -- nobody spins for them)
-            CK(hipStreamWaitEvent(st, h->ev_tm, 0));
-        }
-        hipStream_t ks = st;
-        const size_t sslot = (size_t)(h->sring_calls % (long long)(h->sring.size() / 2));
-        if (h->ev_this_call) CK(hipEventRecord(h->sring[2 * sslot], ks));   // (behind the wait: the pair spans the kernel, not the scan in front of it)
-        if (h->single_sub) k_strict2<false><<<blocks, 256, 0, ks>>>(fa, sx, s2, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
-        else k_strict2<true><<<blocks, 256, 0, ks>>>(fa, sx, s2, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
-        CK(hipGetLastError());
-        if (h->ev_this_call) { CK(hipEventRecord(h->sring[2 * sslot + 1], ks)); h->sring_calls += 1; }
-        return GRAAL_OK;
+    // the union set's kernels (strict2.h): k_gprep (classes per pair of global pieces + the unit list) on the auxiliary stream behind
+    // k_tm, under the scan; k_strict2 waits for both
+    if (!h->d_uset) {
+        CK(hipMalloc(&h->d_uset, sizeof(USet)));
+        CK(hipMalloc(&h->d_cls, sizeof(GClass) * (size_t)US_MAXPAIRS * US_NCAND));
+        CK(hipMalloc(&h->d_cls_n, sizeof(int) * US_MAXPAIRS + 1024));   // (+ the units' draw counter, k_gprep's ticket and completion word: a line of its own each)
+        CK(hipMemset(h->d_cls_n, 0, sizeof(int) * US_MAXPAIRS + 1024));
+        CK(hipDeviceSynchronize());
     }
-    // the unit list holds at most K * nt (nt + 1) / 2 entries, nt = tiles of the two longest contigs (grow-only)
-    const unsigned long long nt = 2ull * (unsigned long long)((std::max(std::max(h->max_lcont, h->lcont_bound), 1) + 63) / 64);
+    const int lc = std::max(std::max(h->max_lcont, h->lcont_bound), 1);
     static const int blocks_env = getenv("GRAAL_STRICT_BLOCKS") ? atoi(getenv("GRAAL_STRICT_BLOCKS")) : 0;
-    const int lc = std::max(h->max_lcont, h->lcont_bound);
-    const int blocks = blocks_env > 0 ? blocks_env : (lc > 0 && lc <= 64 ? 32 : (lc <= 1024 ? 512 : 1024));
-    // fragments y per unit: a 64 x 64 tile pair under half a dozen classes with nine slot pairs each is a millisecond of dependent
-    // float32 powf / expf in ONE wave -- with contigs of a few hundred bins a step has a few dozen tile pairs, and the C2 stand-in
-    // ran at 3.2 ms per step.  The y tile is cut into segments so that the grid has ~6 units per wave (bounded below: the x tile
-    // is loaded once per unit) -- by k_strict_cull, which knows the sets of THIS step; GRAAL_STRICT_SEG fixes it.
+    // (the GRID by the longest contig as last seen -- one commit stale: a performance choice; everything that must HOLD the step is sized by
+    // the bound `lc`, twice that + 2.  By the bound, contigs of 130-256 bins went to the 1,024-block grid behind an event instead of the
+    // 512-block one that follows k_gprep through its word: GRAAL_S2_GRID_BY_BOUND=1 for A/B)
+    static const bool grid_by_bound = getenv("GRAAL_S2_GRID_BY_BOUND") != nullptr;
+    const int lg = grid_by_bound ? lc : std::max(h->max_lcont, 1);
+    const int blocks = blocks_env > 0 ? blocks_env : (lg <= 64 ? 32 : (lg <= 256 ? 512 : 1024));
+    // fragments per tile: 64 (one per lane); with several sub-fragments per bin 32 -- the halves of a wave hold the same 32 fragments and
+    // take two fragments of the segment at a time (k_strict2): a unit is a 32 x 4 block instead of a 64 x 2 strip, which wastes fewer lanes
+    // on pieces of a few dozen bins and at the window's edge (GRAAL_S2_TILE=64: the strips, for A/B)
+    static const int tile_env = getenv("GRAAL_S2_TILE") ? atoi(getenv("GRAAL_S2_TILE")) : 0;
+    const int TILE = tile_env == 64 ? 64 : (tile_env == 32 ? 32 : (h->single_sub ? 64 : 32));
+    // tiles of the union: at most K + 1 contigs, at most every fragment; + one partial tile per global piece
+    const unsigned long long nt = std::min<unsigned long long>((unsigned long long)(K + 1) * (unsigned long long)((lc + TILE - 1) / TILE),
+                                                               (unsigned long long)((h->n + TILE - 1) / TILE + K + 1)) + (unsigned long long)US_MAXP;
+    if (nt >= 65536ull) return fail(h, GRAAL_E_STATE, "reference arithmetic: more than 65,535 tiles in a step's union set");
+    // the unit list's entries: 4 fragments of the segment side (one sub-fragment per bin; k_strict2 merges up to 4 of them) or 1 (several:
+    // up to 2); GRAAL_STRICT_SEG fixes the entry size (entries of one fragment at one sub-fragment per bin: the list's traffic cost the C4
+    // stand-in 20 % of its run), GRAAL_STRICT_REP the waves that may share one unit's classes (1, 2, 4, 8)
     static const int seg_env = getenv("GRAAL_STRICT_SEG") ? atoi(getenv("GRAAL_STRICT_SEG")) : 0;
-    const int seg_fixed = (seg_env == 1 || seg_env == 2 || seg_env == 4 || seg_env == 8 || seg_env == 16 || seg_env == 32 || seg_env == 64) ? seg_env : 0;
-    const int seg_min = h->single_sub ? 4 : 1;
-    const unsigned long long target = 6ull * 4ull * (unsigned long long)blocks;
-    sx.seg = 0;
-    // units: at most one per tile pair when the segments stay whole tiles, below 2 x target once they are cut (the cut stops at the
-    // first size that reaches the target), or every tile pair cut to the fixed / smallest size
-    const unsigned long long pairs_max = (unsigned long long)K * nt * (nt + 1ull) / 2ull;
-    const unsigned long long need = (seg_fixed ? pairs_max * (unsigned long long)(64 / seg_fixed)
-                                               : std::max(pairs_max, std::min(pairs_max * (unsigned long long)(64 / seg_min), 2ull * target))) + 64ull;
+    const int seg_max = h->single_sub ? 16 : (TILE == 32 ? 4 : 2);   // (k_strict2's segment: SEG, seg_cap)
+    // (one sub-fragment per bin: entries of 4 fragments -- of 16, a whole unit, once a contig may exceed 512 bins: a unit of 64 x 4 pairs is
+    // 13 us of set-up for ~1 us per class, and the kernel merges neighbouring entries only from 49,000 of them on; C4 stand-in, 4 cycles:
+    // 214 us per step against 224, the late stage unchanged)
+    // (tiles of 32: entries of TWO fragments, one per half of the wave -- FOUR once the longest contig may hold more than 512 bins (the bound,
+    // one commit stale: twice the longest + 2): a step there has a few thousand units, more than half the grid's waves, so no two waves share
+    // one; with half as many, twice as long, every unit is shared by two waves and none idles.  C3 stand-in (contigs of 350 bins): 142 us
+    // per step against 157; C2 stand-in (contigs of 150-220): 108 against 99)
+    const int seg_unit = ((seg_env == 1 || seg_env == 2 || seg_env == 4 || seg_env == 8 || seg_env == 16) && seg_env <= seg_max) ? seg_env
+                                                                                             : (h->single_sub ? (lc > 512 ? 16 : 4) : (TILE == 32 ? (lc > 512 ? 4 : 2) : 1));
+    static const int rep_env = getenv("GRAAL_STRICT_REP") ? atoi(getenv("GRAAL_STRICT_REP")) : 8;
+    const int rep_max = rep_env >= 16 ? 16 : (rep_env >= 8 ? 8 : (rep_env >= 4 ? 4 : (rep_env >= 2 ? 2 : 1)));
+    // units the grid wants before k_strict2 merges neighbouring entries into longer units (per wave: 6 at one sub-fragment per bin; with
+    // several, a unit's fragment pairs are nine evaluations each -- GRAAL_S2_TARGET_X4: the figure in quarters, for A/B)
+    static const int target_env = getenv("GRAAL_S2_TARGET_X4") ? atoi(getenv("GRAAL_S2_TARGET_X4")) : 0;
+    const unsigned long long target_x4 = target_env > 0 ? (unsigned long long)target_env : 24ull;
+    const unsigned long long target = std::max<unsigned long long>(1ull, target_x4 * 4ull * (unsigned long long)blocks / 4ull);
+    // The list's worst case -- EVERY tile pair of the union listed -- is quadratic in the union's size (2e9 entries for 1e6 fragments in a few
+    // contigs), while the interval cull lists the pairs within reach of each other under some candidate: orders of magnitude fewer.
+    // It is sized ONCE per layout size, for the largest union n fragments and MAXK neighbours can form -- not for this step's longest
+    // contig: growing it with the contigs meant a hipFree / hipMalloc behind two stream synchronizes in the middle of a run, again and
+    // again while an assembly's contigs grow.  One rank: SLIST_SOFT_CAP entries at most to begin with; if a step's list overflows,
+    // k_gprep says so (counters[6] bit 1), the step ends as failed, eval_sync raises the floor and repeats it.  Several ranks: the worst
+    // case (a repeated step on ONE rank would leave the ranks out of step).
+    const unsigned long long nt_n = (unsigned long long)((h->n + TILE - 1) / TILE + MAXK + 1) + (unsigned long long)US_MAXP;
+    const unsigned long long worst = (nt_n * (nt_n + 1ull) / 2ull) * (unsigned long long)(TILE / seg_unit) + 64ull;
+    const unsigned long long SLIST_SOFT_CAP = h->slist_soft_cap;   // (GRAAL_SLIST_SOFT_CAP, read when the handle is created)
+    h->slist_worst = worst;
+    const unsigned long long need = (world == 1 && publish) ? std::min(worst, std::max(SLIST_SOFT_CAP, h->slist_floor)) : worst;
     if (need > h->slist_cap) {
-        CK(hipStreamSynchronize(st));
-        CK(hipStreamSynchronize(h->aux));
+        CK(hipDeviceSynchronize());   // (rare: the first tiled step of a layout size, or a list that has just overflowed)
         if (h->d_slist) CK(hipFree(h->d_slist));
         h->d_slist = nullptr;
-        const unsigned long long cap = std::max<unsigned long long>(need + need / 2ull, 1ull << 16);
+        h->slist_cap = 0;
+        const unsigned long long cap = std::max<unsigned long long>(need, 64ull);
         CK(hipMalloc(&h->d_slist, cap * sizeof(unsigned long long)));
         h->slist_cap = cap;
     }
-    // (the list's length lives in the scalars block -- zeroed, synchronously, when the context was created: a hipMemset issued
-    // here could still be in flight when k_strict_cull counts into it)
     h->d_slist_n = (unsigned long long*)(h->d_scalars + SLIST_N);
     sx.list_cap = h->slist_cap;
+    fa.norm_u = h->uniform_accu > 0 ? (float)(h->uniform_accu * h->uniform_accu) / h->nfpb : -1.0f;
+    static const int s2_skip = getenv("GRAAL_S2_SKIP") ? atoi(getenv("GRAAL_S2_SKIP")) : 0;   // (diagnostics: wrong sums.  1 = no units, 2 = no queued contacts)
+    fa.skip = s2_skip;
     const int no_window = (sx.quirk && h->n_ubins > 0) ? 1 : 0;
-    // rows of candidate units = tiles of the affected sets: a block per row up to the chip's width
-    const int cull_blocks = (int)std::min<unsigned long long>(1024ull, std::max<unsigned long long>(1ull, (unsigned long long)K * nt));
-    k_strict_cull<<<cull_blocks, 256, 0, h->aux>>>(h->tabs, h->geo, h->link, h->cbase, h->perm, fA, K, rank, world, sx.reach_bp, no_window, seg_fixed, seg_min, target,
-                                                   h->d_slist, h->d_slist_n, h->slist_cap, (unsigned long long*)(h->d_scalars + 10));
+    S2Args s2;
+    s2.uset = h->d_uset; s2.cls = h->d_cls; s2.cls_n = h->d_cls_n; s2.seg_unit = seg_unit; s2.rep_max = rep_max; s2.target = target;
+    static const int draw_env = getenv("GRAAL_STRICT_DRAW") ? atoi(getenv("GRAAL_STRICT_DRAW")) : 8;
+    s2.draw_min = draw_env > 0 ? draw_env : 8;
+    s2.next = reinterpret_cast<unsigned long long*>(h->d_cls_n + US_MAXPAIRS + (US_MAXPAIRS & 1));
+    // k_strict2 behind k_gprep WITHOUT an event (S2Args::gp): a kernel behind an event of another stream starts ~11 us after the event
+    // completes (tools/stamps_s2.py, C2 stand-in: k_gprep done 23 us, k_strict2 started 37; without any ordering -- GRAAL_DEBUG runs -- 26, as
+    // soon as the host has submitted it).  k_gprep's results go out as device-scope stores, its last block stores the step's number, and
+    // k_strict2's blocks wait for that word.  Only a grid that leaves room for k_gprep's blocks on every CU may wait for them in the kernel
+    // (512 blocks: two per CU; cf. fin_blocks_no_wait), only one rank (a repeated step must not leave the ranks out of step), only while
+    // the engine's streams are known to run side by side (spin_ok).  (768 blocks -- three per CU, still room -- with the wait instead of 1,024
+    // behind the event: C3 / C4 stand-ins 214-221 / 238-243 us per step against 200-203 / 222-225.)
+    // (round 5 tried the word with the 1,024-block grids too: the wait ran out in every run -- C3 and C4 stand-ins -- and the engine went back to
+    // events, as the argument above predicts)
+    const bool gwait = h->gwait_env && publish && world == 1 && h->spin_ok && blocks <= 512;
+    s2.gp = gwait ? s2.next + 32 : nullptr;   // (ticket: 256 bytes behind the draw counter; the completion word 256 bytes behind the ticket: GP_DONE)
+    s2.gp_seq = (unsigned long long)h->seq;
+    s2.gp_wait_ticks = h->gp_wait_ticks;
+    s2.gp_acquire = h->gp_acquire;
+    if (gwait) { h->spin_used = true; h->rc_gwait += 1; } else h->rc_gevent += 1;
+    const int cull_blocks = (int)std::min<unsigned long long>(1024ull, std::max<unsigned long long>(1ull, nt));
+    // k_gprep goes out on the auxiliary stream behind k_tm, under the scan.  (On the MAIN stream behind the scan and an event of k_tm, with
+    // k_strict2 following it in stream order, was measured for short scans: no gain -- the event in front of k_gprep costs what the one in
+    // front of k_strict2 did.)
+    k_gprep<<<GPREP_CLS_BLOCKS + cull_blocks, 256, 0, h->aux>>>(h->tabs, h->pstart, fA, K, rank, world, sx.reach_bp, no_window, sx.quirk,
+                                                                 seg_unit, TILE, h->d_slist, h->d_slist_n, h->slist_cap,
+                                                                 (unsigned long long*)(h->d_scalars + 10), s2);
     CK(hipGetLastError());
-    CK(hipEventRecord(h->ev_tm, h->aux));      // (behind k_tm and the cull: tables and unit list complete -- nobody spins for them)
-    CK(hipStreamWaitEvent(st, h->ev_tm, 0));
-    if (h->single_sub) k_strict<false><<<blocks, 256, strict_dyn_lds(K), st>>>(fa, sx, fA, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
-    else k_strict<true><<<blocks, 256, strict_dyn_lds(K), st>>>(fa, sx, fA, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
+    // (k_strict2 on the auxiliary stream right behind k_gprep -- stream order instead of the event, next to the scan, its waves waiting for the
+    // scan's completion counters before the queued contacts -- was tried: it starts 9 us earlier (a kernel behind an event of another stream
+    // starts ~10 us late whether the event completes right in front of it or has long completed), but full runs gained nothing (C2 stand-in,
+    // 100 cycles: 130 us per step without, 134-146 with) and on the C4 stand-in the waiting waves once kept the scan off the CUs until their
+    // bound ran out.  Not kept.)
+    if (!gwait) {
+        CK(hipEventRecord(h->ev_tm, h->aux));      // (behind k_tm and k_gprep: tables, classes and unit list complete -- nobody spins for them)
+        CK(hipStreamWaitEvent(st, h->ev_tm, 0));
+    }
+    hipStream_t ks = st;
+    const size_t sslot = (size_t)(h->sring_calls % (long long)(h->sring.size() / 2));
+    if (h->ev_this_call) CK(hipEventRecord(h->sring[2 * sslot], ks));   // (behind the wait: the pair spans the kernel, not the scan in front of it)
+    if (h->single_sub) k_strict2<false><<<blocks, 256, 0, ks>>>(fa, sx, s2, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
+    else k_strict2<true><<<blocks, 256, 0, ks>>>(fa, sx, s2, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
     CK(hipGetLastError());
+    if (h->ev_this_call) { CK(hipEventRecord(h->sring[2 * sslot + 1], ks)); h->sring_calls += 1; }
     return GRAAL_OK;
 }
 
@@ -5252,16 +4834,8 @@ int launch_strict(Ctx* h, int fA, int K, int rank, int world, long long* d_q_out
 int launch_flat(Ctx* h, int fA, const Neigh* nbp /* nullptr: the neighbours of the evaluation in flight */, int K, int rank, int world, long long* d_q_out, bool publish, hipStream_t st)
 {
     FinArgs fa;
-    fa.tm_done = h->tm_done; fa.step_hdr = h->step_hdr; fa.counters = (unsigned long long*)(h->d_scalars + 10); fa.queue = h->queue;
-    fa.cnt = h->cnt; fa.multi = h->single_sub ? 0 : 1;
-    fa.tabs = h->tabs; fa.geo = h->geo; fa.stat = h->stat_frag; fa.acc = h->d_acc; fa.sync = h->d_sync;
-    fa.ln_tab = nullptr; fa.lut_n = 0; fa.skip = 0; fa.seg = 0; fa.norm_u = -1.0f; fa.upw = 4; fa.wq = nullptr;
     StrictArgs sx;
-    sx.perm = h->perm; sx.cbase = h->cbase; sx.lcontbp = h->soa[h->cur].p[F_LCONTBP]; sx.link = h->link; sx.nfpb = h->nfpb; sx.par = h->par;
-    sx.quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
-    sx.reach_bp = reach_bp(h);
-    sx.list_cap = 0;
-    sx.seg = 64;
+    strict_args(h, fa, sx);
     static const int blocks_env = getenv("GRAAL_FLAT_BLOCKS") ? atoi(getenv("GRAAL_FLAT_BLOCKS")) : 0;
     const int blocks = blocks_env > 0 ? std::min(blocks_env, FLAT_BLOCKS) : FLAT_BLOCKS;
     Neigh nb;
@@ -5473,7 +5047,7 @@ void graal_destroy(graal_ctx* h)
     if (h->eval_timing && h->et_n[0]) {
         const double n = (double)h->et_n[0], m = (double)std::max<long long>(h->et_n[1], 1);
         fprintf(stderr, "graal eval timing: %lld synchronous evaluations, launches %.1f us each; %lld finished by k_tm (%.1f us from launch to result); "
-                        "%lld needed k_fin / k_strict: %.1f us until k_tm said so, %.1f us to launch them, %.1f us until the result (%.1f us in all)\n",
+                        "%lld needed k_fin / k_strict_flat / k_strict2: %.1f us until k_tm said so, %.1f us to launch them, %.1f us until the result (%.1f us in all)\n",
                 h->et_n[0], h->et[0] / n, h->et_n[0] - h->et_n[1], h->et[4] / (double)std::max<long long>(h->et_n[0] - h->et_n[1], 1),
                 h->et_n[1], h->et[1] / m, h->et[2] / m, h->et[3] / m, h->et[5] / m);
     }

@@ -10,7 +10,7 @@
 //     of a class (transformed start, orientation, sub-fragment centres) is computed once per (unit, class), the segment side once
 //     per (fragment, class) by one lane each; what remains per (pair, class) is the contact model itself;
 //   * the lanes of a wave take the fuller tile of a tile pair (a cut fragment is a tile of its own).
-// Unit list by the cull blocks of k_gprep (interval arithmetic on tile extents, as k_strict_cull), dealt to ranks by (ti + tj) % world.
+// Unit list by the cull blocks of k_gprep (interval arithmetic on tile extents), dealt to ranks by (ti + tj) % world.
 
 struct S2Args {
     USet* uset;            // written by block 0 of k_gprep

@@ -1,5 +1,5 @@
 """Shared by tests/test_strict_windowed_gpu.py and its child process: a fixed list of (problem, layouts, proposals) cases for the
-reference-arithmetic candidate kernels.  The parent runs them through k_tm / k_strict_cull + k_strict (the product path), the
+reference-arithmetic candidate kernels.  The parent runs them through k_tm / k_strict_flat / k_gprep + k_strict2 (the product path), the
 child -- ``python -m tests.strict_cases out.npz`` with ``GRAAL_STRICT_DENSE=1`` in its environment -- through k_strict_dense, the
 O(m^2) validation kernel that prices every pixel of contig(fA) u contig(fB) under every candidate (kernels3.cu:3259-3718 as written);
 both store the candidates' int64 fixed-point sums, which must be EQUAL."""

@@ -169,7 +169,7 @@ def test_c5_reference_arithmetic_at_full_size(c5_original, c5):
     """GRAAL_MODE_STRICT on C5's OWN fragments (generic bp lengths at coordinates of thousands of kb -- where the float32 noise of
     the reference's geometry is largest, see above).  At one sub-fragment per bin the reference's candidate delta is
     full(after) - full(before) pixel by pixel, so -- unlike the default mode, which needs the grid variant for this -- the
-    windowed strict kernels (k_strict_cull + k_strict) must reproduce the difference of two FULL evaluations (independent
+    windowed strict kernels (k_gprep + k_strict2) must reproduce the difference of two FULL evaluations (independent
     kernels: k_full_nnz / k_full_mass) on the 7 original contigs; and the default mode's distance from the reference arithmetic
     is recorded for the late stage and for the headline state bench.py measures."""
     import json

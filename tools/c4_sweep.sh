@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: the C4 stand-in (explode + 2 cycles, reference arithmetic) under k_strict launch variants.  usage: tools/c4_sweep.sh "ENV=VAL,ENV=VAL" ...
+# GPU box: the C4 stand-in (explode + 2 cycles, reference arithmetic) under launch variants of the reference-arithmetic kernels.  usage: tools/c4_sweep.sh "ENV=VAL,ENV=VAL" ...
 REPO=${GRAFT_REPO_ROOT:-$PWD}
 cd $REPO
 OUT=gpurun_out/c4_sweep.log

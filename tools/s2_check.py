@@ -1,5 +1,5 @@
-"""GPU box: the union-set kernels (k_gprep + k_strict2) against the O(m^2) validation kernel and against round 3's per-neighbour
-kernels on tests/strict_cases.py, case by case (int64 sums must be EQUAL).  Usage: python tools/s2_check.py [cases, e.g. 0,1,4]"""
+"""GPU box: the union-set kernels (k_gprep + k_strict2), alone and behind k_strict_flat as by default, against the O(m^2) validation
+kernel on tests/strict_cases.py, case by case (int64 sums must be EQUAL).  Usage: python tools/s2_check.py [cases, e.g. 0,1,4]"""
 import os
 import subprocess
 import sys
@@ -24,7 +24,7 @@ def run(tag, **env):
 
 
 dense = run("dense", GRAAL_STRICT_DENSE="1")
-variants = {"v2 tiled (no flat)": dict(GRAAL_NO_FLAT="1"), "default (flat + v2)": {}, "v1 tiled (no flat)": dict(GRAAL_NO_FLAT="1", GRAAL_STRICT_V1="1")}
+variants = {"v2 tiled (no flat)": dict(GRAAL_NO_FLAT="1"), "default (flat + v2)": {}}
 ok = True
 for tag, env in variants.items():
     got = run(tag.split()[0] + str(len(env)), **env)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU box, debug build (-DGRAAL_STAMPS): in-kernel wall-clock stamps of MCMC steps in the MIDDLE of a run -- the C4 stand-in
 (40,000 bins, 8 M contacts) after its first cycle, contigs of ~20-100 bins, reference arithmetic: where a step that needs
-k_strict_cull + k_strict spends its time."""
+k_strict_flat (or k_gprep + k_strict2) spends its time."""
 import ctypes, os, sys, subprocess, time
 import torch
 import numpy as np
@@ -36,14 +36,14 @@ for j, i in enumerate(order[:N]):
     assert L.graal_debug_stamps(smp.engine._h, st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))) == 0   # (synchronises the device)
     S[j] = st.astype(np.float64) * 0.01      # us
     C[j] = smp.engine.last_counters()
-strict = S[:, 16] > S[:, 8]          # k_strict ran in this step (its stamp is younger than the step's scan start)
-print("%d of %d steps needed k_strict; host time per step: those %.1f us, the others %.1f us" % (strict.sum(), N, host[strict].mean(), host[~strict].mean()))
+strict = S[:, 16] > S[:, 8]          # k_strict_flat / k_strict2 ran in this step (its stamp is younger than the step's scan start)
+print("%d of %d steps needed k_strict_flat / k_strict2; host time per step: those %.1f us, the others %.1f us" % (strict.sum(), N, host[strict].mean(), host[~strict].mean()))
 print("queued contacts per strict step: mean %.0f median %.0f max %.0f; work units: mean %.0f median %.0f max %.0f" % (C[strict][:, 2].mean(), np.median(C[strict][:, 2]), C[strict][:, 2].max(), C[strict][:, 3].mean(), np.median(C[strict][:, 3]), C[strict][:, 3].max()))
-names = [(22, "k_incr start"), (0, "k_tm start"), (8, "k_scan start"), (24, "k_tm: fA / fB records loaded"), (25, "k_tm: piece representatives loaded"), (26, "k_tm: transforms"), (1, "k_tm tables done"), (10, "k_scan block 0 loop done"), (29, "k_strict_cull start (tiled path only)"),
-         (3, "k_tm: last neighbour's tables released"), (16, "k_strict[_flat] start (block 0)"), (21, "k_strict_flat: tables seen"), (17, "k_strict block 0 past its prologue"), (18, "k_strict units done (latest wave)"),
-         (19, "k_strict queued contacts done (latest wave)"), (20, "k_strict published")]
+names = [(22, "k_incr start"), (0, "k_tm start"), (8, "k_scan start"), (24, "k_tm: fA / fB records loaded"), (25, "k_tm: piece representatives loaded"), (26, "k_tm: transforms"), (1, "k_tm tables done"), (10, "k_scan block 0 loop done"), (29, "k_tm: slots"),
+         (3, "k_tm: last neighbour's tables released"), (16, "k_strict2 / k_strict_flat start (block 0)"), (21, "k_strict_flat: tables seen"), (17, "k_strict2 / k_strict_flat block 0 past its prologue"), (18, "k_strict2 / k_strict_flat units done (latest wave)"),
+         (19, "k_strict2 / k_strict_flat queued contacts done (latest wave)"), (20, "k_strict2 / k_strict_flat published")]
 ref = S[strict][:, 8]
 for idx, nm in names:
     d = S[strict][:, idx] - ref
     ok = np.abs(d) < 1e5
-    print("  %-46s %7.2f us (median %7.2f)" % (nm, d[ok].mean(), np.median(d[ok])))
+    print("  %-62s %7.2f us (median %7.2f)" % (nm, d[ok].mean(), np.median(d[ok])))
