@@ -796,13 +796,6 @@ __global__ __launch_bounds__(256) void k_incr(SoaPtr s, int n, const Changed* __
         STAMP(31, t == 0);
         return;
     }
-#if defined(GRAAL_STAMPS) && defined(GRAAL_EXP_INCR_CHECK)
-    // (diagnostics, tools/incr_check.py: is the committed layout complete when this kernel STARTS?  The fragment's label and position
-    // are read here and again behind the plan; g_stamps[27] counts the fragments for which the two reads differ)
-    const int f_early = blockIdx.x * blockDim.x + t;
-    const int c_early = f_early < n ? __hip_atomic_load(&s.p[F_IDC][f_early], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    const int pos_early = f_early < n ? __hip_atomic_load(&s.p[F_POS][f_early], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-#endif
     if (t == 0) {
         // (built in LDS: as a private struct its dynamically indexed arrays lived in scratch memory -- two dozen dependent scratch accesses in
         // front of every block of this kernel)
@@ -875,9 +868,6 @@ __global__ __launch_bounds__(256) void k_incr(SoaPtr s, int n, const Changed* __
     if (f >= p.nc_new && f < n) len_new[f] = 0; // keep the tail of the length array zero
     if (f >= n) return;
     const int c = s.p[F_IDC][f];
-#if defined(GRAAL_STAMPS) && defined(GRAAL_EXP_INCR_CHECK)
-    if (c != c_early || s.p[F_POS][f] != pos_early) atomicAdd(&g_stamps[27], 1ull);
-#endif
     int rank = -1, off = 0, lenc = 0;
     for (int i = 0; i < 4; i++)
         if (i < p.n_new && c == p.new_lab[i]) { rank = p.new_rank[i]; off = p.new_off[i]; lenc = p.new_len[i]; }
@@ -981,7 +971,7 @@ __global__ __launch_bounds__(256) void k_subrec(int n, const Geo* __restrict__ g
 // two RF counts only, so every block first tabulates its ln (same expressions, same device functions as the general path:
 // bit-identical) for the products that can occur, and such contacts skip the float64 logarithm.
 constexpr int LN_TRANS_LUT = 1024;
-// FULL_G = groups of 4 contacts per lane and iteration (template parameter; GRAAL_FULL_G picks 1, 2 or 4 for experiments)
+// FULL_G = groups of 4 contacts per lane and iteration (template parameter; the host launches 2 -- 1 and 4 as measured: profiles/r02_full_eval_variants.log)
 __device__ __forceinline__ int w4(const int4& q, int j) { return j == 0 ? q.x : (j == 1 ? q.y : (j == 2 ? q.z : q.w)); }
 
 // The same when every sub-fragment carries the SAME RF count (level 0: one restriction fragment per bin; any level of a map whose
@@ -1451,7 +1441,7 @@ __device__ __forceinline__ void keep_xf(Xf& a, Xf& b) { asm volatile("" : "+v"(a
 // one staged fragment y of the mass walk (k_fin): transformed geometry + statistics, 64 bytes
 struct YTile { int start_bp, len_bp, flags, label, lbp; float c0, c1, c2; Stat st; };   // (c*: centres of its sub-fragments, kb)
 // completion counters of k_scan: N_DONE words on lines of their own take the blocks in turn, so that 496 device-scope atomics
-// do not queue on one address (measured: 0.3-0.5 us per step against the single counter, GRAAL_SCAN_DONE_N=1; tools/done_ab.sh)
+// do not queue on one address (measured: 0.3-0.5 us per step against the single counter: profiles/r02_done_counters_ab.log)
 constexpr int N_DONE = 16, DONE_STRIDE = 16;
 constexpr int FLAG_STRIDE = 32; // words between two blocks' completion flags: one 128-byte line each (partial writes to one
                                 // line from many XCDs serialise at the memory side)
@@ -2612,11 +2602,7 @@ __device__ __forceinline__ void scan_mark_affected(const ScanArgs& sa, const int
     }
     pre();
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-#ifdef GRAAL_EXP_NOFOLD   // (A/B build, tools/ab.sh: what the fold's one AND per id costs)
-    const unsigned wm = 0xffffffffu;
-#else
     const unsigned wm = sa.bm_wmask;
-#endif
     auto set_bits = [&](int fr) {   // mark fragment fr: its id, or the ids of its sub-fragments
         if (SINGLE_SUB) atomicOr(&s_bm[((unsigned)fr >> 5) & wm], 1u << (fr & 31));
         else {
@@ -2746,11 +2732,7 @@ __global__ __launch_bounds__(1024, (G <= 4 ? 8 : 4)) void k_scan(ScanArgs sa, in
                                            for (int i = 0; i < G; i++) f[i] = ldg(g0 + i * stride);
                                        }
                                    });
-#ifdef GRAAL_EXP_NOFOLD   // (A/B build, tools/ab.sh: what the fold's one AND per id costs)
-    const unsigned wm = 0xffffffffu;
-#else
     const unsigned wm = sa.bm_wmask;
-#endif
     const int4* __restrict__ col4 = sa.col4;
     const int* __restrict__ sub2bin = sa.sub2bin;
     QRaw* __restrict__ queue = sa.queue;
@@ -2804,10 +2786,6 @@ __global__ __launch_bounds__(1024, (G <= 4 ? 8 : 4)) void k_scan(ScanArgs sa, in
         // third test rejects leave entries with an empty neighbour mask behind, which the pricing skips).  One reservation per
         // PASS of the loop below -- up to 16 per iteration, 10^5 per step when two long contigs are affected -- made the tail
         // of the queue the bottleneck of the late stage: same-address atomics with return, ~0.7 ms of a 0.8 ms scan.
-#ifdef GRAAL_EXP_COLONLY   // (bisecting build: stop behind the second test -- wrong results)
-        n_rel += __popc(hit);
-        return;
-#endif
         // ---- third test.  The doubly-affected contacts of this wave iteration are first DEALT to the lanes, one each, through a
         // per-wave LDS list: they come in clusters -- the rows of a contig's fragments hold contacts with their contig mates next
         // to each other, so one lane owns four of them while the others own none -- and a lane used to take its contacts one per
@@ -2884,23 +2862,17 @@ __global__ __launch_bounds__(1024, (G <= 4 ? 8 : 4)) void k_scan(ScanArgs sa, in
 #pragma unroll
         for (int i = 0; i < G; i++) f[i] = ldg(g0 + i * stride);
     }
-#ifdef GRAAL_EXP_NOHITS   // (bisecting build, tools/ab_scan2.sh: the stream and the first test only -- wrong results)
-#define PROCESS_HITS(a, b, c) do { n_rel += __popc(c); } while (0)
-#else
-#define PROCESS_HITS(a, b, c) process_hits(a, b, c)
-#endif
     {
         const unsigned hit = test_rows(f, g0);
-        if (__ballot(hit != 0) != 0) PROCESS_HITS(f, g0, hit);
+        if (__ballot(hit != 0) != 0) process_hits(f, g0, hit);
     }
     for (int g = g0 + G * stride; g <= n4; g += G * stride) {
         int4 q[G];
 #pragma unroll
         for (int i = 0; i < G; i++) q[i] = ldg(g + i * stride);
         const unsigned hit = test_rows(q, g);
-        if (__ballot(hit != 0) != 0) PROCESS_HITS(q, g, hit);
+        if (__ballot(hit != 0) != 0) process_hits(q, g, hit);
     }
-#undef PROCESS_HITS
     STAMP(10, blockIdx.x == 0 && t == 0 && !dry);
     STAMP_BLK(2, t == 0 && !dry);
     n_rel = (unsigned long long)wave_sum_ll((long long)n_rel);
@@ -3094,7 +3066,7 @@ struct FinArgs { // first-needed pointers by value (see ScanArgs)
     unsigned long long* sync;
     const double* ln_tab;          // ln of the trans value by RF-count product (k_ln_tab), lut_n entries
     int lut_n;
-    int skip;                      // diagnostics (GRAAL_FIN_SKIP): 1 = no mass units, 2 = no queued contacts
+    int skip;                      // diagnostics: 1 = no mass units, 2 = no queued contacts (the host passes 0)
     int seg;                       // fragments y per mass unit (0: chosen per step)
     float norm_u;                  // >= 0: every sub-fragment has the same RF count a, and this is float(a * a) / nfpb
     int upw;                       // mass units per wave of the grid the unit size aims at
@@ -3188,7 +3160,7 @@ __global__ __launch_bounds__(256) void k_fin(const DevArgs* __restrict__ A, FinA
         // SEG: fragments y per unit.  At most 128 (16 with sub-fragments: up to 9 slot pairs per fragment pair), and small enough
         // for the step to have ~4 units per wave of the grid: a unit is one long dependent chain of float32 powf / expf, ~25 us
         // for 16 y with sub-fragments, and a step of the C2 stand-in has only ~1,500 such units for 2,048 waves -- its k_fin lasted
-        // 140 us for 12 us worth of VALU work, the few waves that got two or three units carried it (tools/fin_seg_ab.sh:
+        // 140 us for 12 us worth of VALU work, the few waves that got two or three units carried it (profiles/r02_fin_seg_sweep.log:
         // SEG 16 -> 2 takes the scoring phase from 138 to 79 us there, from 178 to 126 us at the C3 shape).
         const bool multi_sub = A->sub2bin_multi != nullptr;
         // ... and a unit is a RUN of segments: run r of a (task, chunk) takes the segments r, r + R, r + 2R, ... of the walk (R
@@ -4165,20 +4137,21 @@ struct Ctx {
     // graal_step's deferred flow (begin_step_launch(defer)): the next k_tm is ordered behind the relabel by a device flag that the
     // next k_scan sets, not by an event; and it publishes the layout statistics in an extra block
     bool relabel_spin_pending = false, stats_pub_pending = false;
-    bool spin_ok = getenv("GRAAL_NO_TM_SPIN") == nullptr;   // switched off when k_tm and k_scan turn out not to run concurrently
+    bool spin_ok = true;           // GRAAL_NO_TM_SPIN (graal_create); switched off when k_tm and k_scan turn out not to run concurrently
     bool spin_ok_saved = true;                                // ... and while an RCCL communicator is attached (graal_attach_rccl / graal_detach_rccl)
     unsigned long long relabel_flag_seq = 0, scan_relabel_seq = 0;
     bool pub_in_flight = false;   // ... and its k_tm carries the statistics' publication block (re-armed if the evaluation is repeated)
-    unsigned long long tm_spin_ticks = getenv("GRAAL_TM_SPIN_TICKS") ? strtoull(getenv("GRAAL_TM_SPIN_TICKS"), nullptr, 10) : 2000000ull;   // 100 MHz ticks
+    unsigned long long tm_spin_ticks = 2000000ull;   // 100 MHz ticks (GRAAL_TM_SPIN_TICKS, graal_create)
     bool spin_used = false;       // the evaluation in flight relies on the flag (eval_sync repeats it with an event if k_tm gives up)
     // k_strict2 behind k_gprep through a word in memory instead of an event (launch_strict): GRAAL_STRICT_GWAIT=0 orders them by the event,
     // GRAAL_GP_WAIT_TICKS bounds the in-kernel wait (100 MHz ticks; 1 = give up at once: the test hook that forces the repeat-behind-events path),
     // GRAAL_GP_ACQUIRE=0: only a block that had to wait runs the agent-scope acquire (round 4's form).  Default 1: every block's first wave runs
     // it behind its poll -- poll, acquire, wait for the invalidate, barrier, plain loads: the consumer form the memory model asks for, whatever
     // the caches held (MI355X_MICROARCH.md, inter-workgroup visibility); not measurable at the C2 stand-in (117-127 us per step either way)
-    bool gwait_env = getenv("GRAAL_STRICT_GWAIT") == nullptr || atoi(getenv("GRAAL_STRICT_GWAIT")) != 0;
-    int gp_wait_ticks = getenv("GRAAL_GP_WAIT_TICKS") ? std::max(1, atoi(getenv("GRAAL_GP_WAIT_TICKS"))) : 200000;   // 2 ms
-    int gp_acquire = getenv("GRAAL_GP_ACQUIRE") ? atoi(getenv("GRAAL_GP_ACQUIRE")) : 1;
+    // (all three read in graal_create)
+    bool gwait_env = true;
+    int gp_wait_ticks = 200000;   // 2 ms
+    int gp_acquire = 1;
     // run counters (graal_run_counters): evaluations, steps repeated behind events after an in-kernel wait ran out, k_strict2 launches that
     // followed k_gprep through the word / behind the event, k_strict_flat launches, steps k_tm's finisher handed to a finishing kernel
     long long rc_evals = 0, rc_repeats = 0, rc_gwait = 0, rc_gevent = 0, rc_flat = 0, rc_need_fin = 0;
@@ -4200,7 +4173,7 @@ struct Ctx {
     // the row index of the contact list (k_scan_rows)
     long long* rowptr = nullptr;  // [n_sub_total + 1] first contact of row >= s; null: the list is not sorted by row (no index: every step streams)
     long long longest_row = 0;    // contacts of the longest row (host side: the bound on what the indexed pass can visit)
-    int scan_path = getenv("GRAAL_SCAN_PATH") ? std::min(2, std::max(0, atoi(getenv("GRAAL_SCAN_PATH")))) : 0;   // graal_set_scan_path
+    int scan_path = 0;            // graal_set_scan_path; GRAAL_SCAN_PATH (graal_create)
     bool step_indexed = false;    // the evaluation being launched takes its contacts through the row index
     int repeat_producer = 0;      // a step repeated behind events keeps the producer it had: 1 streaming, 2 indexed (0: decide)
     long long rc_indexed = 0;     // evaluations whose contacts came through the row index (graal_run_counters)
@@ -4281,8 +4254,7 @@ struct Ctx {
     unsigned long long slist_worst = 0;      // the last launch's worst case (every tile pair of the union set listed)
     long long rc_list_grown = 0;
     long long rc_carry_repairs = 0;  // graal_step (flag 16): steps whose own-pixel correction was unknown and that evaluated the layout in full instead
-    unsigned long long slist_soft_cap = getenv("GRAAL_SLIST_SOFT_CAP") ? std::max<unsigned long long>(64ull, strtoull(getenv("GRAAL_SLIST_SOFT_CAP"), nullptr, 10))
-                                                                        : (1ull << 23);   // 8 M entries = 64 MB (C5's 7 contigs list ~1e5); tests set it small
+    unsigned long long slist_soft_cap = 1ull << 23;   // 8 M entries = 64 MB (C5's 7 contigs list ~1e5); GRAAL_SLIST_SOFT_CAP (graal_create): tests set it small
     USet* d_uset = nullptr;       // reference arithmetic over the step's union set (strict2.h): the set, the classes per pair of global pieces
     GClass* d_cls = nullptr;
     int* d_cls_n = nullptr;
@@ -4296,16 +4268,11 @@ struct Ctx {
     int event_every = 8;          // a HIP event pair around k_scan on every n-th evaluation (they cost a few us of gaps)
     long long eval_calls = 0;
     DevArgs* d_args = nullptr;    // [2]: one argument block per layout buffer
-    // GRAAL_EVAL_TIMING: host clock of the synchronous evaluation, printed when the context is destroyed (us per step: launches, until
-    // k_tm asked for the finishing kernels, their launches, until the result) -- [0] steps, [1] steps that needed them
     // reference arithmetic, one rank: `mid_run` = k_strict_flat goes out behind every scan and k_tm's last block does not try to
     // finish the step (set while most steps need more than k_tm: need_ema, a running mean of "this step did"); flat_tried = this
     // step's flat kernel has been launched (if it also says NEED_FIN, the tiled kernels follow)
     bool mid_run = false, flat_tried = false, step_needed_fin = false, step_needed_geom = false;
     double need_ema = 0.0;
-    bool eval_timing = getenv("GRAAL_EVAL_TIMING") != nullptr;
-    double et[6] = {0, 0, 0, 0, 0, 0};
-    long long et_n[2] = {0, 0};
     long long* h_res = nullptr;   // pinned host: [0] sequence number of the published step, [1..] K*13 sums
     long long* h_stats = nullptr; // pinned host: [0] sequence number, [1..16] the statistics words of k_stats_fin
     long long* h_full = nullptr;  // pinned host: [0] sequence number, [1..4] the sums / flags of the last full evaluation (k_full_pub)
@@ -4353,6 +4320,30 @@ struct Ctx {
 int fail(Ctx* h, int code, const char* msg) { h->err = msg; return code; }
 
 inline int blocks_for(long long n, int bs) { return (int)((n + bs - 1) / bs); }
+
+// ---- the environment switches read ONCE PER PROCESS, when the first of them is asked for (tests that set one
+// run a child process).  The switches read once per handle are in graal_create, the host loop's debug aids in host_step.h (HostStep).
+inline int env_int(const char* v, int unset) { return v ? atoi(v) : unset; }
+struct Env {
+    //   field                                                               unset   clamp / meaning
+    bool debug_addr = getenv("GRAAL_DEBUG_ADDR") != nullptr;               // off     debug_print_buffers
+    int scan_threads = env_int(getenv("GRAAL_SCAN_THREADS"), 0);            // 0       > 0: threads per block of k_scan (else by the list's size)
+    int scan_g = env_int(getenv("GRAAL_SCAN_G"), 4);                        // 4       2, 4 or 8 (anything else: 4)
+    bool scan_done_counter = !getenv("GRAAL_SCAN_DONE") || strcmp(getenv("GRAAL_SCAN_DONE"), "flags") != 0;   // on   "flags": per-block flags
+    int scan_blocks = env_int(getenv("GRAAL_SCAN_BLOCKS"), scan_groups() == 8 ? 256 - 8 : 256 * 2 - 16);     // (see scan_grid)   as given
+    int scan_fold_bits = getenv("GRAAL_SCAN_FOLD_BITS") ? std::min(18, std::max(5, atoi(getenv("GRAAL_SCAN_FOLD_BITS")))) : 0;   // 0 (by size)   5..18
+    long long scan_rows_r = getenv("GRAAL_SCAN_ROWS_R") ? std::max(1, atoi(getenv("GRAAL_SCAN_ROWS_R"))) : 16;                  // 16   >= 1
+    int fin_blocks = env_int(getenv("GRAAL_FIN_BLOCKS"), 0);                // 0       > 0: k_fin's grid
+    bool strict_dense = getenv("GRAAL_STRICT_DENSE") != nullptr && atoi(getenv("GRAAL_STRICT_DENSE")) != 0;   // off   k_strict_dense (validation)
+    bool no_flat = getenv("GRAAL_NO_FLAT") != nullptr;                      // off     never k_strict_flat
+    bool no_incr = getenv("GRAAL_NO_INCREMENTAL_RELABEL") != nullptr;       // off     every relabel sorts (no k_incr)
+    bool full_no_compact = getenv("GRAAL_FULL_NO_COMPACT") != nullptr;      // off     k_full_nnz whatever the RF counts
+    bool full_no_lds = getenv("GRAAL_FULL_NO_LDS") != nullptr;              // off     k_full_nnz_u instead of k_full_nnz_l
+    int full_mass_tiled = env_int(getenv("GRAAL_FULL_MASS_TILED"), -1);     // -1      0 = never k_full_mass_t, 1 = always
+    int stage_tables = env_int(getenv("GRAAL_STAGE_TABLES"), -1);           // -1      0 / 1: k_tm copies its tables never / always (else by the scan's length)
+    int scan_groups() const { return (scan_g == 8 || scan_g == 2) ? scan_g : 4; }
+};
+const Env& env() { static const Env e; return e; }
 
 // float32 log-factorial term of evaluate_likelihood_double (kernels3.cu:191-210, factorial :80-93)
 double lf_term(double ob)
@@ -4406,8 +4397,7 @@ int reach_bp(const Ctx* h) { return (int)ceil((double)h->par.d_max * 1000.0) + 1
 // can be matched to a buffer (the open fault of the two-ranks-on-one-GPU rehearsal)
 void debug_print_buffers(const Ctx* h, const char* when)
 {
-    static const bool on = getenv("GRAAL_DEBUG_ADDR") != nullptr;
-    if (!on) return;
+    if (!env().debug_addr) return;
     const size_t n = (size_t)h->n, nnz = (size_t)h->nnz;
     fprintf(stderr, "[graal addr, pid %d, %s] n %zu nnz %zu | soa0 %p soa1 %p | row %p col %p cnt %p (%zu B each) queue %p (%zu B) | geo %p link %p perm %p pstart %p cbase %p mates %p | "
                     "stat_frag %p sub2bin %p sub_rec %p | tabs %p d_args %p d_scalars %p d_acc %p d_sync %p d_done %p d_flags %p tm_done %p d_part %p d_chg %p | "
@@ -4467,39 +4457,23 @@ constexpr int SCAN_LDS_MAX = 48 * 1024; // affected bitmap of k_scan: 1 bit per 
 // the whole affected set in its prologue: 256-thread blocks there (C2 stand-in: 177 -> 165 us per step)
 int scan_threads_cfg(const Ctx* h)
 {
-    static const int v = getenv("GRAAL_SCAN_THREADS") ? atoi(getenv("GRAAL_SCAN_THREADS")) : 0;
+    const int v = env().scan_threads;
     return v > 0 ? v : (h->nnz < 2000000 ? 256 : 1024);
 }
 
-int scan_groups_cfg()
-{
-    static const int e = getenv("GRAAL_SCAN_G") ? atoi(getenv("GRAAL_SCAN_G")) : 4;
-    static const int v = (e == 8 || e == 2) ? e : 4;
-    return v;
-}
+int scan_groups_cfg() { return env().scan_groups(); }
 
 // How k_tm's finishing block learns that the scan is complete.  Default: every scan block adds itself to one counter with a
 // fire-and-forget atomic and the finisher polls that one word.  GRAAL_SCAN_DONE=flags: one flag line per block, all 496 of
 // them polled -- measured 1.5 us slower per step (each polling round is 8 uncached loads per lane behind the scan's own
 // stream in the memory queues: scan complete -> seen took ~7 us).
-bool scan_done_counter()
-{
-    static const bool v = getenv("GRAAL_SCAN_DONE") ? (strcmp(getenv("GRAAL_SCAN_DONE"), "flags") != 0) : true;
-    return v;
-}
-
-int scan_done_n()
-{
-    static const int e = getenv("GRAAL_SCAN_DONE_N") ? atoi(getenv("GRAAL_SCAN_DONE_N")) : N_DONE;
-    return e >= 1 && e <= N_DONE ? e : N_DONE;
-}
+bool scan_done_counter() { return env().scan_done_counter; }
 
 int scan_grid(const Ctx* h)
 {
     // two 1024-thread blocks per CU fill the 256 CUs; 16 fewer leave room for k_tm's blocks, which run at the same time (a
     // CU that hosts one of them takes only one scan block, and a scan block that has to wait for a slot ends 8 us late)
-    static const int scan_blocks = getenv("GRAAL_SCAN_BLOCKS") ? atoi(getenv("GRAAL_SCAN_BLOCKS"))
-                                                               : (scan_groups_cfg() == 8 ? 256 - 8 : 256 * 2 - 16);
+    const int scan_blocks = env().scan_blocks;   // (unset: 496, or 248 with 8 groups per lane)
     const long long groups = (h->nnz >> 2) + 1;
     const long long per_block = (long long)scan_groups_cfg() * scan_threads_cfg(h); // groups one block takes per iteration
     return (int)std::max<long long>(1, std::min<long long>((groups + per_block - 1) / per_block, scan_blocks));
@@ -4513,7 +4487,7 @@ void scan_bitmap_cfg(const Ctx* h, size_t* shm_out, unsigned* wmask_out)
     // (ScanArgs::bm_wmask): with a' affected ids a fraction a' / 2^18 of the rows takes the second test for nothing and
     // (a' / 2^18)^2 of the contacts is queued for nothing -- dropped by the consumers' membership test, results unchanged.
     // GRAAL_SCAN_FOLD_BITS = b folds onto 2^b bits whatever the size (tests: b = 10 makes every other row a false positive)
-    static const int fold_bits = getenv("GRAAL_SCAN_FOLD_BITS") ? std::min(18, std::max(5, atoi(getenv("GRAAL_SCAN_FOLD_BITS")))) : 0;
+    const int fold_bits = env().scan_fold_bits;
     size_t shm = (size_t)((h->n_sub_total + 31) / 32 + 2) * 4;
     unsigned wmask = 0xffffffffu;
     if (shm > (size_t)SCAN_LDS_MAX || fold_bits) {
@@ -4547,10 +4521,9 @@ bool rows_possible(const Ctx* h, int K, const char** why)
 // (reasoned, with the measured points there).  Per step, stateless; ranks may choose for themselves.
 bool scan_use_rows(const Ctx* h, int K)
 {
-    static const long long R = getenv("GRAAL_SCAN_ROWS_R") ? std::max(1, atoi(getenv("GRAAL_SCAN_ROWS_R"))) : 16;
     const char* why = nullptr;
     if (!rows_possible(h, K, &why)) return false;
-    return scan_rows_wins(rows_bound(h, K), h->longest_row, h->nnz, R);
+    return scan_rows_wins(rows_bound(h, K), h->longest_row, h->nnz, env().scan_rows_r);
 }
 
 // grid of the indexed pass: a wave per row of the bound, four waves per block, a few dozen blocks at most (every block pays the
@@ -4582,7 +4555,7 @@ int launch_scan(Ctx* h, int fA, const Neigh& nb, int K, int max_id, int dry, hip
     sa.relabel_flag = (unsigned long long*)(h->d_scalars + RELABEL_FLAG);
     sa.relabel_seq = dry ? 0ull : h->scan_relabel_seq;
     sa.done = (scan_done_counter() && !dry) ? h->d_done : nullptr;
-    sa.n_done = scan_done_n();
+    sa.n_done = N_DONE;
     if (sa.done) for (int c = 0; c < sa.n_done; c++) h->scan_done_total[c] += (unsigned long long)((nbk - c + sa.n_done - 1) / sa.n_done);
     if (nbk > MAX_SCAN_BLOCKS) return fail(h, GRAAL_E_ARG, "GRAAL_SCAN_BLOCKS too large");
     if (rows) {
@@ -4642,14 +4615,23 @@ int fin_blocks_no_wait(int K)
 
 int fin_blocks_cfg(const Ctx* h, int K)
 {
-    static const int fin_blocks_env = getenv("GRAAL_FIN_BLOCKS") ? atoi(getenv("GRAAL_FIN_BLOCKS")) : 0;
     // short contigs leave k_fin a handful of contacts: a small grid keeps its launch and completion ticket cheap.  Contigs of a
     // few hundred fragments: the largest grid that may spin for k_tm's tables (3 blocks per CU unless LDS allows fewer).
     // Contigs of thousands of fragments: long dependent chains, 4 resident blocks per CU and fresh ones as they retire keep the
     // VALUs busiest (2.8 -> 2.2 ms per step on C5's 7 contigs in round 1) -- that grid waits for k_tm through an event.
-    if (fin_blocks_env > 0) return fin_blocks_env;
+    if (env().fin_blocks > 0) return env().fin_blocks;
     if (h->max_lcont > 0 && h->max_lcont <= 16) return 32;
     return h->max_lcont > 1024 ? 2048 : std::min(768, fin_blocks_no_wait(K));
+}
+
+// what every finishing kernel is handed alike: the step's buffers, and k_fin's options at their fixed values (skip, seg, upw: once
+// switches of closed experiments; the kernels still take them as arguments)
+void fin_args(Ctx* h, FinArgs& fa)
+{
+    fa.tm_done = h->tm_done; fa.step_hdr = h->step_hdr; fa.counters = (unsigned long long*)(h->d_scalars + 10); fa.queue = h->queue;
+    fa.cnt = h->cnt; fa.multi = h->single_sub ? 0 : 1;
+    fa.tabs = h->tabs; fa.geo = h->geo; fa.stat = h->stat_frag; fa.acc = h->d_acc; fa.sync = h->d_sync;
+    fa.ln_tab = nullptr; fa.lut_n = 0; fa.skip = 0; fa.seg = 0; fa.norm_u = -1.0f; fa.upw = 4; fa.wq = nullptr;
 }
 
 // left-over mass items, queued contacts, hand-out.  Short contigs leave it a handful of contacts: a small grid keeps its
@@ -4658,37 +4640,23 @@ int launch_fin(Ctx* h, int K, int rank, int world, long long* d_q_out, bool publ
 {
     const int fin_blocks = fin_blocks_cfg(h, K);
     if (fin_blocks > fin_blocks_no_wait(K)) { CK(hipEventRecord(h->ev_tm, h->aux)); CK(hipStreamWaitEvent(st, h->ev_tm, 0)); }   // (see fin_blocks_no_wait)
-    static const int fin_skip = getenv("GRAAL_FIN_SKIP") ? atoi(getenv("GRAAL_FIN_SKIP")) : 0;   // (diagnostics: wrong sums)
     FinArgs fa;
-    fa.tm_done = h->tm_done; fa.step_hdr = h->step_hdr; fa.counters = (unsigned long long*)(h->d_scalars + 10); fa.queue = h->queue;
-    fa.cnt = h->cnt; fa.multi = h->single_sub ? 0 : 1;
-    fa.tabs = h->tabs; fa.geo = h->geo; fa.stat = h->stat_frag; fa.acc = h->d_acc; fa.sync = h->d_sync;
-    static const int fin_seg = getenv("GRAAL_FIN_SEG") ? atoi(getenv("GRAAL_FIN_SEG")) : 0;
-    fa.ln_tab = h->d_ln_tab; fa.lut_n = h->d_ln_tab ? h->ln_lut_n : 0; fa.skip = fin_skip; fa.seg = fin_seg;
+    fin_args(h, fa);
+    fa.ln_tab = h->d_ln_tab; fa.lut_n = h->d_ln_tab ? h->ln_lut_n : 0;
     fa.norm_u = h->uniform_accu > 0 ? (float)(h->uniform_accu * h->uniform_accu) / h->nfpb : -1.0f;
-    static const int fin_upw = getenv("GRAAL_FIN_UPW") ? std::max(1, atoi(getenv("GRAAL_FIN_UPW"))) : 4;
-    fa.upw = fin_upw;
-    static const bool fin_static = getenv("GRAAL_FIN_STATIC") != nullptr;   // (units and contact batches dealt statically)
-    fa.wq = fin_static ? nullptr : h->d_wq;
+    fa.wq = h->d_wq;
     k_fin<<<fin_blocks, 256, fin_dyn_lds(K), st>>>(h->d_args + h->cur, fa, h->last_fA_launch, K, rank, world, d_q_out, publish ? h->res_dev : nullptr, h->seq);
     CK(hipGetLastError());
     return GRAAL_OK;
 }
 
 // GRAAL_STRICT_DENSE=1: the O(m^2) validation kernel (k_strict_dense) instead of k_strict_flat / k_gprep + k_strict2 (tests compare them)
-bool strict_dense_cfg()
-{
-    static const bool v = getenv("GRAAL_STRICT_DENSE") != nullptr && atoi(getenv("GRAAL_STRICT_DENSE")) != 0;
-    return v;
-}
+bool strict_dense_cfg() { return env().strict_dense; }
 
 // what the reference-arithmetic kernels are handed alike: the step's buffers (none of k_fin's options) and the layout's constants
 void strict_args(Ctx* h, FinArgs& fa, StrictArgs& sx)
 {
-    fa.tm_done = h->tm_done; fa.step_hdr = h->step_hdr; fa.counters = (unsigned long long*)(h->d_scalars + 10); fa.queue = h->queue;
-    fa.cnt = h->cnt; fa.multi = h->single_sub ? 0 : 1;
-    fa.tabs = h->tabs; fa.geo = h->geo; fa.stat = h->stat_frag; fa.acc = h->d_acc; fa.sync = h->d_sync;
-    fa.ln_tab = nullptr; fa.lut_n = 0; fa.skip = 0; fa.seg = 0; fa.norm_u = -1.0f; fa.upw = 4; fa.wq = nullptr;
+    fin_args(h, fa);
     sx.perm = h->perm; sx.cbase = h->cbase; sx.lcontbp = h->soa[h->cur].p[F_LCONTBP]; sx.link = h->link; sx.nfpb = h->nfpb; sx.par = h->par;
     sx.quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     sx.reach_bp = reach_bp(h);
@@ -4719,27 +4687,21 @@ int launch_strict(Ctx* h, int fA, int K, int rank, int world, long long* d_q_out
         CK(hipDeviceSynchronize());
     }
     const int lc = std::max(std::max(h->max_lcont, h->lcont_bound), 1);
-    static const int blocks_env = getenv("GRAAL_STRICT_BLOCKS") ? atoi(getenv("GRAAL_STRICT_BLOCKS")) : 0;
     // (the GRID by the longest contig as last seen -- one commit stale: a performance choice; everything that must HOLD the step is sized by
     // the bound `lc`, twice that + 2.  By the bound, contigs of 130-256 bins went to the 1,024-block grid behind an event instead of the
-    // 512-block one that follows k_gprep through its word: GRAAL_S2_GRID_BY_BOUND=1 for A/B)
-    static const bool grid_by_bound = getenv("GRAAL_S2_GRID_BY_BOUND") != nullptr;
-    const int lg = grid_by_bound ? lc : std::max(h->max_lcont, 1);
-    const int blocks = blocks_env > 0 ? blocks_env : (lg <= 64 ? 32 : (lg <= 256 ? 512 : 1024));
+    // 512-block one that follows k_gprep through its word)
+    const int lg = std::max(h->max_lcont, 1);
+    const int blocks = lg <= 64 ? 32 : (lg <= 256 ? 512 : 1024);
     // fragments per tile: 64 (one per lane); with several sub-fragments per bin 32 -- the halves of a wave hold the same 32 fragments and
     // take two fragments of the segment at a time (k_strict2): a unit is a 32 x 4 block instead of a 64 x 2 strip, which wastes fewer lanes
-    // on pieces of a few dozen bins and at the window's edge (GRAAL_S2_TILE=64: the strips, for A/B)
-    static const int tile_env = getenv("GRAAL_S2_TILE") ? atoi(getenv("GRAAL_S2_TILE")) : 0;
-    const int TILE = tile_env == 64 ? 64 : (tile_env == 32 ? 32 : (h->single_sub ? 64 : 32));
+    // on pieces of a few dozen bins and at the window's edge
+    const int TILE = h->single_sub ? 64 : 32;
     // tiles of the union: at most K + 1 contigs, at most every fragment; + one partial tile per global piece
     const unsigned long long nt = std::min<unsigned long long>((unsigned long long)(K + 1) * (unsigned long long)((lc + TILE - 1) / TILE),
                                                                (unsigned long long)((h->n + TILE - 1) / TILE + K + 1)) + (unsigned long long)US_MAXP;
     if (nt >= 65536ull) return fail(h, GRAAL_E_STATE, "reference arithmetic: more than 65,535 tiles in a step's union set");
-    // the unit list's entries: 4 fragments of the segment side (one sub-fragment per bin; k_strict2 merges up to 4 of them) or 1 (several:
-    // up to 2); GRAAL_STRICT_SEG fixes the entry size (entries of one fragment at one sub-fragment per bin: the list's traffic cost the C4
-    // stand-in 20 % of its run), GRAAL_STRICT_REP the waves that may share one unit's classes (1, 2, 4, 8)
-    static const int seg_env = getenv("GRAAL_STRICT_SEG") ? atoi(getenv("GRAAL_STRICT_SEG")) : 0;
-    const int seg_max = h->single_sub ? 16 : (TILE == 32 ? 4 : 2);   // (k_strict2's segment: SEG, seg_cap)
+    // the unit list's entries: 4 fragments of the segment side (one sub-fragment per bin; k_strict2 merges up to 4 of them) or 2 (several);
+    // with entries of one fragment at one sub-fragment per bin the list's traffic cost the C4 stand-in 20 % of its run
     // (one sub-fragment per bin: entries of 4 fragments -- of 16, a whole unit, once a contig may exceed 512 bins: a unit of 64 x 4 pairs is
     // 13 us of set-up for ~1 us per class, and the kernel merges neighbouring entries only from 49,000 of them on; C4 stand-in, 4 cycles:
     // 214 us per step against 224, the late stage unchanged)
@@ -4747,15 +4709,9 @@ int launch_strict(Ctx* h, int fA, int K, int rank, int world, long long* d_q_out
     // one commit stale: twice the longest + 2): a step there has a few thousand units, more than half the grid's waves, so no two waves share
     // one; with half as many, twice as long, every unit is shared by two waves and none idles.  C3 stand-in (contigs of 350 bins): 142 us
     // per step against 157; C2 stand-in (contigs of 150-220): 108 against 99)
-    const int seg_unit = ((seg_env == 1 || seg_env == 2 || seg_env == 4 || seg_env == 8 || seg_env == 16) && seg_env <= seg_max) ? seg_env
-                                                                                             : (h->single_sub ? (lc > 512 ? 16 : 4) : (TILE == 32 ? (lc > 512 ? 4 : 2) : 1));
-    static const int rep_env = getenv("GRAAL_STRICT_REP") ? atoi(getenv("GRAAL_STRICT_REP")) : 8;
-    const int rep_max = rep_env >= 16 ? 16 : (rep_env >= 8 ? 8 : (rep_env >= 4 ? 4 : (rep_env >= 2 ? 2 : 1)));
-    // units the grid wants before k_strict2 merges neighbouring entries into longer units (per wave: 6 at one sub-fragment per bin; with
-    // several, a unit's fragment pairs are nine evaluations each -- GRAAL_S2_TARGET_X4: the figure in quarters, for A/B)
-    static const int target_env = getenv("GRAAL_S2_TARGET_X4") ? atoi(getenv("GRAAL_S2_TARGET_X4")) : 0;
-    const unsigned long long target_x4 = target_env > 0 ? (unsigned long long)target_env : 24ull;
-    const unsigned long long target = std::max<unsigned long long>(1ull, target_x4 * 4ull * (unsigned long long)blocks / 4ull);
+    const int seg_unit = h->single_sub ? (lc > 512 ? 16 : 4) : (lc > 512 ? 4 : 2);
+    // units the grid wants before k_strict2 merges neighbouring entries into longer units: 6 per wave (24 per block)
+    const unsigned long long target = 24ull * (unsigned long long)blocks;
     // The list's worst case -- EVERY tile pair of the union listed -- is quadratic in the union's size (2e9 entries for 1e6 fragments in a few
     // contigs), while the interval cull lists the pairs within reach of each other under some candidate: orders of magnitude fewer.
     // It is sized ONCE per layout size, for the largest union n fragments and MAXK neighbours can form -- not for this step's longest
@@ -4780,13 +4736,10 @@ int launch_strict(Ctx* h, int fA, int K, int rank, int world, long long* d_q_out
     h->d_slist_n = (unsigned long long*)(h->d_scalars + SLIST_N);
     sx.list_cap = h->slist_cap;
     fa.norm_u = h->uniform_accu > 0 ? (float)(h->uniform_accu * h->uniform_accu) / h->nfpb : -1.0f;
-    static const int s2_skip = getenv("GRAAL_S2_SKIP") ? atoi(getenv("GRAAL_S2_SKIP")) : 0;   // (diagnostics: wrong sums.  1 = no units, 2 = no queued contacts)
-    fa.skip = s2_skip;
     const int no_window = (sx.quirk && h->n_ubins > 0) ? 1 : 0;
     S2Args s2;
-    s2.uset = h->d_uset; s2.cls = h->d_cls; s2.cls_n = h->d_cls_n; s2.seg_unit = seg_unit; s2.rep_max = rep_max; s2.target = target;
-    static const int draw_env = getenv("GRAAL_STRICT_DRAW") ? atoi(getenv("GRAAL_STRICT_DRAW")) : 8;
-    s2.draw_min = draw_env > 0 ? draw_env : 8;
+    s2.uset = h->d_uset; s2.cls = h->d_cls; s2.cls_n = h->d_cls_n; s2.seg_unit = seg_unit; s2.target = target;
+    s2.rep_max = 8; s2.draw_min = 8;   // (once switches of closed experiments; k_strict2 still takes them as arguments)
     s2.next = reinterpret_cast<unsigned long long*>(h->d_cls_n + US_MAXPAIRS + (US_MAXPAIRS & 1));
     // k_strict2 behind k_gprep WITHOUT an event (S2Args::gp): a kernel behind an event of another stream starts ~11 us after the event
     // completes (tools/stamps_s2.py, C2 stand-in: k_gprep done 23 us, k_strict2 started 37; without any ordering -- GRAAL_DEBUG runs -- 26, as
@@ -4836,8 +4789,7 @@ int launch_flat(Ctx* h, int fA, const Neigh* nbp /* nullptr: the neighbours of t
     FinArgs fa;
     StrictArgs sx;
     strict_args(h, fa, sx);
-    static const int blocks_env = getenv("GRAAL_FLAT_BLOCKS") ? atoi(getenv("GRAAL_FLAT_BLOCKS")) : 0;
-    const int blocks = blocks_env > 0 ? std::min(blocks_env, FLAT_BLOCKS) : FLAT_BLOCKS;
+    const int blocks = FLAT_BLOCKS;
     Neigh nb;
     for (int k = 0; k < MAXK; k++) nb.fB[k] = nbp ? nbp->fB[k] : h->last_fB[k];
     h->rc_flat += 1;
@@ -4853,27 +4805,37 @@ int launch_flat(Ctx* h, int fA, const Neigh* nbp /* nullptr: the neighbours of t
 // rank's own scan found -- its shard's queued contacts -- only decides WHO prices those contacts, which are that rank's alone
 bool flat_allowed(const Ctx* h, int world)
 {
-    static const bool no_flat = getenv("GRAAL_NO_FLAT") != nullptr;
-    return !no_flat && (h->mode & GRAAL_MODE_STRICT) && !strict_dense_cfg() && (world == 1 || h->x_host != nullptr) && h->publish;
+    return !env().no_flat && (h->mode & GRAAL_MODE_STRICT) && !strict_dense_cfg() && (world == 1 || h->x_host != nullptr) && h->publish;
 }
 
 } // namespace
+
+// A kernel on stream `st` publishes to pinned host memory, its sequence number last (word[0]): spin on that word; every 2^20 spins ask the
+// stream -- one that has drained without the word will not write it; past the bound, or then, synchronise the stream and look once more.
+// GRAAL_OK: word[0] == want, and what was published in front of it may be read.  Otherwise the error is set (`missing`: the caller's words
+// for a stream that ended without the word) and the caller cleans up what it must.
+static int wait_word(Ctx* h, const long long* word, long long want, hipStream_t st, const char* missing)
+{
+    const volatile long long* p = word;
+    bool seen = false;
+    for (long long spin = 0; spin < 400000000ll; spin++) {
+        if (p[0] == want) { seen = true; break; }
+        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(st) != hipErrorNotReady) { seen = (p[0] == want); break; }
+        __builtin_ia32_pause();
+    }
+    if (!seen) {
+        CK(hipStreamSynchronize(st));
+        if (p[0] != want) return fail(h, GRAAL_E_HIP, missing);
+    }
+    __sync_synchronize();
+    return GRAAL_OK;
+}
 
 // statistics of the layout (k_stats ran earlier on the stream): publish + wait; res[0..15] on return
 static int wait_stats(Ctx* h, long long res[16])
 {
     volatile long long* p = h->h_stats;
-    bool seen = false;
-    for (long long spin = 0; spin < 400000000ll; spin++) {
-        if (p[0] == h->stats_seq) { seen = true; break; }
-        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(h->stream) != hipErrorNotReady) { seen = (p[0] == h->stats_seq); break; }
-        __builtin_ia32_pause();
-    }
-    if (!seen) {
-        CK(hipStreamSynchronize(h->stream));
-        if (p[0] != h->stats_seq) return fail(h, GRAAL_E_HIP, "the layout statistics were not published");
-    }
-    __sync_synchronize();
+    { const int rc = wait_word(h, h->h_stats, h->stats_seq, h->stream, "the layout statistics were not published"); if (rc) return rc; }
     for (int i = 0; i < 16; i++) res[i] = p[1 + i];
     return GRAAL_OK;
 }
@@ -4883,17 +4845,7 @@ static int wait_own(Ctx* h, long long* q, long long* bad)
 {
     if (!h->own_pending) { if (q) *q = 0; if (bad) *bad = 1; return GRAAL_OK; }   // (nothing out: unknown)
     volatile long long* p = h->h_own;
-    bool seen = false;
-    for (long long spin = 0; spin < 400000000ll; spin++) {
-        if (p[0] == h->own_seq) { seen = true; break; }
-        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(h->fstream) != hipErrorNotReady) { seen = (p[0] == h->own_seq); break; }
-        __builtin_ia32_pause();
-    }
-    if (!seen) {
-        CK(hipStreamSynchronize(h->fstream));
-        if (p[0] != h->own_seq) return fail(h, GRAAL_E_HIP, "the commit's own-pixel correction was not published");
-    }
-    __sync_synchronize();
+    { const int rc = wait_word(h, h->h_own, h->own_seq, h->fstream, "the commit's own-pixel correction was not published"); if (rc) return rc; }
     if (q) *q = p[1];
     if (bad) *bad = p[2];
     h->own_pending = false;
@@ -4963,6 +4915,14 @@ int graal_create(int device, graal_ctx** out)
     *out = nullptr;
     graal_ctx* h = new graal_ctx();
     *out = h; // returned even on failure so that graal_last_error works; caller destroys it
+    // the switches read once per HANDLE (tests set them between two engines of one process); the others are read once per process: env()
+    h->spin_ok = getenv("GRAAL_NO_TM_SPIN") == nullptr;
+    if (const char* e = getenv("GRAAL_TM_SPIN_TICKS")) h->tm_spin_ticks = strtoull(e, nullptr, 10);
+    if (const char* e = getenv("GRAAL_STRICT_GWAIT")) h->gwait_env = atoi(e) != 0;
+    if (const char* e = getenv("GRAAL_GP_WAIT_TICKS")) h->gp_wait_ticks = std::max(1, atoi(e));
+    if (const char* e = getenv("GRAAL_GP_ACQUIRE")) h->gp_acquire = atoi(e);
+    if (const char* e = getenv("GRAAL_SCAN_PATH")) h->scan_path = std::min(2, std::max(0, atoi(e)));
+    if (const char* e = getenv("GRAAL_SLIST_SOFT_CAP")) h->slist_soft_cap = std::max<unsigned long long>(64ull, strtoull(e, nullptr, 10));
     h->device = device;
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
@@ -5007,7 +4967,6 @@ int graal_create(int device, graal_ctx** out)
     CK(hipMemset(h->d_sync, 0, 32 * sizeof(unsigned long long)));
     CK(hipMalloc(&h->d_flags, (size_t)MAX_SCAN_BLOCKS * FLAG_STRIDE * sizeof(unsigned)));
     CK(hipMemset(h->d_flags, 0, (size_t)MAX_SCAN_BLOCKS * FLAG_STRIDE * sizeof(unsigned)));
-    if (getenv("GRAAL_EVENT_EVERY")) h->event_every = std::max(1, atoi(getenv("GRAAL_EVENT_EVERY")));
     CK(hipMalloc(&h->d_qout, 3 * MAXK * N_OPS * sizeof(long long)));   // (fine sums, coarse sums, not-finite flags: hand_out)
     CK(hipMalloc(&h->tabs, MAXK * sizeof(NbTables)));
     CK(hipMalloc(&h->step_hdr, 2 * MAXK * sizeof(int)));
@@ -5044,13 +5003,6 @@ int graal_create(int device, graal_ctx** out)
 void graal_destroy(graal_ctx* h)
 {
     if (!h) return;
-    if (h->eval_timing && h->et_n[0]) {
-        const double n = (double)h->et_n[0], m = (double)std::max<long long>(h->et_n[1], 1);
-        fprintf(stderr, "graal eval timing: %lld synchronous evaluations, launches %.1f us each; %lld finished by k_tm (%.1f us from launch to result); "
-                        "%lld needed k_fin / k_strict_flat / k_strict2: %.1f us until k_tm said so, %.1f us to launch them, %.1f us until the result (%.1f us in all)\n",
-                h->et_n[0], h->et[0] / n, h->et_n[0] - h->et_n[1], h->et[4] / (double)std::max<long long>(h->et_n[0] - h->et_n[1], 1),
-                h->et_n[1], h->et[1] / m, h->et[2] / m, h->et[3] / m, h->et[5] / m);
-    }
     if (h->stream) {
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
@@ -5473,12 +5425,11 @@ static int begin_step_launch(graal_ctx* h, bool defer = false)
     const int n = h->n, bs = 256, nb = blocks_for(n, bs);
     const int cur = h->cur;
     SoaPtr s = h->soa[cur];
-    static const bool no_incr = getenv("GRAAL_NO_INCREMENTAL_RELABEL") != nullptr;
     // The statistics do not depend on the relabel.  After exactly one commit they are in pinned host memory already (the
     // commit kernel published them); when nothing changed, the statistics kernel publishes them itself.  Either way the host
     // reads them -- and goes on to draw the step's proposal -- while the relabel kernels launched here still run (everything
     // the host launches next is ordered after them: same stream, or the event recorded below).
-    const bool incr = h->ranks_valid && h->pending_commits == 1 && h->incr_ok && !no_incr;
+    const bool incr = h->ranks_valid && h->pending_commits == 1 && h->incr_ok && !env().no_incr;
     const bool early = h->ranks_valid && (h->pending_commits == 0 || incr);
     bool full_relabel = false;
     const bool from_apply = incr && h->stats_from_apply;
@@ -5623,6 +5574,17 @@ static int begin_step_collect(graal_ctx* h, int64_t stats[8], int32_t* max_id)
 
 int graal_relabel_contigs(graal_ctx* h, int32_t* max_id) { return graal_begin_step(h, nullptr, max_id); }
 
+// the full evaluation's accumulators (d_scalars[8], [9], [17], [FULL_BAD]) are zero at rest because k_full_pub clears them behind the sums
+// it publishes: a call that fails between its first kernel and that publication must not leave partial sums to the next one
+static void reset_acc(graal_ctx* h, hipStream_t fs)
+{
+    (void)hipStreamSynchronize(fs);
+    (void)hipGetLastError();
+    (void)hipMemset(h->d_scalars + 8, 0, 2 * sizeof(long long));
+    (void)hipMemset(h->d_scalars + 17, 0, sizeof(long long));
+    (void)hipMemset(h->d_scalars + FULL_BAD, 0, sizeof(long long));
+}
+
 // the full evaluation in two halves: the kernels (and the publication of the sums) on stream `fs`, and the wait for them.  A caller
 // that launches on another stream than the engine's orders it behind the relabel itself (graal_step, flag 8).
 static int full_launch(graal_ctx* h, hipStream_t fs)
@@ -5633,54 +5595,44 @@ static int full_launch(graal_ctx* h, hipStream_t fs)
     SoaPtr s = h->soa[h->cur];
     const bool quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) != 0;
     if (h->nnz) {
-        static const bool no_compact = getenv("GRAAL_FULL_NO_COMPACT") != nullptr;
         // (equal RF counts everywhere: the reference's trans-branch indexing picks the same count whatever the orientation, so
         // the compact records serve that mode too)
-        const bool compact = h->uniform_accu > 0 && !no_compact;
+        const bool compact = h->uniform_accu > 0 && !env().full_no_compact;
         k_subrec<<<blocks_for(h->n, 256), 256, 0, fs>>>(h->n, h->geo, h->stat_frag, h->d_sub_ids, h->sub_rec, compact ? h->sub_rec8 : nullptr, h->sub_lab16);
-        // 8 blocks of 256 threads per CU; every lane takes FULL_G groups of 4 contacts per iteration
-        static const int full_g = getenv("GRAAL_FULL_G") ? atoi(getenv("GRAAL_FULL_G")) : 2;
-        static const int full_bpc = getenv("GRAAL_FULL_BPC") ? atoi(getenv("GRAAL_FULL_BPC")) : 8;   // blocks per CU
-        const int FG = full_g == 1 ? 1 : (full_g == 4 ? 4 : 2);
+        // 8 blocks of 256 threads per CU; every lane takes FG groups of 4 contacts per iteration
+        constexpr int FG = 2;
         const long long groups = (h->nnz >> 2) + 1;
-        const int nb = (int)std::max<long long>(1, std::min<long long>((groups + 256 * FG - 1) / (256 * FG), 256 * full_bpc));
+        const int nb = (int)std::max<long long>(1, std::min<long long>((groups + 256 * FG - 1) / (256 * FG), 256 * 8));
 #define FULL_NNZ_ARGS reinterpret_cast<const int4*>(h->row), reinterpret_cast<const int4*>(h->col), reinterpret_cast<const int4*>(h->cnt), \
                       h->nnz, h->sub_rec, s.p[F_LCONTBP], h->nfpb, h->par, h->ln_lut_n, quirk ? 1 : 0, h->d_scalars + 8, h->d_scalars + FULL_BAD
         // labels in LDS (k_full_nnz_l): uniform RF counts, a list worth it, and 2 bytes per sub-fragment within 150 KB of LDS
-        static const bool no_lds = getenv("GRAAL_FULL_NO_LDS") != nullptr;
         const size_t lab_bytes = 2 * (((size_t)h->n_sub_total + 7) & ~(size_t)7);
-        if (compact && !no_lds && h->nnz >= 2000000 && lab_bytes <= 150 * 1024) {
+        if (compact && !env().full_no_lds && h->nnz >= 2000000 && lab_bytes <= 150 * 1024) {
             static bool attr_set = false;
             if (!attr_set) {
-                CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_full_nnz_l<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_full_nnz_l<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_full_nnz_l<FG>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
                 attr_set = true;
             }
             const int nbl = (int)std::max<long long>(1, std::min<long long>((groups + 1024 * FG - 1) / (1024 * FG), 256));
 #define FULL_NNZ_L_ARGS reinterpret_cast<const int4*>(h->row), reinterpret_cast<const int4*>(h->col), reinterpret_cast<const int4*>(h->cnt), \
                         h->nnz, h->sub_lab16, h->n_sub_total, h->sub_rec8, h->sub_rec, s.p[F_LCONTBP], h->nfpb, h->par, h->uniform_accu,        \
                         h->d_scalars + 8, h->d_scalars + FULL_BAD
-            if (FG == 2) k_full_nnz_l<2><<<nbl, 1024, lab_bytes, fs>>>(FULL_NNZ_L_ARGS);
-            else k_full_nnz_l<4><<<nbl, 1024, lab_bytes, fs>>>(FULL_NNZ_L_ARGS);
+            k_full_nnz_l<FG><<<nbl, 1024, lab_bytes, fs>>>(FULL_NNZ_L_ARGS);
 #undef FULL_NNZ_L_ARGS
         }
         else if (compact) {
 #define FULL_NNZ_U_ARGS reinterpret_cast<const int4*>(h->row), reinterpret_cast<const int4*>(h->col), reinterpret_cast<const int4*>(h->cnt), \
                         h->nnz, h->sub_rec8, h->sub_rec, s.p[F_LCONTBP], h->nfpb, h->par, h->uniform_accu, h->d_scalars + 8, h->d_scalars + FULL_BAD
-            if (FG == 1) k_full_nnz_u<1><<<nb, 256, 0, fs>>>(FULL_NNZ_U_ARGS);
-            else if (FG == 4) k_full_nnz_u<4><<<nb, 256, 0, fs>>>(FULL_NNZ_U_ARGS);
-            else k_full_nnz_u<2><<<nb, 256, 0, fs>>>(FULL_NNZ_U_ARGS);
+            k_full_nnz_u<FG><<<nb, 256, 0, fs>>>(FULL_NNZ_U_ARGS);
 #undef FULL_NNZ_U_ARGS
         }
-        else if (FG == 1) k_full_nnz<1><<<nb, 256, 0, fs>>>(FULL_NNZ_ARGS);
-        else if (FG == 4) k_full_nnz<4><<<nb, 256, 0, fs>>>(FULL_NNZ_ARGS);
-        else k_full_nnz<2><<<nb, 256, 0, fs>>>(FULL_NNZ_ARGS);
+        else k_full_nnz<FG><<<nb, 256, 0, fs>>>(FULL_NNZ_ARGS);
 #undef FULL_NNZ_ARGS
     }
     if (quirk && h->n_ubins) // T_all prices every pair of different bins with the plain trans value: add the indexing's difference
         k_quirk_mass<<<blocks_for((long long)h->n_ubins * h->n_bins, 256), 256, 0, fs>>>(h->n_ubins, h->d_ubins, h->n_bins, h->geo, h->stat_frag,
                                                                                              h->nfpb, h->par, h->d_scalars + 9, h->d_scalars + FULL_BAD);
-    static const int fmt_env = getenv("GRAAL_FULL_MASS_TILED") ? atoi(getenv("GRAAL_FULL_MASS_TILED")) : -1;   // (A/B: 0 = never, 1 = always)
+    const int fmt_env = env().full_mass_tiled;   // (tools/full_mass_check.py: 0 = never, 1 = always)
     const int lc_full = std::max(std::max(h->max_lcont, h->lcont_bound), 1);
     // (maps of a few thousand bins keep the kernel with one WAVE per fragment x: 3,500 bins are 55 tiles -- the C3 stand-in, which evaluates the
     // full likelihood every step, went from 237 to 522 us per step with the tiled kernel)
@@ -5709,45 +5661,16 @@ static int full_launch(graal_ctx* h, hipStream_t fs)
         h->full_rep_sharded = fw > 1;
         k_rep_full<<<blocks_for((long long)h->n_dup * h->n_bins, 256), 256, 0, fs>>>(R, fr, fw, h->d_scalars + 17, h->d_scalars + FULL_BAD);
     }
-    // the accumulators (d_scalars[8], [9], [17], [FULL_BAD]) are zero at rest because k_full_pub clears them behind the sums it
-    // publishes: a call that fails between its first kernel and that publication must not leave partial sums to the next one
-    auto reset_acc = [&]() {
-        (void)hipStreamSynchronize(fs);
-        (void)hipGetLastError();
-        (void)hipMemset(h->d_scalars + 8, 0, 2 * sizeof(long long));
-        (void)hipMemset(h->d_scalars + 17, 0, sizeof(long long));
-        (void)hipMemset(h->d_scalars + FULL_BAD, 0, sizeof(long long));
-    };
-    { const hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { reset_acc(); h->err = hipGetErrorString(e_); return GRAAL_E_HIP; } }
+    { const hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { reset_acc(h, fs); h->err = hipGetErrorString(e_); return GRAAL_E_HIP; } }
     h->full_seq += 1;
     k_full_pub<<<1, 64, 0, fs>>>(h->d_scalars, h->h_full, h->full_seq);
-    { const hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { reset_acc(); h->err = hipGetErrorString(e_); return GRAAL_E_HIP; } }
+    { const hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { reset_acc(h, fs); h->err = hipGetErrorString(e_); return GRAAL_E_HIP; } }
     return GRAAL_OK;
 }
 
 static int full_collect(graal_ctx* h, hipStream_t fs, int64_t q_out[2])
 {
-    auto reset_acc = [&]() {
-        (void)hipStreamSynchronize(fs);
-        (void)hipGetLastError();
-        (void)hipMemset(h->d_scalars + 8, 0, 2 * sizeof(long long));
-        (void)hipMemset(h->d_scalars + 17, 0, sizeof(long long));
-        (void)hipMemset(h->d_scalars + FULL_BAD, 0, sizeof(long long));
-    };
-    {
-        volatile long long* p = h->h_full;
-        bool seen = false;
-        for (long long spin = 0; spin < 400000000ll; spin++) {
-            if (p[0] == h->full_seq) { seen = true; break; }
-            if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(fs) != hipErrorNotReady) { seen = (p[0] == h->full_seq); break; }
-            __builtin_ia32_pause();
-        }
-        if (!seen) {
-            const hipError_t e_ = hipStreamSynchronize(fs);
-            if (e_ != hipSuccess || p[0] != h->full_seq) { reset_acc(); return fail(h, GRAAL_E_HIP, "the full evaluation did not publish its sums"); }
-        }
-        __sync_synchronize();
-    }
+    { const int rc = wait_word(h, h->h_full, h->full_seq, fs, "the full evaluation did not publish its sums"); if (rc) { reset_acc(h, fs); return rc; } }
     const long long res[2] = {h->h_full[1], h->h_full[2]};
     const long long bad = h->h_full[3], rep_q = h->has_rep ? h->h_full[4] : 0;
     // (q[0]: what the callers add up over the ranks -- the contacts of this rank's shard and, when the repeated bins' pixels were dealt to the
@@ -5872,10 +5795,9 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
 
     ta.geo = h->geo; ta.link = h->link; ta.cbase = h->cbase; ta.mates = h->mates; ta.tabs = h->tabs; ta.step_hdr = h->step_hdr;
     ta.perm = h->perm; ta.reach_bp = reach_bp(h); ta.tm_done = h->tm_done;
-    static const bool no_finisher = getenv("GRAAL_NO_FINISHER") != nullptr; // always finish with k_fin (diagnostics)
     ta.flags = h->d_flags;
     ta.sync = h->d_sync; ta.n_scan_blocks = producer_grid(h, K);
-    ta.done = scan_done_counter() ? h->d_done : nullptr; ta.n_done = scan_done_n();
+    ta.done = scan_done_counter() ? h->d_done : nullptr; ta.n_done = N_DONE;
     for (int c = 0; c < N_DONE; c++) ta.done_target[c] = c < ta.n_done ? h->scan_done_total[c] + (unsigned long long)((producer_grid(h, K) - c + ta.n_done - 1) / ta.n_done) : 0ull;
     // (late stage -- a few long contigs hold nearly every fragment: nearly every step needs k_fin anyway, so it is launched
     // right behind the scan instead of after k_tm's verdict has made the round trip through the host, ~10 us per step)
@@ -5883,7 +5805,7 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
     // (one rank only: in this flow k_tm prices no small sets itself, and the ranks would have to enter and leave it together -- a rank whose
     // finisher is off, or whose running mean differs, must not deal a small set's pairs one way while its peers deal them the other.  With
     // several ranks k_strict_flat goes out on k_tm's word instead: one host round trip later)
-    const bool mid = flat_allowed(h, world) && world == 1 && h->mid_run && !late_stage && h->finisher_ok && !no_finisher;
+    const bool mid = flat_allowed(h, world) && world == 1 && h->mid_run && !late_stage && h->finisher_ok;
     h->flat_tried = false;
     // (with k_strict_flat behind the scan k_tm prices nothing itself: one thread per pair walking the classes is 30-50 us for a set
     // of 20 fragments, and the flat kernel would wait for it)
@@ -5891,9 +5813,9 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
     // (a long scan -- millions of contacts: the copy is over before the scan is.  A short one -- the C2 / C3 stand-ins -- is complete before the
     // tables are: the copy would stand in front of the contacts, two round trips for a handful of them; C2 stand-in 130 -> 137 us per step)
     // The indexed pass is always a short scan: no copy.  (GRAAL_STAGE_TABLES = 0 / 1 overrides, for A/B runs)
-    static const int stage_env = getenv("GRAAL_STAGE_TABLES") ? atoi(getenv("GRAAL_STAGE_TABLES")) : -1;
+    const int stage_env = env().stage_tables;
     ta.stage_tables = stage_env >= 0 ? (stage_env ? 1 : 0) : ((!h->step_indexed && h->nnz >= 4000000) ? 1 : 0);
-    ta.host_res = (h->publish && (world == 1 || h->x_host) && !no_finisher && h->finisher_ok && !h->has_rep && !late_stage && !mid && !(strict && strict_dense_cfg())) ? h->res_dev : nullptr;
+    ta.host_res = (h->publish && (world == 1 || h->x_host) && h->finisher_ok && !h->has_rep && !late_stage && !mid && !(strict && strict_dense_cfg())) ? h->res_dev : nullptr;
     ta.wait_ticks = fin_wait_ticks(h);
     ta.counters = (unsigned long long*)(h->d_scalars + 10); ta.queue = h->queue; ta.cnt = h->cnt; ta.multi = h->single_sub ? 0 : 1; ta.stat = h->stat_frag;
     ta.lcontbp = h->soa[h->cur].p[F_LCONTBP]; ta.acc = h->d_acc; ta.nfpb = h->nfpb; ta.par = h->par;
@@ -6010,9 +5932,6 @@ static int eval_sync(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int
         h->res_host = h->x_host + off;
         h->res_dev = h->x_dev + off;
     } else { h->res_host = h->res_dev = h->h_res; }
-    auto now_us = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = h->eval_timing ? now_us() : 0.0;
-    double t1 = 0.0, t2 = 0.0, t3 = 0.0;
     h->publish = true;
     h->step_needed_fin = false;
     h->step_needed_geom = false;
@@ -6021,7 +5940,6 @@ static int eval_sync(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int
     h->publish = false;
     if (rc) return rc;
     const bool launched_mid = h->flat_tried;   // (k_strict_flat went out with the step: it reports whether it was needed)
-    if (h->eval_timing) t1 = now_us();
     volatile long long* res = h->res_host;
     bool seen = false;
     for (long long spin = 0; spin < 200000000ll; spin++) {
@@ -6031,7 +5949,6 @@ static int eval_sync(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int
             if ((v & GAVE_UP) && ++h->gave_up >= 3) h->finisher_ok = false;
             if (v & NEED_GEOM) h->step_needed_geom = true;
             res[0] = 0;
-            if (h->eval_timing) t2 = now_us();
             h->publish = true;
             h->step_needed_fin = true;
             h->rc_need_fin += 1;
@@ -6043,7 +5960,6 @@ static int eval_sync(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int
                                                    : launch_fin(h, K, rank, world, (long long*)h->d_qout, true, h->stream);
             h->publish = false;
             if (rc) return rc;
-            if (h->eval_timing) t3 = now_us();
             continue;
         }
         if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(h->stream) != hipErrorNotReady && hipStreamQuery(h->aux) != hipErrorNotReady) {
@@ -6068,12 +5984,6 @@ static int eval_sync(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int
         h->need_ema = 0.9 * h->need_ema + (needed ? 0.1 : 0.0);
         if (!h->mid_run && h->need_ema > 0.5) h->mid_run = true;
         else if (h->mid_run && h->need_ema < 0.25) h->mid_run = false;
-    }
-    if (h->eval_timing) {
-        const double t4 = now_us();
-        h->et_n[0] += 1; h->et[0] += t1 - t0;
-        if (t2 > 0.0) { h->et_n[1] += 1; h->et[1] += t2 - t1; h->et[2] += t3 - t2; h->et[3] += t4 - t3; h->et[5] += t4 - t0; }
-        else h->et[4] += t4 - t1;
     }
     const unsigned long long why = res[0] == -want ? (unsigned long long)res[X_WHY] : 0ull;
     // (a step's unit list overflowed its soft cap -- launch_strict -- and can still grow: one rank only, see there)
@@ -6314,17 +6224,7 @@ int graal_genome_distance(graal_ctx* h, int64_t* half_units)
     k_dist<<<blocks_for(h->n, 256), 256, 0, h->stream>>>(h->soa[h->cur], h->n, h->d_dref, h->d_dist, h->h_dist, h->dist_seq);
     CK(hipGetLastError());
     volatile long long* p = h->h_dist;
-    bool seen = false;
-    for (long long spin = 0; spin < 400000000ll; spin++) {
-        if (p[0] == h->dist_seq) { seen = true; break; }
-        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(h->stream) != hipErrorNotReady) { seen = (p[0] == h->dist_seq); break; }
-        __builtin_ia32_pause();
-    }
-    if (!seen) {
-        CK(hipStreamSynchronize(h->stream));
-        if (p[0] != h->dist_seq) return fail(h, GRAAL_E_HIP, "k_dist did not publish the genome distance");
-    }
-    __sync_synchronize();
+    { const int rc = wait_word(h, h->h_dist, h->dist_seq, h->stream, "k_dist did not publish the genome distance"); if (rc) return rc; }
     *half_units = p[1];
     return GRAAL_OK;
 }
@@ -6381,8 +6281,7 @@ int graal_apply_move(graal_ctx* h, int32_t fA, int32_t fB, int32_t op, int32_t m
     h->stats_seq += 1;
     // (one fragment per thread up to 256 blocks: the kernel is a dependent chain -- records of fA / fB, the fragment's own 13
     // words, the stores -- and no longer pays atomics per block, so more, shorter blocks win: 12.4 -> ~6 us at 50k fragments)
-    static const int apply_blocks_env = getenv("GRAAL_APPLY_BLOCKS") ? atoi(getenv("GRAAL_APPLY_BLOCKS")) : 256;
-    h->apply_blocks = std::min(blocks_for(h->n, 256), std::max(1, std::min(apply_blocks_env, 1024)));
+    h->apply_blocks = std::min(blocks_for(h->n, 256), 256);
     // (several ranks: a rank's own table covers its shard of the list only -- unless the caller handed in the whole one, graal_upload_own_obs:
     // then every rank computes the same correction and nothing has to be exchanged; with an RCCL communicator of several ranks a repair could
     // not be exchanged inside the step: not offered)

@@ -63,25 +63,6 @@ __device__ __forceinline__ double mm_exp(double t)
     return ldexp(q, (int)n);
 }
 
-#ifdef GRAAL_EXP_OCML_MATH   // (A/B build, tools/ab.sh: the device library's float-float powf internals, expf and log -- what the engine called until round 3)
-typedef float mm_v2f __attribute__((ext_vector_type(2)));
-extern "C" __device__ mm_v2f __ocmlpriv_epln_f32(float);
-extern "C" __device__ float __ocmlpriv_expep_f32(mm_v2f);
-__device__ __forceinline__ float mm_powf(float x, float y)
-{
-    const mm_v2f ln = __ocmlpriv_epln_f32(x);
-    const float yh = y * ln.y;
-    const float err = fmaf(y, ln.y, -yh);
-    const float t = fmaf(y, ln.x, err);
-    const float hi = yh + t;
-    const float lo = t - (hi - yh);
-    mm_v2f a; a.x = lo; a.y = hi;
-    return __ocmlpriv_expep_f32(a);
-}
-__device__ __forceinline__ float mm_powf_pos(float x, float y) { return mm_powf(x, y); }
-__device__ __forceinline__ float mm_expf(float t) { return expf(t); }
-__device__ __forceinline__ double mm_ln(float x) { return log((double)x); }
-#else
 // The special cases are resolved by selects behind the main computation -- no second implementation is inlined next to it (the
 // kernels that price contacts hold this code a dozen times over; with the device library's powf / log as fallbacks they grew
 // past the instruction cache and ran 1.5x slower than before).
@@ -126,4 +107,3 @@ __device__ __forceinline__ double mm_ln(float x)
     if (!ok) r = x == 0.0f ? -(double)__builtin_inff() : (x == __builtin_inff() ? (double)__builtin_inff() : (double)__builtin_nanf(""));
     return r;
 }
-#endif

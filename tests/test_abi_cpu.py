@@ -65,3 +65,23 @@ def test_environment_switches_are_documented():
     documented = set(re.findall(r"`(GRAAL_[A-Z0-9_]+)`", doc))
     assert used, "no switches found: the patterns of this test are out of date"
     assert used <= documented, sorted(used - documented)
+
+
+def test_documented_environment_switches_are_read():
+    """The other direction: every variable in the first column of a row of INTEGRATION.md section 5's table is read by the library, the
+    host package or bench.py -- a switch that leaves the sources leaves the table with it."""
+    import glob
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    used = set()
+    for f in glob.glob(os.path.join(root, "graal_amd", "csrc", "*")) + glob.glob(os.path.join(root, "graal_amd", "*.py")) + [os.path.join(root, "bench.py")]:
+        if os.path.isfile(f) and not f.endswith(".so"):
+            txt = open(f, errors="ignore").read()
+            used |= set(re.findall(r'getenv\(\s*"(GRAAL_[A-Z0-9_]+)"', txt))
+            used |= set(re.findall(r'environ(?:\.get|\.pop)?[\[(]\s*"(GRAAL_[A-Z0-9_]+)"', txt))
+    rows = [l for l in open(os.path.join(root, "INTEGRATION.md")).read().splitlines() if l.startswith("| `GRAAL_")]
+    assert len(rows) >= 20, "section 5's table was not found: the pattern of this test is out of date"
+    documented = set()
+    for l in rows:
+        documented |= set(re.findall(r"`(GRAAL_[A-Z0-9_]+)`", l.split("|")[1]))
+    assert documented <= used, sorted(documented - used)
