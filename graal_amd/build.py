@@ -5,6 +5,7 @@
   for the host with g++ so that the CPU test-suite can check it against the oracle without a GPU.
   It contains no likelihood code and is never loaded by the product path.
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -28,12 +29,13 @@ def hipcc_path():
     return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
+def _sources(main):
+    """The main source first, then everything it can include: a new header cannot leave a stale library behind."""
+    return [os.path.join(CSRC, main)] + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "graal_hip.h")]
+
+
 def build_hip(force=False, verbose=False):
-    srcs = [os.path.join(CSRC, "graal_hip.hip"), os.path.join(CSRC, "frag_ops.h"), os.path.join(CSRC, "host_step.h"),
-            os.path.join(CSRC, "model_math.h"), os.path.join(CSRC, "strict_sets.h"), os.path.join(CSRC, "strict2.h"),
-            os.path.join(CSRC, "host_fit.h"), os.path.join(CSRC, "simulate.h"), os.path.join(CSRC, "junctions.h"), os.path.join(CSRC, "links.h"), os.path.join(CSRC, "edit.h"),
-            os.path.join(CSRC, "insert.h"), os.path.join(CSRC, "flips.h"), os.path.join(CSRC, "score_common.h"), os.path.join(CSRC, "scan_rows.h"),
-            os.path.join(ROOT, "include", "graal_hip.h")]
+    srcs = _sources("graal_hip.hip")
     if force or _newer(HIP_LIB, srcs):
         cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off",  # float32 model arithmetic exactly as written (parity with the oracle)
@@ -45,8 +47,7 @@ def build_hip(force=False, verbose=False):
 
 
 def build_hostcheck(force=False):
-    srcs = [os.path.join(CSRC, "host_check.cpp"), os.path.join(CSRC, "frag_ops.h"), os.path.join(CSRC, "strict_sets.h"),
-            os.path.join(CSRC, "scan_rows.h")]
+    srcs = _sources("host_check.cpp")
     if force or _newer(HOSTCHECK_LIB, srcs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", HOSTCHECK_LIB, srcs[0]])
     return HOSTCHECK_LIB

@@ -34,6 +34,7 @@
 #include "strict_sets.h"
 #include "model_math.h"
 #include "scan_rows.h"
+#include "step_plan.h"
 
 using namespace graal;
 
@@ -2411,7 +2412,7 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
     __shared__ PieceKey s_qkeys[MAXK];
     __shared__ unsigned s_qlive;
     // (dynamic LDS, requested only when a finisher can exist: a k_tm block that k_fin's resident blocks wait for must stay small
-    // enough to be placed next to them -- tm_fin_dyn_lds / fin_blocks_no_wait)
+    // enough to be placed next to them -- tm_fin_dyn_lds / plan_fin_no_wait)
     extern __shared__ long long s_tm_dyn[];
     PTask* const s_ptl = reinterpret_cast<PTask*>(s_tm_dyn);
     unsigned short* const s_prl = reinterpret_cast<unsigned short*>(s_ptl + MAXK * PT_CAP);
@@ -4330,7 +4331,7 @@ struct Env {
     int scan_threads = env_int(getenv("GRAAL_SCAN_THREADS"), 0);            // 0       > 0: threads per block of k_scan (else by the list's size)
     int scan_g = env_int(getenv("GRAAL_SCAN_G"), 4);                        // 4       2, 4 or 8 (anything else: 4)
     bool scan_done_counter = !getenv("GRAAL_SCAN_DONE") || strcmp(getenv("GRAAL_SCAN_DONE"), "flags") != 0;   // on   "flags": per-block flags
-    int scan_blocks = env_int(getenv("GRAAL_SCAN_BLOCKS"), scan_groups() == 8 ? 256 - 8 : 256 * 2 - 16);     // (see scan_grid)   as given
+    int scan_blocks = env_int(getenv("GRAAL_SCAN_BLOCKS"), scan_groups() == 8 ? 256 - 8 : 256 * 2 - 16);     // (see plan_producer)   as given
     int scan_fold_bits = getenv("GRAAL_SCAN_FOLD_BITS") ? std::min(18, std::max(5, atoi(getenv("GRAAL_SCAN_FOLD_BITS")))) : 0;   // 0 (by size)   5..18
     long long scan_rows_r = getenv("GRAAL_SCAN_ROWS_R") ? std::max(1, atoi(getenv("GRAAL_SCAN_ROWS_R"))) : 16;                  // 16   >= 1
     int fin_blocks = env_int(getenv("GRAAL_FIN_BLOCKS"), 0);                // 0       > 0: k_fin's grid
@@ -4342,6 +4343,11 @@ struct Env {
     int full_mass_tiled = env_int(getenv("GRAAL_FULL_MASS_TILED"), -1);     // -1      0 = never k_full_mass_t, 1 = always
     int stage_tables = env_int(getenv("GRAAL_STAGE_TABLES"), -1);           // -1      0 / 1: k_tm copies its tables never / always (else by the scan's length)
     int scan_groups() const { return (scan_g == 8 || scan_g == 2) ? scan_g : 4; }
+    PlanEnv plan() const   // the switches that shape a launch (step_plan.h)
+    {
+        return {scan_threads, scan_groups(), scan_blocks, scan_fold_bits, scan_rows_r, fin_blocks, strict_dense, no_flat, full_no_compact, full_no_lds,
+                full_mass_tiled, stage_tables};
+    }
 };
 const Env& env() { static const Env e; return e; }
 
@@ -4450,97 +4456,56 @@ constexpr int MAX_SCAN_BLOCKS = 4096;
 constexpr int FULL_BAD = 27; // d_scalars[FULL_BAD]: a term of the last full evaluation was not finite / out of range
 constexpr int SLIST_N = 28;  // d_scalars[SLIST_N]: length of k_strict2's unit list (zero at rest)
 constexpr int RELABEL_FLAG = 30; // d_scalars[RELABEL_FLAG]: sequence number of the last relabel k_scan has announced as complete (k_tm spins on it)
-constexpr int SCAN_LDS_MAX = 48 * 1024; // affected bitmap of k_scan: 1 bit per contact-list id up to 393,216 ids, folded beyond (launch_scan)
+static_assert(PLAN_MAXK == MAXK && PLAN_N_DONE == N_DONE && PLAN_STRICT_INLINE_M == STRICT_INLINE_M, "step_plan.h against the kernels' constants");
 
-// threads per block of the streaming pass: 1024 (two blocks per CU) for the lists it is built for; a list of a few hundred
-// thousand contacts (a yeast-sized genome at 3 sub-fragments per bin) would fill only a handful of such blocks, each marking
-// the whole affected set in its prologue: 256-thread blocks there (C2 stand-in: 177 -> 165 us per step)
-int scan_threads_cfg(const Ctx* h)
+size_t fin_dyn_lds(int K) { return (size_t)K * (S_PER_K * sizeof(long long) + (MAX_TASKS + 1) * sizeof(int)); }   // K = 10: 37 KB
+
+// ---- the facts a step's plan reads (step_plan.h): the switches and the kernels' figures once per process, the handle's as they stand
+const KernelFigures& kernel_figures()
 {
-    const int v = env().scan_threads;
-    return v > 0 ? v : (h->nnz < 2000000 ? 256 : 1024);
+    static const KernelFigures kf = [] {
+        KernelFigures k;   // (what the runtime does not report keeps its default)
+        hipFuncAttributes a;
+        if (hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_tm)) == hipSuccess) { if (a.sharedSizeBytes) k.lds_tm = a.sharedSizeBytes; if (a.numRegs > 0) k.regs_tm = a.numRegs; }
+        if (hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_fin)) == hipSuccess) { if (a.sharedSizeBytes) k.lds_fin = a.sharedSizeBytes; if (a.numRegs > 0) k.regs_fin = a.numRegs; }
+        k.fin_dyn_lds_per_k = fin_dyn_lds(1);
+        return k;
+    }();
+    return kf;
 }
 
-int scan_groups_cfg() { return env().scan_groups(); }
-
-// How k_tm's finishing block learns that the scan is complete.  Default: every scan block adds itself to one counter with a
-// fire-and-forget atomic and the finisher polls that one word.  GRAAL_SCAN_DONE=flags: one flag line per block, all 496 of
-// them polled -- measured 1.5 us slower per step (each polling round is 8 uncached loads per lane behind the scan's own
-// stream in the memory queues: scan complete -> seen took ~7 us).
-bool scan_done_counter() { return env().scan_done_counter; }
-
-int scan_grid(const Ctx* h)
+StepFacts step_facts(const Ctx* h, int K, int world, bool ev = false)
 {
-    // two 1024-thread blocks per CU fill the 256 CUs; 16 fewer leave room for k_tm's blocks, which run at the same time (a
-    // CU that hosts one of them takes only one scan block, and a scan block that has to wait for a slot ends 8 us late)
-    const int scan_blocks = env().scan_blocks;   // (unset: 496, or 248 with 8 groups per lane)
-    const long long groups = (h->nnz >> 2) + 1;
-    const long long per_block = (long long)scan_groups_cfg() * scan_threads_cfg(h); // groups one block takes per iteration
-    return (int)std::max<long long>(1, std::min<long long>((groups + per_block - 1) / per_block, scan_blocks));
+    StepFacts f;
+    f.n = h->n; f.n_sub_total = h->n_sub_total; f.nnz = h->nnz; f.single_sub = h->single_sub;
+    f.n_contigs = h->n_contigs; f.max_lcont = h->max_lcont; f.lcont_bound = h->lcont_bound;
+    f.has_rep = h->has_rep; f.has_ubins = h->n_ubins > 0; f.uniform_accu = h->uniform_accu;
+    f.strict = (h->mode & GRAAL_MODE_STRICT) != 0; f.quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) != 0;
+    f.K = K; f.world = world; f.exchange = h->x_host != nullptr; f.publish = h->publish; f.ev = ev;
+    f.finisher_ok = h->finisher_ok; f.spin_ok = h->spin_ok; f.gwait_env = h->gwait_env; f.mid_run = h->mid_run;
+    f.has_rowptr = h->rowptr != nullptr; f.longest_row = h->longest_row;
+    f.forced_producer = h->repeat_producer ? h->repeat_producer : h->scan_path;   // (a step repeated behind events keeps the producer it had)
+    f.slist_soft_cap = h->slist_soft_cap; f.slist_floor = h->slist_floor; f.slist_cap = h->slist_cap;
+    f.env = env().plan(); f.kf = kernel_figures();
+    return f;
 }
 
-// ---- which producer a step gets (k_scan: one pass over the list; k_scan_rows: the affected rows through the row index)
-// bitmap of the producers: bytes of LDS and the word mask (all ones: every id has its own bit)
-void scan_bitmap_cfg(const Ctx* h, size_t* shm_out, unsigned* wmask_out)
+// the streaming pass's plan whatever the step would choose (the timing replays)
+ProducerPlan streaming_plan(const Ctx* h, int K)
 {
-    // one bit per contact-list id while they fit the LDS budget (393,216 ids); beyond that the ids are folded onto 2^18 bits
-    // (ScanArgs::bm_wmask): with a' affected ids a fraction a' / 2^18 of the rows takes the second test for nothing and
-    // (a' / 2^18)^2 of the contacts is queued for nothing -- dropped by the consumers' membership test, results unchanged.
-    // GRAAL_SCAN_FOLD_BITS = b folds onto 2^b bits whatever the size (tests: b = 10 makes every other row a false positive)
-    const int fold_bits = env().scan_fold_bits;
-    size_t shm = (size_t)((h->n_sub_total + 31) / 32 + 2) * 4;
-    unsigned wmask = 0xffffffffu;
-    if (shm > (size_t)SCAN_LDS_MAX || fold_bits) {
-        const int b = fold_bits ? fold_bits : 18;
-        if ((size_t)1 << b < (size_t)h->n_sub_total) { wmask = (1u << (b - 5)) - 1u; shm = ((size_t)1 << (b - 5)) * 4; }
-    }
-    *shm_out = shm; *wmask_out = wmask;
+    StepFacts f = step_facts(h, K, 1);
+    f.forced_producer = 1;
+    return plan_producer(f);
 }
 
-// bound on the rows a step can affect: K + 1 contigs of at most the longest contig's fragments (max_lcont is one commit stale in
-// graal_step's flow; lcont_bound = 2 * max + 2 covers what one commit can do to it), every sub-fragment of a bin a row of its own
-long long rows_bound(const Ctx* h, int K)
+// the streaming pass (see k_scan) or, for a step that goes through the row index, k_scan_rows, as the plan says; dry = timing replay of the
+// streaming pass that counts relevant contacts but queues nothing
+int launch_scan(Ctx* h, const ProducerPlan& pp, int fA, const Neigh& nb, int K, int max_id, int dry, hipStream_t st, bool finisher_reads = true)
 {
-    return scan_rows_bound(K, std::max(std::max(h->max_lcont, h->lcont_bound), 1), h->single_sub);
-}
-
-// 0: the step cannot go through the row index; else why not is in *why (static text)
-bool rows_possible(const Ctx* h, int K, const char** why)
-{
-    size_t shm; unsigned wmask;
-    scan_bitmap_cfg(h, &shm, &wmask);
-    if (!h->rowptr) { *why = "the contact list has no row index (it was not uploaded sorted by row)"; return false; }
-    if (wmask != 0xffffffffu) { *why = "the affected bitmap is folded (more ids than LDS bits): no indexed pass"; return false; }
-    if (rows_bound(h, K) > (long long)ROWS_CAP) { *why = "the contigs are too long for the indexed pass (more affected rows than its list holds)"; return false; }
-    return true;
-}
-
-// The switch.  Indexed iff possible and the contacts the pass can visit at worst, B = rows_bound x longest row, are at most nnz / R.
-// R = 16 by default (GRAAL_SCAN_ROWS_R): the indexed pass has at most 256 waves x 8 loads in flight, the streaming pass the whole chip, so
-// per contact visited it is taken to be an order of magnitude slower; B * 16 <= nnz keeps its worst case below the stream's time
-// (reasoned, with the measured points there).  Per step, stateless; ranks may choose for themselves.
-bool scan_use_rows(const Ctx* h, int K)
-{
-    const char* why = nullptr;
-    if (!rows_possible(h, K, &why)) return false;
-    return scan_rows_wins(rows_bound(h, K), h->longest_row, h->nnz, env().scan_rows_r);
-}
-
-// grid of the indexed pass: a wave per row of the bound, four waves per block, a few dozen blocks at most (every block pays the
-// prologue and the listing of the bitmap; beyond 64 blocks the rows go round)
-int rows_grid(const Ctx* h, int K) { return (int)std::max<long long>(1, std::min<long long>((rows_bound(h, K) + 3) / 4, 64)); }
-
-// blocks of the producer the evaluation being launched uses (the completion targets of k_tm's finishing block)
-int producer_grid(const Ctx* h, int K) { return h->step_indexed ? rows_grid(h, K) : scan_grid(h); }
-
-// the streaming pass (see k_scan) or, for a step that goes through the row index, k_scan_rows; dry = timing replay of the streaming pass
-// that counts relevant contacts but queues nothing
-int launch_scan(Ctx* h, int fA, const Neigh& nb, int K, int max_id, int dry, hipStream_t st, bool finisher_reads = true)
-{
-    const bool rows = !dry && h->step_indexed;
-    const int nbk = rows ? rows_grid(h, K) : scan_grid(h), scan_threads = scan_threads_cfg(h);
-    size_t shm; unsigned wmask;
-    scan_bitmap_cfg(h, &shm, &wmask);
+    const bool rows = pp.indexed;
+    const int nbk = pp.grid, scan_threads = pp.threads;
+    const size_t shm = pp.bitmap_bytes;
+    const unsigned wmask = pp.wmask;
     ScanArgs sa;
     sa.geo = h->geo; sa.link = h->link; sa.mates = h->mates; sa.cnt = h->cnt;
     sa.cbase = h->cbase; sa.perm = h->perm; sa.sub_ids = h->d_sub_ids;
@@ -4554,18 +4519,18 @@ int launch_scan(Ctx* h, int fA, const Neigh& nb, int K, int max_id, int dry, hip
     sa.nc = h->d_scalars + NC_WORD;
     sa.relabel_flag = (unsigned long long*)(h->d_scalars + RELABEL_FLAG);
     sa.relabel_seq = dry ? 0ull : h->scan_relabel_seq;
-    sa.done = (scan_done_counter() && !dry) ? h->d_done : nullptr;
+    sa.done = (env().scan_done_counter && !dry) ? h->d_done : nullptr;
     sa.n_done = N_DONE;
-    if (sa.done) for (int c = 0; c < sa.n_done; c++) h->scan_done_total[c] += (unsigned long long)((nbk - c + sa.n_done - 1) / sa.n_done);
+    if (sa.done) for (int c = 0; c < N_DONE; c++) h->scan_done_total[c] += (unsigned long long)pp.done_inc[c];
     if (nbk > MAX_SCAN_BLOCKS) return fail(h, GRAAL_E_ARG, "GRAAL_SCAN_BLOCKS too large");
     if (rows) {
         if (h->single_sub) k_scan_rows<true><<<nbk, ROWS_THREADS, shm, st>>>(sa, h->rowptr, h->col, h->n_sub_total, fA, nb, K);
         else k_scan_rows<false><<<nbk, ROWS_THREADS, shm, st>>>(sa, h->rowptr, h->col, h->n_sub_total, fA, nb, K);
         h->rc_indexed += 1;
-    } else if (scan_groups_cfg() == 8) {
+    } else if (pp.groups == 8) {
         if (h->single_sub) k_scan<true, 8><<<nbk, scan_threads, shm, st>>>(sa, fA, nb, K, max_id, dry);
         else k_scan<false, 8><<<nbk, scan_threads, shm, st>>>(sa, fA, nb, K, max_id, dry);
-    } else if (scan_groups_cfg() == 2) {
+    } else if (pp.groups == 2) {
         if (h->single_sub) k_scan<true, 2><<<nbk, scan_threads, shm, st>>>(sa, fA, nb, K, max_id, dry);
         else k_scan<false, 2><<<nbk, scan_threads, shm, st>>>(sa, fA, nb, K, max_id, dry);
     } else {
@@ -4576,52 +4541,10 @@ int launch_scan(Ctx* h, int fA, const Neigh& nb, int K, int max_id, int dry, hip
     return GRAAL_OK;
 }
 
-// how long a kernel waits for the scan's completion: a generous multiple of the time the streaming pass needs at 2 TB/s, plus launch slack
-int fin_wait_ticks(const Ctx* h) { return (int)std::min<long long>(100ll * 50 + (long long)(4.0 * 4.0 * (double)h->nnz / 2.0e12 * 1.0e8), 1ll << 30); }
-
 // dynamic LDS of k_tm's finishing block: the pricing records of all K tables (see k_tm)
 constexpr size_t tm_fin_dyn_lds()
 {
     return sizeof(PTask) * MAXK * PT_CAP + sizeof(unsigned short) * MAXK * N_PAIRS * PR_WORDS + sizeof(int) * MAXK + 16;
-}
-size_t fin_dyn_lds(int K) { return (size_t)K * (S_PER_K * sizeof(long long) + (MAX_TASKS + 1) * sizeof(int)); }   // K = 10: 37 KB
-
-// k_fin's blocks spin until k_tm has released the tables.  k_tm is launched first, on the other stream, but nothing guarantees
-// that its blocks are PLACED first: if k_fin's grid gets there first (a short scan) and fills every CU, k_tm's blocks have
-// nowhere to go, every block of k_fin spins to its bound and the step fails (seen: 2,048 blocks on the C2 stand-in -- registers;
-// and once in ~100 runs with 768 blocks after k_tm's LDS had grown -- LDS).  So the largest grid that may spin is the one that
-// leaves room for a block of k_tm on every CU, in registers AND in LDS, computed from the kernels' own attributes; a larger
-// grid is ordered behind k_tm by an event instead (launch_fin).
-int fin_blocks_no_wait(int K)
-{
-    static size_t lds_tm = 0, lds_fin = 0;
-    static int regs_tm = 0, regs_fin = 0;
-    if (lds_tm == 0) {
-        hipFuncAttributes a;
-        if (hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_tm)) == hipSuccess) { lds_tm = a.sharedSizeBytes; regs_tm = a.numRegs; }
-        if (hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_fin)) == hipSuccess) { lds_fin = a.sharedSizeBytes; regs_fin = a.numRegs; }
-        if (lds_tm == 0) lds_tm = 64 * 1024;
-        if (lds_fin == 0) lds_fin = 32 * 1024;
-        if (regs_tm <= 0) regs_tm = 128;
-        if (regs_fin <= 0) regs_fin = 128;
-    }
-    const size_t lds_cu = 160 * 1024;   // gfx950
-    const int regs_simd = 512;          // VGPRs per lane and SIMD; a 256-thread block puts one wave on each SIMD
-    const auto up8 = [](int r) { return (r + 7) & ~7; };
-    const int by_lds = (int)((lds_cu - std::min(lds_cu, lds_tm)) / (lds_fin + fin_dyn_lds(K)));
-    const int by_regs = (regs_simd - up8(regs_tm)) / up8(regs_fin);
-    return 256 * std::max(1, std::min(by_lds, by_regs));
-}
-
-int fin_blocks_cfg(const Ctx* h, int K)
-{
-    // short contigs leave k_fin a handful of contacts: a small grid keeps its launch and completion ticket cheap.  Contigs of a
-    // few hundred fragments: the largest grid that may spin for k_tm's tables (3 blocks per CU unless LDS allows fewer).
-    // Contigs of thousands of fragments: long dependent chains, 4 resident blocks per CU and fresh ones as they retire keep the
-    // VALUs busiest (2.8 -> 2.2 ms per step on C5's 7 contigs in round 1) -- that grid waits for k_tm through an event.
-    if (env().fin_blocks > 0) return env().fin_blocks;
-    if (h->max_lcont > 0 && h->max_lcont <= 16) return 32;
-    return h->max_lcont > 1024 ? 2048 : std::min(768, fin_blocks_no_wait(K));
 }
 
 // what every finishing kernel is handed alike: the step's buffers, and k_fin's options at their fixed values (skip, seg, upw: once
@@ -4636,22 +4559,18 @@ void fin_args(Ctx* h, FinArgs& fa)
 
 // left-over mass items, queued contacts, hand-out.  Short contigs leave it a handful of contacts: a small grid keeps its
 // launch and completion ticket cheap; long contigs get the whole chip.
-int launch_fin(Ctx* h, int K, int rank, int world, long long* d_q_out, bool publish, hipStream_t st)
+int launch_fin(Ctx* h, const FinPlan& fp, int K, int rank, int world, long long* d_q_out, bool publish, hipStream_t st)
 {
-    const int fin_blocks = fin_blocks_cfg(h, K);
-    if (fin_blocks > fin_blocks_no_wait(K)) { CK(hipEventRecord(h->ev_tm, h->aux)); CK(hipStreamWaitEvent(st, h->ev_tm, 0)); }   // (see fin_blocks_no_wait)
+    if (fp.event) { CK(hipEventRecord(h->ev_tm, h->aux)); CK(hipStreamWaitEvent(st, h->ev_tm, 0)); }   // (see plan_fin)
     FinArgs fa;
     fin_args(h, fa);
     fa.ln_tab = h->d_ln_tab; fa.lut_n = h->d_ln_tab ? h->ln_lut_n : 0;
     fa.norm_u = h->uniform_accu > 0 ? (float)(h->uniform_accu * h->uniform_accu) / h->nfpb : -1.0f;
     fa.wq = h->d_wq;
-    k_fin<<<fin_blocks, 256, fin_dyn_lds(K), st>>>(h->d_args + h->cur, fa, h->last_fA_launch, K, rank, world, d_q_out, publish ? h->res_dev : nullptr, h->seq);
+    k_fin<<<fp.grid, 256, fin_dyn_lds(K), st>>>(h->d_args + h->cur, fa, h->last_fA_launch, K, rank, world, d_q_out, publish ? h->res_dev : nullptr, h->seq);
     CK(hipGetLastError());
     return GRAAL_OK;
 }
-
-// GRAAL_STRICT_DENSE=1: the O(m^2) validation kernel (k_strict_dense) instead of k_strict_flat / k_gprep + k_strict2 (tests compare them)
-bool strict_dense_cfg() { return env().strict_dense; }
 
 // what the reference-arithmetic kernels are handed alike: the step's buffers (none of k_fin's options) and the layout's constants
 void strict_args(Ctx* h, FinArgs& fa, StrictArgs& sx)
@@ -4664,13 +4583,14 @@ void strict_args(Ctx* h, FinArgs& fa, StrictArgs& sx)
     sx.pad = 0;
 }
 
-// reference arithmetic: what k_tm left (sets larger than STRICT_INLINE_M, the queued contacts when there are many), hand-out
-int launch_strict(Ctx* h, int fA, int K, int rank, int world, long long* d_q_out, bool publish, hipStream_t st)
+// reference arithmetic: what k_tm left (sets larger than STRICT_INLINE_M, the queued contacts when there are many), hand-out.  Grid, tile,
+// entries, list sizes and the hand-off behind k_gprep are the plan's (plan_strict)
+int launch_strict(Ctx* h, const StrictPlan& sp, int fA, int K, int rank, int world, long long* d_q_out, bool publish, hipStream_t st)
 {
     FinArgs fa;
     StrictArgs sx;
     strict_args(h, fa, sx);
-    if (strict_dense_cfg()) {
+    if (sp.dense) {
         CK(hipEventRecord(h->ev_tm, h->aux));      // (k_tm is on the auxiliary stream, done or not: the event completes behind it)
         CK(hipStreamWaitEvent(st, h->ev_tm, 0));   // the tables are complete before the kernel starts: nobody spins for them
         k_strict_dense<<<1024, 256, 0, st>>>(fa, sx, fA, K, rank, world, d_q_out, publish ? h->res_dev : nullptr, h->seq);
@@ -4686,100 +4606,46 @@ int launch_strict(Ctx* h, int fA, int K, int rank, int world, long long* d_q_out
         CK(hipMemset(h->d_cls_n, 0, sizeof(int) * US_MAXPAIRS + 1024));
         CK(hipDeviceSynchronize());
     }
-    const int lc = std::max(std::max(h->max_lcont, h->lcont_bound), 1);
-    // (the GRID by the longest contig as last seen -- one commit stale: a performance choice; everything that must HOLD the step is sized by
-    // the bound `lc`, twice that + 2.  By the bound, contigs of 130-256 bins went to the 1,024-block grid behind an event instead of the
-    // 512-block one that follows k_gprep through its word)
-    const int lg = std::max(h->max_lcont, 1);
-    const int blocks = lg <= 64 ? 32 : (lg <= 256 ? 512 : 1024);
-    // fragments per tile: 64 (one per lane); with several sub-fragments per bin 32 -- the halves of a wave hold the same 32 fragments and
-    // take two fragments of the segment at a time (k_strict2): a unit is a 32 x 4 block instead of a 64 x 2 strip, which wastes fewer lanes
-    // on pieces of a few dozen bins and at the window's edge
-    const int TILE = h->single_sub ? 64 : 32;
-    // tiles of the union: at most K + 1 contigs, at most every fragment; + one partial tile per global piece
-    const unsigned long long nt = std::min<unsigned long long>((unsigned long long)(K + 1) * (unsigned long long)((lc + TILE - 1) / TILE),
-                                                               (unsigned long long)((h->n + TILE - 1) / TILE + K + 1)) + (unsigned long long)US_MAXP;
-    if (nt >= 65536ull) return fail(h, GRAAL_E_STATE, "reference arithmetic: more than 65,535 tiles in a step's union set");
-    // the unit list's entries: 4 fragments of the segment side (one sub-fragment per bin; k_strict2 merges up to 4 of them) or 2 (several);
-    // with entries of one fragment at one sub-fragment per bin the list's traffic cost the C4 stand-in 20 % of its run
-    // (one sub-fragment per bin: entries of 4 fragments -- of 16, a whole unit, once a contig may exceed 512 bins: a unit of 64 x 4 pairs is
-    // 13 us of set-up for ~1 us per class, and the kernel merges neighbouring entries only from 49,000 of them on; C4 stand-in, 4 cycles:
-    // 214 us per step against 224, the late stage unchanged)
-    // (tiles of 32: entries of TWO fragments, one per half of the wave -- FOUR once the longest contig may hold more than 512 bins (the bound,
-    // one commit stale: twice the longest + 2): a step there has a few thousand units, more than half the grid's waves, so no two waves share
-    // one; with half as many, twice as long, every unit is shared by two waves and none idles.  C3 stand-in (contigs of 350 bins): 142 us
-    // per step against 157; C2 stand-in (contigs of 150-220): 108 against 99)
-    const int seg_unit = h->single_sub ? (lc > 512 ? 16 : 4) : (lc > 512 ? 4 : 2);
-    // units the grid wants before k_strict2 merges neighbouring entries into longer units: 6 per wave (24 per block)
-    const unsigned long long target = 24ull * (unsigned long long)blocks;
-    // The list's worst case -- EVERY tile pair of the union listed -- is quadratic in the union's size (2e9 entries for 1e6 fragments in a few
-    // contigs), while the interval cull lists the pairs within reach of each other under some candidate: orders of magnitude fewer.
-    // It is sized ONCE per layout size, for the largest union n fragments and MAXK neighbours can form -- not for this step's longest
-    // contig: growing it with the contigs meant a hipFree / hipMalloc behind two stream synchronizes in the middle of a run, again and
-    // again while an assembly's contigs grow.  One rank: SLIST_SOFT_CAP entries at most to begin with; if a step's list overflows,
-    // k_gprep says so (counters[6] bit 1), the step ends as failed, eval_sync raises the floor and repeats it.  Several ranks: the worst
-    // case (a repeated step on ONE rank would leave the ranks out of step).
-    const unsigned long long nt_n = (unsigned long long)((h->n + TILE - 1) / TILE + MAXK + 1) + (unsigned long long)US_MAXP;
-    const unsigned long long worst = (nt_n * (nt_n + 1ull) / 2ull) * (unsigned long long)(TILE / seg_unit) + 64ull;
-    const unsigned long long SLIST_SOFT_CAP = h->slist_soft_cap;   // (GRAAL_SLIST_SOFT_CAP, read when the handle is created)
-    h->slist_worst = worst;
-    const unsigned long long need = (world == 1 && publish) ? std::min(worst, std::max(SLIST_SOFT_CAP, h->slist_floor)) : worst;
-    if (need > h->slist_cap) {
+    if (sp.refused) return fail(h, GRAAL_E_STATE, "reference arithmetic: more than 65,535 tiles in a step's union set");
+    // if a step's list overflows its soft cap, k_gprep says so (counters[6] bit 1), the step ends as failed, eval_sync raises the floor and repeats it
+    h->slist_worst = sp.worst;
+    if (sp.alloc) {
         CK(hipDeviceSynchronize());   // (rare: the first tiled step of a layout size, or a list that has just overflowed)
         if (h->d_slist) CK(hipFree(h->d_slist));
         h->d_slist = nullptr;
         h->slist_cap = 0;
-        const unsigned long long cap = std::max<unsigned long long>(need, 64ull);
-        CK(hipMalloc(&h->d_slist, cap * sizeof(unsigned long long)));
-        h->slist_cap = cap;
+        CK(hipMalloc(&h->d_slist, sp.alloc * sizeof(unsigned long long)));
+        h->slist_cap = sp.alloc;
     }
     h->d_slist_n = (unsigned long long*)(h->d_scalars + SLIST_N);
     sx.list_cap = h->slist_cap;
     fa.norm_u = h->uniform_accu > 0 ? (float)(h->uniform_accu * h->uniform_accu) / h->nfpb : -1.0f;
-    const int no_window = (sx.quirk && h->n_ubins > 0) ? 1 : 0;
     S2Args s2;
-    s2.uset = h->d_uset; s2.cls = h->d_cls; s2.cls_n = h->d_cls_n; s2.seg_unit = seg_unit; s2.target = target;
+    s2.uset = h->d_uset; s2.cls = h->d_cls; s2.cls_n = h->d_cls_n; s2.seg_unit = sp.seg_unit; s2.target = sp.target;
     s2.rep_max = 8; s2.draw_min = 8;   // (once switches of closed experiments; k_strict2 still takes them as arguments)
     s2.next = reinterpret_cast<unsigned long long*>(h->d_cls_n + US_MAXPAIRS + (US_MAXPAIRS & 1));
-    // k_strict2 behind k_gprep WITHOUT an event (S2Args::gp): a kernel behind an event of another stream starts ~11 us after the event
-    // completes (tools/stamps_s2.py, C2 stand-in: k_gprep done 23 us, k_strict2 started 37; without any ordering -- GRAAL_DEBUG runs -- 26, as
-    // soon as the host has submitted it).  k_gprep's results go out as device-scope stores, its last block stores the step's number, and
-    // k_strict2's blocks wait for that word.  Only a grid that leaves room for k_gprep's blocks on every CU may wait for them in the kernel
-    // (512 blocks: two per CU; cf. fin_blocks_no_wait), only one rank (a repeated step must not leave the ranks out of step), only while
-    // the engine's streams are known to run side by side (spin_ok).  (768 blocks -- three per CU, still room -- with the wait instead of 1,024
-    // behind the event: C3 / C4 stand-ins 214-221 / 238-243 us per step against 200-203 / 222-225.)
-    // (round 5 tried the word with the 1,024-block grids too: the wait ran out in every run -- C3 and C4 stand-ins -- and the engine went back to
-    // events, as the argument above predicts)
-    const bool gwait = h->gwait_env && publish && world == 1 && h->spin_ok && blocks <= 512;
-    s2.gp = gwait ? s2.next + 32 : nullptr;   // (ticket: 256 bytes behind the draw counter; the completion word 256 bytes behind the ticket: GP_DONE)
+    // k_strict2 behind k_gprep WITHOUT an event (S2Args::gp): k_gprep's results go out as device-scope stores, its last block stores the step's
+    // number, and k_strict2's blocks wait for that word
+    s2.gp = sp.gwait ? s2.next + 32 : nullptr;   // (ticket: 256 bytes behind the draw counter; the completion word 256 bytes behind the ticket: GP_DONE)
     s2.gp_seq = (unsigned long long)h->seq;
     s2.gp_wait_ticks = h->gp_wait_ticks;
     s2.gp_acquire = h->gp_acquire;
-    if (gwait) { h->spin_used = true; h->rc_gwait += 1; } else h->rc_gevent += 1;
-    const int cull_blocks = (int)std::min<unsigned long long>(1024ull, std::max<unsigned long long>(1ull, nt));
-    // k_gprep goes out on the auxiliary stream behind k_tm, under the scan.  (On the MAIN stream behind the scan and an event of k_tm, with
-    // k_strict2 following it in stream order, was measured for short scans: no gain -- the event in front of k_gprep costs what the one in
-    // front of k_strict2 did.)
-    k_gprep<<<GPREP_CLS_BLOCKS + cull_blocks, 256, 0, h->aux>>>(h->tabs, h->pstart, fA, K, rank, world, sx.reach_bp, no_window, sx.quirk,
-                                                                 seg_unit, TILE, h->d_slist, h->d_slist_n, h->slist_cap,
-                                                                 (unsigned long long*)(h->d_scalars + 10), s2);
+    if (sp.gwait) { h->spin_used = true; h->rc_gwait += 1; } else h->rc_gevent += 1;
+    // k_gprep goes out on the auxiliary stream behind k_tm, under the scan
+    k_gprep<<<GPREP_CLS_BLOCKS + sp.cull_blocks, 256, 0, h->aux>>>(h->tabs, h->pstart, fA, K, rank, world, sx.reach_bp, sp.no_window, sx.quirk,
+                                                                    sp.seg_unit, sp.tile, h->d_slist, h->d_slist_n, h->slist_cap,
+                                                                    (unsigned long long*)(h->d_scalars + 10), s2);
     CK(hipGetLastError());
-    // (k_strict2 on the auxiliary stream right behind k_gprep -- stream order instead of the event, next to the scan, its waves waiting for the
-    // scan's completion counters before the queued contacts -- was tried: it starts 9 us earlier (a kernel behind an event of another stream
-    // starts ~10 us late whether the event completes right in front of it or has long completed), but full runs gained nothing (C2 stand-in,
-    // 100 cycles: 130 us per step without, 134-146 with) and on the C4 stand-in the waiting waves once kept the scan off the CUs until their
-    // bound ran out.  Not kept.)
-    if (!gwait) {
+    if (!sp.gwait) {
         CK(hipEventRecord(h->ev_tm, h->aux));      // (behind k_tm and k_gprep: tables, classes and unit list complete -- nobody spins for them)
         CK(hipStreamWaitEvent(st, h->ev_tm, 0));
     }
-    hipStream_t ks = st;
     const size_t sslot = (size_t)(h->sring_calls % (long long)(h->sring.size() / 2));
-    if (h->ev_this_call) CK(hipEventRecord(h->sring[2 * sslot], ks));   // (behind the wait: the pair spans the kernel, not the scan in front of it)
-    if (h->single_sub) k_strict2<false><<<blocks, 256, 0, ks>>>(fa, sx, s2, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
-    else k_strict2<true><<<blocks, 256, 0, ks>>>(fa, sx, s2, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
+    if (h->ev_this_call) CK(hipEventRecord(h->sring[2 * sslot], st));   // (behind the wait: the pair spans the kernel, not the scan in front of it)
+    if (h->single_sub) k_strict2<false><<<sp.grid, 256, 0, st>>>(fa, sx, s2, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
+    else k_strict2<true><<<sp.grid, 256, 0, st>>>(fa, sx, s2, K, h->d_slist, h->d_slist_n, d_q_out, publish ? h->res_dev : nullptr, h->seq);
     CK(hipGetLastError());
-    if (h->ev_this_call) { CK(hipEventRecord(h->sring[2 * sslot + 1], ks)); h->sring_calls += 1; }
+    if (h->ev_this_call) { CK(hipEventRecord(h->sring[2 * sslot + 1], st)); h->sring_calls += 1; }
     return GRAAL_OK;
 }
 
@@ -4797,15 +4663,6 @@ int launch_flat(Ctx* h, int fA, const Neigh* nbp /* nullptr: the neighbours of t
     else k_strict_flat<true><<<blocks, 256, 0, st>>>(fa, sx, fA, nb, K, rank, world, d_q_out, publish ? h->res_dev : nullptr, h->seq);
     CK(hipGetLastError());
     return GRAAL_OK;
-}
-
-// may this evaluation use k_strict_flat?  With several ranks (an exchange attached) too: the flat and the tiled kernels deal the fragment
-// pairs to the ranks differently, so every rank must pick the same one -- and it does: the choice between them is the sets' geometry
-// (k_tm says at once that a set is beyond its own pricing, k_strict_flat that the pairs are too many), the same on every rank; what a
-// rank's own scan found -- its shard's queued contacts -- only decides WHO prices those contacts, which are that rank's alone
-bool flat_allowed(const Ctx* h, int world)
-{
-    return !env().no_flat && (h->mode & GRAAL_MODE_STRICT) && !strict_dense_cfg() && (world == 1 || h->x_host != nullptr) && h->publish;
 }
 
 } // namespace
@@ -5594,64 +5451,51 @@ static int full_launch(graal_ctx* h, hipStream_t fs)
     CK(hipSetDevice(h->device));
     SoaPtr s = h->soa[h->cur];
     const bool quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) != 0;
+    const FullPlan fp = plan_full(step_facts(h, 1, 1));   // which kernels and their grids (step_plan.h)
     if (h->nnz) {
         // (equal RF counts everywhere: the reference's trans-branch indexing picks the same count whatever the orientation, so
         // the compact records serve that mode too)
-        const bool compact = h->uniform_accu > 0 && !env().full_no_compact;
-        k_subrec<<<blocks_for(h->n, 256), 256, 0, fs>>>(h->n, h->geo, h->stat_frag, h->d_sub_ids, h->sub_rec, compact ? h->sub_rec8 : nullptr, h->sub_lab16);
-        // 8 blocks of 256 threads per CU; every lane takes FG groups of 4 contacts per iteration
-        constexpr int FG = 2;
-        const long long groups = (h->nnz >> 2) + 1;
-        const int nb = (int)std::max<long long>(1, std::min<long long>((groups + 256 * FG - 1) / (256 * FG), 256 * 8));
+        k_subrec<<<blocks_for(h->n, 256), 256, 0, fs>>>(h->n, h->geo, h->stat_frag, h->d_sub_ids, h->sub_rec, fp.compact ? h->sub_rec8 : nullptr, h->sub_lab16);
+        constexpr int FG = PLAN_FULL_G;
 #define FULL_NNZ_ARGS reinterpret_cast<const int4*>(h->row), reinterpret_cast<const int4*>(h->col), reinterpret_cast<const int4*>(h->cnt), \
                       h->nnz, h->sub_rec, s.p[F_LCONTBP], h->nfpb, h->par, h->ln_lut_n, quirk ? 1 : 0, h->d_scalars + 8, h->d_scalars + FULL_BAD
-        // labels in LDS (k_full_nnz_l): uniform RF counts, a list worth it, and 2 bytes per sub-fragment within 150 KB of LDS
-        const size_t lab_bytes = 2 * (((size_t)h->n_sub_total + 7) & ~(size_t)7);
-        if (compact && !env().full_no_lds && h->nnz >= 2000000 && lab_bytes <= 150 * 1024) {
+        if (fp.nnz_kernel == FULL_NNZ_L) {   // labels in LDS
             static bool attr_set = false;
             if (!attr_set) {
                 CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_full_nnz_l<FG>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
                 attr_set = true;
             }
-            const int nbl = (int)std::max<long long>(1, std::min<long long>((groups + 1024 * FG - 1) / (1024 * FG), 256));
 #define FULL_NNZ_L_ARGS reinterpret_cast<const int4*>(h->row), reinterpret_cast<const int4*>(h->col), reinterpret_cast<const int4*>(h->cnt), \
                         h->nnz, h->sub_lab16, h->n_sub_total, h->sub_rec8, h->sub_rec, s.p[F_LCONTBP], h->nfpb, h->par, h->uniform_accu,        \
                         h->d_scalars + 8, h->d_scalars + FULL_BAD
-            k_full_nnz_l<FG><<<nbl, 1024, lab_bytes, fs>>>(FULL_NNZ_L_ARGS);
+            k_full_nnz_l<FG><<<fp.nnz_grid, 1024, fp.lab_bytes, fs>>>(FULL_NNZ_L_ARGS);
 #undef FULL_NNZ_L_ARGS
         }
-        else if (compact) {
+        else if (fp.nnz_kernel == FULL_NNZ_U) {
 #define FULL_NNZ_U_ARGS reinterpret_cast<const int4*>(h->row), reinterpret_cast<const int4*>(h->col), reinterpret_cast<const int4*>(h->cnt), \
                         h->nnz, h->sub_rec8, h->sub_rec, s.p[F_LCONTBP], h->nfpb, h->par, h->uniform_accu, h->d_scalars + 8, h->d_scalars + FULL_BAD
-            k_full_nnz_u<FG><<<nb, 256, 0, fs>>>(FULL_NNZ_U_ARGS);
+            k_full_nnz_u<FG><<<fp.nnz_grid, 256, 0, fs>>>(FULL_NNZ_U_ARGS);
 #undef FULL_NNZ_U_ARGS
         }
-        else k_full_nnz<FG><<<nb, 256, 0, fs>>>(FULL_NNZ_ARGS);
+        else k_full_nnz<FG><<<fp.nnz_grid, 256, 0, fs>>>(FULL_NNZ_ARGS);
 #undef FULL_NNZ_ARGS
     }
     if (quirk && h->n_ubins) // T_all prices every pair of different bins with the plain trans value: add the indexing's difference
         k_quirk_mass<<<blocks_for((long long)h->n_ubins * h->n_bins, 256), 256, 0, fs>>>(h->n_ubins, h->d_ubins, h->n_bins, h->geo, h->stat_frag,
                                                                                              h->nfpb, h->par, h->d_scalars + 9, h->d_scalars + FULL_BAD);
-    const int fmt_env = env().full_mass_tiled;   // (tools/full_mass_check.py: 0 = never, 1 = always)
-    const int lc_full = std::max(std::max(h->max_lcont, h->lcont_bound), 1);
-    // (maps of a few thousand bins keep the kernel with one WAVE per fragment x: 3,500 bins are 55 tiles -- the C3 stand-in, which evaluates the
-    // full likelihood every step, went from 237 to 522 us per step with the tiled kernel)
-    if (fmt_env == 1 || (fmt_env != 0 && lc_full > 256 && h->n > 16384)) {
-        // long contigs: the tiled kernel; S waves share an x tile so that the grid has a few thousand waves whatever the contigs' length
-        const int n_tiles = (h->n + 63) / 64;
-        const int S = std::min(16, std::max(1, ((std::min(lc_full, h->n) + 63) / 64 + 7) / 8));
+    if (fp.mass_kernel == FULL_MASS_T) {   // long contigs in a large map (GRAAL_FULL_MASS_TILED: tools/full_mass_check.py)
+        const int S = fp.S, nb = fp.mass_grid;
         const float norm_u = h->uniform_accu > 0 ? (float)(h->uniform_accu * h->uniform_accu) / h->nfpb : -1.0f;
-        const int nb = (n_tiles * S + 3) / 4;
         if (h->single_sub) k_full_mass_t<false><<<nb, 256, 0, fs>>>(h->n, h->perm, h->geo, h->stat_frag, s.p[F_LCONT], s.p[F_LCONTBP], s.p[F_POS], h->nfpb, h->par,
                                                                    reach_bp(h), S, norm_u, h->d_scalars + 9, h->d_scalars + FULL_BAD);
         else k_full_mass_t<true><<<nb, 256, 0, fs>>>(h->n, h->perm, h->geo, h->stat_frag, s.p[F_LCONT], s.p[F_LCONTBP], s.p[F_POS], h->nfpb, h->par,
                                                      reach_bp(h), S, norm_u, h->d_scalars + 9, h->d_scalars + FULL_BAD);
-    } else if (h->n <= 16384)
-        k_full_mass<64><<<blocks_for(h->n, 4), 256, 0, fs>>>(h->n, h->perm, h->contig_off2[h->cur], h->geo, h->stat_frag, s.p[F_LCONT],
+    } else if (fp.mass_kernel == FULL_MASS_64)
+        k_full_mass<64><<<fp.mass_grid, 256, 0, fs>>>(h->n, h->perm, h->contig_off2[h->cur], h->geo, h->stat_frag, s.p[F_LCONT],
                                                                     s.p[F_LCONTBP], s.p[F_POS], h->nfpb, h->par, reach_bp(h),
                                                                     h->d_scalars + 9, h->d_scalars + FULL_BAD);
     else
-        k_full_mass<16><<<blocks_for(h->n, 16), 256, 0, fs>>>(h->n, h->perm, h->contig_off2[h->cur], h->geo, h->stat_frag, s.p[F_LCONT],
+        k_full_mass<16><<<fp.mass_grid, 256, 0, fs>>>(h->n, h->perm, h->contig_off2[h->cur], h->geo, h->stat_frag, s.p[F_LCONT],
                                                                      s.p[F_LCONTBP], s.p[F_POS], h->nfpb, h->par, reach_bp(h),
                                                                      h->d_scalars + 9, h->d_scalars + FULL_BAD);
     if (h->has_rep) { // every pixel of a repeated bin, densely.  With an exchange attached the pixels are dealt to the ranks and the sum travels
@@ -5759,17 +5603,15 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
         nb.fB[k] = k < K ? fB[k] : -1;
         if (k < K && (fB[k] < 0 || fB[k] >= h->n)) return fail(h, GRAAL_E_ARG, "fB out of range");
     }
-    // the step's producer, decided before anything is launched (k_tm's completion targets follow its grid).  An evaluation that carries a
-    // HIP event pair streams: the pairs are pairs around the streaming kernel (graal_scan_times, 4 bytes x contacts / time).  A step
-    // repeated behind events keeps the producer it had.
-    const bool ev = h->want_events && (h->eval_calls % h->event_every == 0);
-    {
-        const char* why = nullptr;
-        const int forced = h->repeat_producer ? h->repeat_producer : h->scan_path;
-        if (forced == 2 && !rows_possible(h, K, &why)) return fail(h, GRAAL_E_STATE, why);
-        h->step_indexed = forced == 2 || (forced == 0 && !ev && scan_use_rows(h, K));
-    }
     CK(hipSetDevice(h->device));
+    // the step's shape, decided before anything is launched (step_plan.h): the producer -- k_tm's completion targets are its grid's -- and who
+    // finishes the step.  An evaluation that carries a HIP event pair streams (graal_scan_times, 4 bytes x contacts / time).
+    const bool ev = h->want_events && (h->eval_calls % h->event_every == 0);
+    const StepFacts facts = step_facts(h, K, world, ev);
+    const ProducerPlan pp = plan_producer(facts);
+    if (pp.why_not) return fail(h, GRAAL_E_STATE, pp.why_not);
+    const FlowPlan flow = plan_flow(facts, pp.indexed);
+    h->step_indexed = pp.indexed;
     hipStream_t st = stream_v ? (hipStream_t)stream_v : h->stream;
     const DevArgs* A = h->d_args + h->cur;
     h->seq += 1;
@@ -5787,36 +5629,22 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
     const bool spin = h->relabel_spin_pending && st == h->stream;
     if (h->relabel_spin_pending && !spin) { CK(hipEventRecord(h->ev_relabel, h->stream)); CK(hipStreamWaitEvent(h->aux, h->ev_relabel, 0)); CK(hipStreamWaitEvent(st, h->ev_relabel, 0)); }
     h->relabel_spin_pending = false;
-    const bool strict = (h->mode & GRAAL_MODE_STRICT) != 0;
     TmArgs ta;
-    ta.strict = strict ? 1 : 0;
+    ta.strict = facts.strict ? 1 : 0;
     ta.quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     ta.nc = h->d_scalars + NC_WORD;
 
     ta.geo = h->geo; ta.link = h->link; ta.cbase = h->cbase; ta.mates = h->mates; ta.tabs = h->tabs; ta.step_hdr = h->step_hdr;
     ta.perm = h->perm; ta.reach_bp = reach_bp(h); ta.tm_done = h->tm_done;
     ta.flags = h->d_flags;
-    ta.sync = h->d_sync; ta.n_scan_blocks = producer_grid(h, K);
-    ta.done = scan_done_counter() ? h->d_done : nullptr; ta.n_done = N_DONE;
-    for (int c = 0; c < N_DONE; c++) ta.done_target[c] = c < ta.n_done ? h->scan_done_total[c] + (unsigned long long)((producer_grid(h, K) - c + ta.n_done - 1) / ta.n_done) : 0ull;
-    // (late stage -- a few long contigs hold nearly every fragment: nearly every step needs k_fin anyway, so it is launched
-    // right behind the scan instead of after k_tm's verdict has made the round trip through the host, ~10 us per step)
-    const bool late_stage = h->max_lcont > 128 && (long long)h->n_contigs * 64 < (long long)h->n;
-    // (one rank only: in this flow k_tm prices no small sets itself, and the ranks would have to enter and leave it together -- a rank whose
-    // finisher is off, or whose running mean differs, must not deal a small set's pairs one way while its peers deal them the other.  With
-    // several ranks k_strict_flat goes out on k_tm's word instead: one host round trip later)
-    const bool mid = flat_allowed(h, world) && world == 1 && h->mid_run && !late_stage && h->finisher_ok;
+    ta.sync = h->d_sync; ta.n_scan_blocks = pp.grid;
+    ta.done = env().scan_done_counter ? h->d_done : nullptr; ta.n_done = N_DONE;
+    for (int c = 0; c < N_DONE; c++) ta.done_target[c] = h->scan_done_total[c] + (unsigned long long)pp.done_inc[c];
     h->flat_tried = false;
-    // (with k_strict_flat behind the scan k_tm prices nothing itself: one thread per pair walking the classes is 30-50 us for a set
-    // of 20 fragments, and the flat kernel would wait for it)
-    ta.strict_inline_m = strict_dense_cfg() ? -1 : (mid ? 0 : STRICT_INLINE_M);
-    // (a long scan -- millions of contacts: the copy is over before the scan is.  A short one -- the C2 / C3 stand-ins -- is complete before the
-    // tables are: the copy would stand in front of the contacts, two round trips for a handful of them; C2 stand-in 130 -> 137 us per step)
-    // The indexed pass is always a short scan: no copy.  (GRAAL_STAGE_TABLES = 0 / 1 overrides, for A/B runs)
-    const int stage_env = env().stage_tables;
-    ta.stage_tables = stage_env >= 0 ? (stage_env ? 1 : 0) : ((!h->step_indexed && h->nnz >= 4000000) ? 1 : 0);
-    ta.host_res = (h->publish && (world == 1 || h->x_host) && h->finisher_ok && !h->has_rep && !late_stage && !mid && !(strict && strict_dense_cfg())) ? h->res_dev : nullptr;
-    ta.wait_ticks = fin_wait_ticks(h);
+    ta.strict_inline_m = flow.strict_inline_m;
+    ta.stage_tables = flow.stage_tables;
+    ta.host_res = flow.tm_publishes ? h->res_dev : nullptr;
+    ta.wait_ticks = flow.fin_wait_ticks;
     ta.counters = (unsigned long long*)(h->d_scalars + 10); ta.queue = h->queue; ta.cnt = h->cnt; ta.multi = h->single_sub ? 0 : 1; ta.stat = h->stat_frag;
     ta.lcontbp = h->soa[h->cur].p[F_LCONTBP]; ta.acc = h->d_acc; ta.nfpb = h->nfpb; ta.par = h->par;
     ta.relabel_flag = (const unsigned long long*)(h->d_scalars + RELABEL_FLAG);
@@ -5836,12 +5664,12 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
     h->eval_calls += 1;
     const size_t slot = (size_t)(h->ring_calls % (long long)(h->ring.size() / 2));
     if (ev) CK(hipEventRecord(h->ring[2 * slot], st));
-    { int rc_ = launch_scan(h, fA, nb, K, max_id, 0, st, ta.host_res != nullptr); if (rc_) return rc_; }
+    { int rc_ = launch_scan(h, pp, fA, nb, K, max_id, 0, st, flow.tm_publishes); if (rc_) return rc_; }
     if (ev) { CK(hipEventRecord(h->ring[2 * slot + 1], st)); h->ring_calls += 1; }
     // (3) finishing kernel -- unless k_tm's last block does that job (it asks for k_fin through the result word if not)
-    if (h->has_rep) { // the repeated bins' pixels, densely, for all 13 K candidates
+    if (flow.rep_delta) { // the repeated bins' pixels, densely, for all 13 K candidates
         // (its blocks wait for k_tm's tables too, and with 167 VGPRs three of them fill a CU's register files: ordered behind
-        // k_tm by the event rather than trusted to be placed after it -- see fin_blocks_no_wait)
+        // k_tm by the event rather than trusted to be placed after it -- see plan_fin)
         CK(hipEventRecord(h->ev_tm, h->aux));
         CK(hipStreamWaitEvent(st, h->ev_tm, 0));
         const RepArgs R = rep_args(h);
@@ -5849,18 +5677,11 @@ int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t
                                                                                          h->d_acc, (unsigned long long*)(h->d_scalars + 10));
         CK(hipGetLastError());
     }
-    if (strict) {
-        if (ta.host_res == nullptr) {
-            int rc_ = 0;
-            // (several ranks: whoever finishes a step that is not in the late stage -- this rank's finisher may be off while its peers' are on --
-            // goes through k_strict_flat first, like a rank that k_tm sent there: the flat and the tiled kernels deal the pairs differently)
-            if (mid || (world > 1 && !late_stage && flat_allowed(h, world))) { rc_ = launch_flat(h, fA, &nb, K, rank, world, (long long*)d_q_out, h->publish, st); h->flat_tried = true; }
-            else rc_ = launch_strict(h, fA, K, rank, world, (long long*)d_q_out, h->publish, st);
-            if (rc_) return rc_;
-            if (!h->publish) { CK(hipEventRecord(h->ev_fin, st)); h->fin_pending = true; }
-        }
-    } else if (ta.host_res == nullptr) {
-        int rc_ = launch_fin(h, K, rank, world, (long long*)d_q_out, h->publish, st);
+    if (flow.finisher != FIN_NONE) {
+        int rc_ = 0;
+        if (flow.finisher == FIN_FLAT) { rc_ = launch_flat(h, fA, &nb, K, rank, world, (long long*)d_q_out, h->publish, st); h->flat_tried = true; }
+        else if (flow.finisher == FIN_TILED) rc_ = launch_strict(h, plan_strict(facts), fA, K, rank, world, (long long*)d_q_out, h->publish, st);
+        else rc_ = launch_fin(h, plan_fin(facts), K, rank, world, (long long*)d_q_out, h->publish, st);
         if (rc_) return rc_;
         if (!h->publish) { CK(hipEventRecord(h->ev_fin, st)); h->fin_pending = true; }
     }
@@ -5952,12 +5773,14 @@ static int eval_sync(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int
             h->publish = true;
             h->step_needed_fin = true;
             h->rc_need_fin += 1;
-            if ((h->mode & GRAAL_MODE_STRICT) && flat_allowed(h, world) && !h->flat_tried) { // small sets first; if they are not, it says NEED_FIN again
+            const StepFacts facts = step_facts(h, K, world);
+            const Finisher fin = plan_finisher(facts, !h->flat_tried);   // small sets first; if they are not, it says NEED_FIN again
+            if (fin == FIN_FLAT) {
                 h->flat_tried = true;
                 rc = launch_flat(h, fA, nullptr, K, rank, world, (long long*)h->d_qout, true, h->stream);
             } else
-                rc = (h->mode & GRAAL_MODE_STRICT) ? launch_strict(h, fA, K, rank, world, (long long*)h->d_qout, true, h->stream)
-                                                   : launch_fin(h, K, rank, world, (long long*)h->d_qout, true, h->stream);
+                rc = fin == FIN_TILED ? launch_strict(h, plan_strict(facts), fA, K, rank, world, (long long*)h->d_qout, true, h->stream)
+                                      : launch_fin(h, plan_fin(facts), K, rank, world, (long long*)h->d_qout, true, h->stream);
             h->publish = false;
             if (rc) return rc;
             continue;
@@ -6249,11 +6072,11 @@ int graal_set_scan_path(graal_ctx* h, int32_t path)
 {
     if (!h || path < 0 || path > 2) return GRAAL_E_ARG;
     if (path == 2) {
-        const char* why = nullptr;
         if (!h->have_contacts) return fail(h, GRAAL_E_STATE, "upload the contacts first");
+        const StepFacts facts = step_facts(h, 1, 1);
         size_t shm; unsigned wmask;
-        scan_bitmap_cfg(h, &shm, &wmask);
-        if (!h->rowptr || wmask != 0xffffffffu) { (void)rows_possible(h, 1, &why); return fail(h, GRAAL_E_STATE, why ? why : "no indexed pass for this map"); }
+        plan_bitmap(facts, &shm, &wmask);
+        if (const char* why = plan_no_index(facts, wmask)) return fail(h, GRAAL_E_STATE, why);
     }
     h->scan_path = path;
     return GRAAL_OK;
@@ -6361,13 +6184,14 @@ int graal_time_scan(graal_ctx* h, int32_t K, int32_t reps, float* avg_ms)
         CK(hipSetDevice(h->device));
         Neigh nb;
         for (int k = 0; k < MAXK; k++) nb.fB[k] = h->last_fB[k];
+        const ProducerPlan pp = streaming_plan(h, K);
         std::vector<float> t;
         for (int i = 0; i < -reps + 3; i++) {
             CK(hipStreamSynchronize(h->stream));
             const auto t0 = std::chrono::steady_clock::now();
             while (std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(50)) { }
             CK(hipEventRecord(h->ev[0], h->stream));
-            { int rc = launch_scan(h, h->last_fA, nb, K, h->last_max_id, 1, h->stream); if (rc) return rc; }
+            { int rc = launch_scan(h, pp, h->last_fA, nb, K, h->last_max_id, 1, h->stream); if (rc) return rc; }
             CK(hipEventRecord(h->ev[4], h->stream));
             CK(hipEventSynchronize(h->ev[4]));
             float ms = 0.0f;
@@ -6384,9 +6208,10 @@ int graal_time_scan(graal_ctx* h, int32_t K, int32_t reps, float* avg_ms)
     if (K != h->last_K) return fail(h, GRAAL_E_ARG, "K differs from the last evaluation");
     Neigh nb;
     for (int k = 0; k < MAXK; k++) nb.fB[k] = h->last_fB[k];
-    for (int i = 0; i < 3; i++) { int rc = launch_scan(h, h->last_fA, nb, K, h->last_max_id, 1, h->stream); if (rc) return rc; }
+    const ProducerPlan pp = streaming_plan(h, K);
+    for (int i = 0; i < 3; i++) { int rc = launch_scan(h, pp, h->last_fA, nb, K, h->last_max_id, 1, h->stream); if (rc) return rc; }
     CK(hipEventRecord(h->ev[0], h->stream));
-    for (int i = 0; i < reps; i++) { int rc = launch_scan(h, h->last_fA, nb, K, h->last_max_id, 1, h->stream); if (rc) return rc; }
+    for (int i = 0; i < reps; i++) { int rc = launch_scan(h, pp, h->last_fA, nb, K, h->last_max_id, 1, h->stream); if (rc) return rc; }
     CK(hipEventRecord(h->ev[4], h->stream));
     CK(hipEventSynchronize(h->ev[4]));
     float ms = 0.0f;

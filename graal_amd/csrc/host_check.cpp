@@ -11,6 +11,7 @@
 #include "frag_ops.h"
 #include "strict_sets.h"
 #include "scan_rows.h"
+#include "step_plan.h"
 
 using namespace graal;
 
@@ -331,5 +332,73 @@ void hc_row_index(const int32_t* row, int64_t nnz, int32_t S, int64_t* out, int6
 int64_t hc_scan_rows_bound(int K, int64_t lc, int single_sub) { return scan_rows_bound(K, lc, single_sub != 0); }
 int hc_scan_rows_wins(int64_t rows, int64_t longest_row, int64_t nnz, int64_t R) { return scan_rows_wins(rows, longest_row, nnz, R) ? 1 : 0; }
 int hc_scan_rows_cap() { return ROWS_CAP; }
+
+// ---- a step's plan (step_plan.h).  in[HC_N_FACTS]: the facts in StepFacts' order, the switches' and the kernels' figures behind them
+enum { HC_N_FACTS = 44 };
+static StepFacts hc_facts(const int64_t* in)
+{
+    StepFacts f;
+    int i = 0;
+    f.n = (int)in[i++]; f.n_sub_total = (int)in[i++]; f.nnz = in[i++]; f.single_sub = in[i++] != 0;
+    f.n_contigs = (int)in[i++]; f.max_lcont = (int)in[i++]; f.lcont_bound = (int)in[i++];
+    f.has_rep = in[i++] != 0; f.has_ubins = in[i++] != 0; f.uniform_accu = (int)in[i++];
+    f.strict = in[i++] != 0; f.quirk = in[i++] != 0;
+    f.K = (int)in[i++]; f.world = (int)in[i++]; f.exchange = in[i++] != 0; f.publish = in[i++] != 0; f.ev = in[i++] != 0;
+    f.finisher_ok = in[i++] != 0; f.spin_ok = in[i++] != 0; f.gwait_env = in[i++] != 0; f.mid_run = in[i++] != 0;
+    f.has_rowptr = in[i++] != 0; f.longest_row = in[i++]; f.forced_producer = (int)in[i++];
+    f.slist_soft_cap = (unsigned long long)in[i++]; f.slist_floor = (unsigned long long)in[i++]; f.slist_cap = (unsigned long long)in[i++];
+    f.env.scan_threads = (int)in[i++]; f.env.scan_groups = (int)in[i++]; f.env.scan_blocks = (int)in[i++]; f.env.scan_fold_bits = (int)in[i++];
+    f.env.scan_rows_r = in[i++]; f.env.fin_blocks = (int)in[i++]; f.env.strict_dense = in[i++] != 0; f.env.no_flat = in[i++] != 0;
+    f.env.full_no_compact = in[i++] != 0; f.env.full_no_lds = in[i++] != 0; f.env.full_mass_tiled = (int)in[i++]; f.env.stage_tables = (int)in[i++];
+    f.kf.lds_tm = (size_t)in[i++]; f.kf.lds_fin = (size_t)in[i++]; f.kf.regs_tm = (int)in[i++]; f.kf.regs_fin = (int)in[i++];
+    f.kf.fin_dyn_lds_per_k = (size_t)in[i++];
+    static_assert(HC_N_FACTS == 44, "tests/test_step_plan_cpu.py lists the same fields");
+    return f;
+}
+int hc_plan_n_facts() { return HC_N_FACTS; }
+
+// out[0..7] = indexed, forced and impossible, threads, groups, grid, bitmap bytes, mask, ROWS bound; out[8..23] = the completion increments
+void hc_plan_producer(const int64_t* in, int64_t* out)
+{
+    const StepFacts f = hc_facts(in);
+    const ProducerPlan p = plan_producer(f);
+    out[0] = p.indexed; out[1] = p.why_not != nullptr; out[2] = p.threads; out[3] = p.groups; out[4] = p.grid;
+    out[5] = (int64_t)p.bitmap_bytes; out[6] = p.wmask; out[7] = plan_rows_bound(f);
+    for (int c = 0; c < PLAN_N_DONE; c++) out[8 + c] = p.done_inc[c];
+}
+
+// out[0..7] = late_stage, mid, strict_inline_m, stage_tables, k_tm publishes, fin_wait_ticks, k_rep_delta, finisher (0 none, 1 k_fin, 2 flat, 3 tiled)
+void hc_plan_flow(const int64_t* in, int indexed, int64_t* out)
+{
+    const FlowPlan p = plan_flow(hc_facts(in), indexed != 0);
+    out[0] = p.late_stage; out[1] = p.mid; out[2] = p.strict_inline_m; out[3] = p.stage_tables; out[4] = p.tm_publishes;
+    out[5] = p.fin_wait_ticks; out[6] = p.rep_delta; out[7] = (int64_t)p.finisher;
+}
+
+int hc_plan_finisher(const int64_t* in, int flat_first) { return (int)plan_finisher(hc_facts(in), flat_first != 0); }
+
+// out[0..2] = grid, behind an event, the largest grid that may spin
+void hc_plan_fin(const int64_t* in, int64_t* out)
+{
+    const StepFacts f = hc_facts(in);
+    const FinPlan p = plan_fin(f);
+    out[0] = p.grid; out[1] = p.event; out[2] = plan_fin_no_wait(f);
+}
+
+// out[0..12] = dense, grid, tile, nt, refused, seg_unit, target, worst, need, alloc, gwait, cull_blocks, no_window
+void hc_plan_strict(const int64_t* in, int64_t* out)
+{
+    const StrictPlan p = plan_strict(hc_facts(in));
+    out[0] = p.dense; out[1] = p.grid; out[2] = p.tile; out[3] = (int64_t)p.nt; out[4] = p.refused; out[5] = p.seg_unit; out[6] = (int64_t)p.target;
+    out[7] = (int64_t)p.worst; out[8] = (int64_t)p.need; out[9] = (int64_t)p.alloc; out[10] = p.gwait; out[11] = p.cull_blocks; out[12] = p.no_window;
+}
+
+// out[0..6] = compact, contacts' kernel (0 none, 1 k_full_nnz, 2 _u, 3 _l), its grid, label bytes, mass kernel (0 <64>, 1 <16>, 2 tiled), its grid, S
+void hc_plan_full(const int64_t* in, int64_t* out)
+{
+    const FullPlan p = plan_full(hc_facts(in));
+    out[0] = p.compact; out[1] = (int64_t)p.nnz_kernel; out[2] = p.nnz_grid; out[3] = (int64_t)p.lab_bytes; out[4] = (int64_t)p.mass_kernel;
+    out[5] = p.mass_grid; out[6] = p.S;
+}
 
 } // extern "C"
