@@ -1,8 +1,8 @@
 """Build the engine's shared libraries in-tree (they travel to the GPU box with the snapshot).
 
 * ``libgraal_hip.so``  -- the product: HIP kernels + C ABI, ``hipcc --offload-arch=gfx950``.
-* ``libgraal_hostcheck.so`` -- TEST ONLY: ``frag_ops.h`` (host/device shared layout algebra) compiled
-  for the host with g++ so that the CPU test-suite can check it against the oracle without a GPU.
+* ``libgraal_hostcheck.so`` -- TEST ONLY: ``frag_ops.h`` (host/device shared layout algebra) and the other
+  pure headers (``strict_sets.h``, ``scan_rows.h``, ``step_plan.h``, ``map_shape.h``) compiled for the host with g++ so that the CPU test-suite can check it against the oracle without a GPU.
   It contains no likelihood code and is never loaded by the product path.
 """
 import glob

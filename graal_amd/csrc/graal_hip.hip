@@ -35,6 +35,7 @@
 #include "model_math.h"
 #include "scan_rows.h"
 #include "step_plan.h"
+#include "map_shape.h"
 
 using namespace graal;
 
@@ -4101,6 +4102,8 @@ struct InBuf;                  // insert.h: graal_insertions' buffers and result
 void in_free(InBuf* b);
 struct FlBuf;                  // flips.h: graal_block_flips' buffers
 void fl_free(FlBuf* b);
+struct MpBuf;                  // maps.h: graal_layout_maps' buffers and images
+void mp_free(MpBuf* b);
 
 struct Ctx {
     int device = 0;
@@ -4305,6 +4308,7 @@ struct Ctx {
     EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
     InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
     FlBuf* fl = nullptr;          // graal_block_flips' buffers (flips.h; allocated by its first call)
+    MpBuf* mp = nullptr;          // graal_layout_maps' buffers and images (maps.h; allocated by its first call)
 };
 
 #define CK(call)                                                                                     \
@@ -4881,6 +4885,7 @@ void graal_destroy(graal_ctx* h)
         ed_free(h->ed); h->ed = nullptr;
         in_free(h->ins); h->ins = nullptr;
         fl_free(h->fl); h->fl = nullptr;
+        mp_free(h->mp); h->mp = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
         if (h->h_stats) (void)hipHostFree(h->h_stats);
@@ -6338,3 +6343,4 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "insert.h"
 #include "flips.h"
 #include "edit.h"
+#include "maps.h"

@@ -1,6 +1,7 @@
 // host_check.cpp -- TEST ONLY.  Host build of frag_ops.h / strict_sets.h so that the CPU test-suite can compare the engine's
 // layout algebra (mutations, pieces, per-piece transforms, relation flags; the union set of a step, its classes of equal inputs
-// and its work units) with the oracle and with brute force without a GPU.
+// and its work units) with the oracle and with brute force without a GPU; and of the small pure headers beside them (scan_rows.h,
+// step_plan.h, map_shape.h).
 // No likelihood code here and nothing in graal_amd/ loads this library.
 #include <stddef.h>
 #include <stdint.h>
@@ -12,6 +13,7 @@
 #include "strict_sets.h"
 #include "scan_rows.h"
 #include "step_plan.h"
+#include "map_shape.h"
 
 using namespace graal;
 
@@ -399,6 +401,14 @@ void hc_plan_full(const int64_t* in, int64_t* out)
     const FullPlan p = plan_full(hc_facts(in));
     out[0] = p.compact; out[1] = (int64_t)p.nnz_kernel; out[2] = p.nnz_grid; out[3] = (int64_t)p.lab_bytes; out[4] = (int64_t)p.mass_kernel;
     out[5] = p.mass_grid; out[6] = p.S;
+}
+
+// ---- a layout map's binning (map_shape.h): out[0] = bin, out[1] = m, out[2 + i] = the pixel of ranks[i]
+void hc_map_shape(int S, int max_px, const int32_t* ranks, int n_ranks, int32_t* out)
+{
+    const MapShape s = map_shape(S, max_px);
+    out[0] = s.bin; out[1] = s.m;
+    for (int i = 0; i < n_ranks; i++) out[2 + i] = map_pixel(ranks[i], s.bin);
 }
 
 } // extern "C"

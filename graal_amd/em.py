@@ -26,8 +26,11 @@ class Trace(object):
         return np.array([self.id_fA, self.id_fB, self.op_sampled], dtype=np.int64).T.reshape(-1, 3)
 
 
-def run_em(sampler, n_cycles, n_neighbours, rng=None, sample_param=False, scrambled=True, dt=0, on_step=None, matrix_files=None):
-    """``matrix_files = (before, after)``: the two images start_EM writes through display_current_matrix (``main_gl.py:213, 283``:
+def run_em(sampler, n_cycles, n_neighbours, rng=None, sample_param=False, scrambled=True, dt=0, on_step=None, matrix_files=None,
+           on_cycle=None):
+    """``on_cycle(j, sampler)`` is called behind the last step of every cycle j (unlike ``on_step`` it leaves the cycle's steps on their
+    fast path); None: nothing is called.
+    ``matrix_files = (before, after)``: the two images start_EM writes through display_current_matrix (``main_gl.py:213, 283``:
     pre_simu.tiff before the first step -- of the layout as loaded --, post_em.tiff behind the last cycle); None: no images."""
     if rng is None and getattr(getattr(sampler, "group", None), "world", 1) > 1:
         raise ValueError("run_em over a sharded sampler needs the sampler's (identically seeded) rng: every rank shuffles itself")
@@ -63,6 +66,8 @@ def run_em(sampler, n_cycles, n_neighbours, rng=None, sample_param=False, scramb
                 trace.slope.append(slope)
                 trace.likelihood_nuisance.append(o)
                 trace.success.append(1)
+            if on_cycle is not None:
+                on_cycle(j, sampler)
             continue
         for i in list_frags:
             o, n_contigs, min_len, mean_len, max_len, op_sampled, id_f_sampled, dist, temp = \
@@ -92,6 +97,8 @@ def run_em(sampler, n_cycles, n_neighbours, rng=None, sample_param=False, scramb
             trace.success.append(success)
             if on_step is not None:
                 on_step(j, i, trace)
+        if on_cycle is not None:
+            on_cycle(j, sampler)
     if matrix_files and len(matrix_files) > 1 and matrix_files[1]:
         sampler.display_current_matrix(matrix_files[1])
     return trace

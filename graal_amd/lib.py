@@ -53,6 +53,7 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_set_scan_path", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
            "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
+           "graal_layout_maps", "graal_layout_maps_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
 STEP_DONE, STEP_PAUSED, STEP_FALLBACK, STEP_SELECT = 0, 1, 2, 3
@@ -142,6 +143,8 @@ def load():
         L.graal_insertions_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, ctypes.POINTER(ctypes.c_uint8), _i64p, _i64p,
                                              ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
         L.graal_block_flips.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
+        L.graal_layout_maps.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p]
+        L.graal_layout_maps_fetch.argtypes = [ctypes.c_void_p, _f32p, _f32p, _f32p, _i32p]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_scan_path.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_finisher.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -256,6 +259,8 @@ class Engine:
         self._ck(self._L.graal_upload_subfrags(self._h, sid.ctypes.data_as(_i32p), sl.ctypes.data_as(_f32p),
                                                sa.ctypes.data_as(_i32p), len(sid), int(n_sub_total),
                                                ctypes.c_float(float(n_frags_per_bins))), "graal_upload_subfrags")
+        self.n_sub_total = int(n_sub_total)
+        self.sub_id = sid.copy()   # a host copy of the id table, nothing else changes (graal_amd.maps names a contig's pixels with it)
 
     def upload_repeats(self, dup_bins, dispatcher, collector, obs_rows):
         """Repeated bins: their ids, the copies of every bin, and their rows of the observation matrix
@@ -497,6 +502,38 @@ class Engine:
                                            c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
                  "graal_block_flips")
         return q, c, st
+
+    def layout_maps(self, max_px=2048):
+        """graal_layout_maps + graal_layout_maps_fetch: (observed, expected, residual, pixel_of_sub, bin, bad_pixels).  The three images
+        are float32 [m, m] in the current genome order (contigs by ascending label, fragments by position, sub-fragments in stored order,
+        reversed when ori == -1), `bin` consecutive sub-fragments of that order per pixel (bin = max(1, ceil(S / max_px)), 1 <= max_px <=
+        4096): the summed contacts between two pixels, what the contact model expects there, and the Pearson residual (observed - expected)
+        / sqrt(expected).  pixel_of_sub int32[S]: the pixel of every sub-fragment id.  bad_pixels: pixels whose expected value is not
+        finite (NaN in expected and residual).  Same preconditions and refusals as junction_scores.  Leaves the step state alone."""
+        m, b = self.layout_maps_compute(max_px)
+        obs, exp, res = (np.zeros((m, m), dtype=np.float32) for _ in range(3))
+        pix = self.layout_maps_fetch(obs, exp, res)
+        return obs, exp, res, pix, b, self._maps_bad
+
+    def layout_maps_compute(self, max_px=2048):
+        """graal_layout_maps alone: the images stay on the device; (m, bin)."""
+        m, b, bad = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        self._ck(self._L.graal_layout_maps(self._h, int(max_px), ctypes.byref(m), ctypes.byref(b), ctypes.byref(bad)), "graal_layout_maps")
+        self._maps_bad = int(bad.value)
+        self._maps_m = int(m.value)
+        return int(m.value), int(b.value)
+
+    def layout_maps_fetch(self, observed=None, expected=None, residual=None, pixel_of_sub=True):
+        """graal_layout_maps_fetch into the given float32 [m, m] arrays (None: not copied); returns pixel_of_sub (or None)."""
+        pix = np.zeros(int(getattr(self, "n_sub_total", 0)), dtype=np.int32) if pixel_of_sub else None
+        ptr = []
+        for a in (observed, expected, residual):
+            if a is not None and not (a.dtype == np.float32 and a.flags["C_CONTIGUOUS"] and a.shape == (getattr(self, "_maps_m", -1),) * 2):
+                raise ValueError("layout_maps_fetch takes C-contiguous float32 [m, m] arrays of the last layout_maps_compute")
+            ptr.append(None if a is None else a.ctypes.data_as(_f32p))
+        self._ck(self._L.graal_layout_maps_fetch(self._h, ptr[0], ptr[1], ptr[2], None if pix is None else pix.ctypes.data_as(_i32p)),
+                 "graal_layout_maps_fetch")
+        return pix
 
     def edit_layout(self, cuts=(), joins=()):
         """graal_edit_layout: cut the junction after every fragment of `cuts`, then apply `joins` (pairs of ends, end = 2 * fragment +

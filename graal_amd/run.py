@@ -71,7 +71,15 @@ def main(argv=None):
     ap.add_argument("--insertions", action="store_true", help="write insertions.tsv into the output folder: every insertion of a piece of "
                                                               "up to --insert-max-frags fragments into a junction of the final layout that the "
                                                               "contacts support, with the log-likelihood it would add (graal_amd.insert)")
+    ap.add_argument("--maps", action="store_true", help="write observed.tiff, expected.tiff, residual.tiff and map_contigs.tsv into the output "
+                                                        "folder: the contact matrix of the final layout in genome order, what the model "
+                                                        "expects there and their Pearson residual, computed on the GPU (graal_amd.maps)")
+    ap.add_argument("--maps-max-px", type=int, default=2048, help="with --maps: the images' largest side, 1 .. 4096 (default 2048)")
+    ap.add_argument("--maps-every", type=int, default=0, help="with --maps: also write maps/cycle_%%05d_* behind every C-th cycle (default 0: "
+                                                              "the final layout's only)")
     args = ap.parse_args(argv)
+    if args.maps and not 1 <= args.maps_max_px <= 4096:
+        raise SystemExit("--maps-max-px must be in 1 .. 4096")
     if not 0 <= args.level < args.size_pyramid:
         raise SystemExit("--level must be in 0 .. size-pyramid - 1 (levels >= 1: the level below holds the observations; 0: the level itself)")
     from .sampler import sampler
@@ -125,8 +133,15 @@ def main(argv=None):
             smp.explode_genome()
         scaffold.write_scaffold_tsv(os.path.join(out, "scaffold.tsv"), scaffold.scaffold(smp, min_score=args.scaffold_min_score))
         scrambled = False
+    on_cycle = None
+    if args.maps and args.maps_every > 0:
+        from . import maps
+
+        def on_cycle(j, s):
+            if (j + 1) % args.maps_every == 0:
+                maps.write_maps(os.path.join(out, "maps"), "cycle_%05d_" % j, maps.layout_maps(s, args.maps_max_px))
     trace = em.run_em(smp, args.cycles, args.neighbours, rng=rng, sample_param=args.sample_params, scrambled=scrambled,
-                      matrix_files=images)
+                      matrix_files=images, on_cycle=on_cycle)
     dt = time.perf_counter() - t0
     em.save_behaviour_to_txt(trace, out)
     if args.polish:
@@ -161,6 +176,9 @@ def main(argv=None):
         eng = scaffold._engine(smp)
         soa = eng.download_frags()
         flips.write_flips_tsv(os.path.join(out, "flips.tsv"), flips.score_table(eng, soa, flips.tilings(soa, None, args.flip_max_frags)))
+    if args.maps:
+        from . import maps
+        maps.write_maps(out, "", maps.layout_maps(smp, args.maps_max_px))
     n_steps = len(trace.likelihood)
     print("%d bins (%d fragments, %d sub-fragments), %d MCMC steps in %.1f s (%.0f us/step): %d contigs, logL %.6e, "
           "distance to the initial genome %.4f; traces in %s" % (inp["n_frags"], inp["n_new_frags"], inp["init_n_sub_frags"], n_steps,

@@ -439,6 +439,35 @@ int graal_insertions_fetch(graal_ctx* h, int32_t* piece, int32_t* after, uint8_t
 int graal_block_flips(graal_ctx* h, int32_t n_blocks, const int32_t* first, const int32_t* last, int64_t* q, int64_t* contacts,
                       uint8_t* status);
 
+/* Layout maps: the observed contacts, the contacts the model expects and their residual, as images in the current genome order
+ * (graal_amd/csrc/maps.h).
+ * Order: contigs by ascending label, fragments by position inside a contig, a fragment's sub-fragments in stored order, reversed when
+ * ori == -1 (sampler.display_current_matrix's full_order_high), built from the layout fields.  S = the number of sub-fragments.
+ * Binning (graal_amd/csrc/map_shape.h, image.matrix_image's rule): bin = max(1, ceil(S / max_px)), m = ceil(S / bin), the sub-fragment
+ * of rank u lies in pixel u / bin.  max_px must lie in 1 .. 4096 (GRAAL_E_ARG otherwise).
+ *   observed[p][q]  the summed counts of the contacts (row != col) between pixels p and q, both ways: symmetric, a diagonal pixel holds
+ *                   twice the counts inside it.  Summed per pixel as int64 of count * 2^24, rounded once per contact: integer counts
+ *                   are exact, the image is the same from call to call and for any grid.
+ *   expected[p][q]  the same binning of lambda(a, b) over every pair a < b of sub-fragments, lambda what graal_simulate_contacts draws
+ *                   from: the cis price (rippe / rippe_circ of the float32 centres) inside a contig, v_inter across contigs, times
+ *                   accu_a accu_b / n_frags_per_bins, RF counts indexed exactly (GRAAL_MODE_REF_TRANS_ACCU is not applied), negative
+ *                   values as 0.  Computed as max(v_inter, 0) / n_frags_per_bins * (sum of RF counts of p) * (of q) in float64 from
+ *                   exact integers (on the diagonal the square minus the sum of squares), plus, for every cis pair (inside the window
+ *                   in a linear contig; every pair of a circular one), max(cis price, 0) - max(trans price, 0) of the two float32
+ *                   prices, rounded to 2^-30 once per pair and summed as int64.
+ *   residual[p][q]  (observed - expected) / sqrt(expected) where expected > 0, else 0 (the Pearson residual of the Poisson model).
+ * A pair whose term is not finite or does not fit makes its pixel NaN in expected and residual; *bad_pixels_out counts the NaN pixels
+ * of the m x m image.  Outputs of graal_layout_maps: *m_out = m, *bin_out = bin (each may be NULL).  graal_layout_maps_fetch copies the
+ * images of the last call out, m * m float32 row major, and pixel_of_sub (one entry per sub-fragment id); any pointer may be NULL;
+ * GRAAL_E_STATE before a successful graal_layout_maps.
+ * Needs sub-fragments, parameters, fragments and contacts.  Does not relabel and leaves the step state alone (ranked layout, carried
+ * total, a pending commit's correction, the proposal tables).  Device memory: two int64 sums and three float32 images of m * m pixels
+ * (at 4096: 268 MB + 201 MB), kept by the handle.  GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats) and for a layout with
+ * an inactive fragment; GRAAL_E_STATE with an exchange or RCCL attached (one rank only). */
+#define GRAAL_MAPS_MAX_PX 4096
+int graal_layout_maps(graal_ctx* h, int32_t max_px, int32_t* m_out, int32_t* bin_out, int64_t* bad_pixels_out);
+int graal_layout_maps_fetch(graal_ctx* h, float* observed, float* expected, float* residual, int32_t* pixel_of_sub);
+
 /* ---- the sampler's per-step HOST logic behind the boundary (graal_amd/csrc/host_step.h) --------------------------------
  * What cuda_lib_gl.sampler.step_max_likelihood does on the host between its launches: return_neighbours
  * (cuda_lib_gl.py:2295-2331: RandomState.choice(xk, n, p=pk, replace=False), expansion to the copies of repeated bins,
