@@ -1,31 +1,27 @@
 """graal_junction_scores, graal_end_links / graal_end_links_best, graal_insertions and graal_edit_layout at mid-size shapes, against the
 windowed restatement (tests/window_reference.py) and tests/edit_reference.py.  The shapes (tests/window_cases.py) reach what the small
-problems never do: multi-stripe junction tiles up to the cap of 16 waves and a second tile per wave, the window exits, groups of 8
-beyond the first on both sides of a link, grids that stride over more than 524,288 contacts, open-addressing tables of thousands of
-keys, and 11 rounds of pointer jumping.  Keys and contact counts are compared for every link and insertion; Q and status for every
-link and for a seeded sample of the insertions that covers each shape class.  Every test asserts that its shape engages, and that each
-class of terms moves at least a few of the compared values by more than the tolerance (1e-9 * sum of |terms| + 1, in Q)."""
+problems never do: multi-stripe junction tiles up to the cap of 16 waves and a second tile per wave (on a STEPPED engine, one that ran
+graal_begin_step behind the upload: the handle sizes k_jn_mass's and k_mp_cis's waves per tile by the longest contig of its last
+begin_step, so a FRESH engine, upload only, runs one wave per tile whatever the layout, and a STALE one the waves of the layout before
+-- tests/engine_states.py; the junction tests run in all three, the other tests' kernels do not read that statistic and run fresh), the window
+exits, groups of 8 beyond the first on both sides of a link, grids that stride over more than 524,288 contacts, open-addressing tables
+of thousands of keys, and 11 rounds of pointer jumping.  Keys and contact counts are compared for every link and insertion; Q and
+status for every link and for a seeded sample of the insertions that covers each shape class.  Every test asserts that its shape
+engages, and that each class of terms moves at least a few of the compared values by more than the tolerance (1e-9 * sum of |terms| +
+1, in Q)."""
 import numpy as np
 import pytest
 
 from graal_amd import links
-from graal_amd.lib import Engine, JUNCTION_VALID, LINK_VALID, INSERT_VALID
+from graal_amd.lib import JUNCTION_VALID, LINK_VALID, INSERT_VALID
 from tests import edit_reference as ER
 from tests import link_reference as LR
 from tests import window_cases as WC
 from tests import window_reference as WR
+from tests.engine_states import GRID_CONTACTS, cached, engine_for, engine_in, stripes_of
 
 pytestmark = pytest.mark.gpu
-GRID_CONTACTS = 2048 * 4 * 64           # the contact-streaming kernels' contacts per grid pass
 SAMPLE = 2048                           # insertions compared in full per table (the rest: keys and contacts only)
-
-_CACHE = {}
-
-
-def cached(key, fn):
-    if key not in _CACHE:
-        _CACHE[key] = fn()
-    return _CACHE[key]
 
 
 def problem(name):
@@ -38,18 +34,6 @@ def window(name, quirk):
 
 def tol(A):
     return 1e-9 * np.asarray(A, np.float64) + 1
-
-
-def engine_for(P, state=None, quirk=False):
-    e = Engine(0)
-    e.upload_subfrags(P["np_sub_frags_id"], P["np_sub_frags_len_bp"], P["np_sub_frags_accu"], P["init_n_sub_frags"],
-                      P["mean_squared_frags_per_bin"])
-    e.upload_contacts(P["coo_row"], P["coo_col"], P["coo_val"])
-    e.set_params(P["param_simu"])
-    e.upload_frags(P["S_o_A_frags"] if state is None else state)
-    if quirk:
-        e.set_mode(ref_trans_accu=True)
-    return e
 
 
 def _window_frags(s, reach):
@@ -83,34 +67,43 @@ def _classes_move(parts, A, names):
 # ---- junctions -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,quirk", [("m1", False), ("m1", True), ("m2", False), ("m2", True)])
 def test_junctions_equal_restatement(name, quirk):
+    """On a fresh engine (one wave per x tile) and on a stepped one, where k_jn_mass runs the `stripes` waves per tile that the layout
+    calls for; each against the restatement of the layout that engine holds, and the two against each other word for word (the sums are
+    int64 atomics and a junction's score does not depend on its contig's label)."""
     P = problem(name)
-    s = P["S_o_A_frags"]
     W = window(name, quirk)
-    e = engine_for(P, quirk=quirk)
-    try:
-        q, st = e.junction_scores_q()
-    finally:
-        e.close()
-    parts = {}
-    J, rst, A = W.junction_scores(s, parts)
-    linear = s["circ"] == 0
-    lc = int(s["l_cont"][linear].max())
-    stripes = min(16, -(-(-(-lc // 64)) // 8))          # k_jn_mass: waves per 64-slot tile of the longest contig
-    if name == "m1":
-        widest = max(_window_frags(s, W.reach))
-        assert lc > 8192 and stripes == 16 and widest > 1024, (lc, widest)      # the cap, and a second tile per wave
-        assert len(P["coo_row"]) > GRID_CONTACTS and (s["circ"] == 1).any()
-    else:
-        assert lc > 1024 and stripes == 3, lc
-        assert (s["l_cont_bp"][linear] > W.reach).all()                         # every contig leaves the window
-    assert np.array_equal(st, rst)
-    ok = st == JUNCTION_VALID
-    assert ok.sum() >= linear.sum() - 10 and (q[~ok] == 0).all()
-    bad = np.nonzero(np.abs(q[ok] - J[ok]) > tol(A[ok]))[0]
-    assert len(bad) == 0, (len(bad), np.nonzero(ok)[0][bad[:5]], (q[ok] - J[ok])[bad[:5]])
-    classes = ("contacts", "near", "wide") + (("far",) if quirk and name == "m2" else ())
-    for k in classes:
-        assert (np.abs(parts[k][ok]) > tol(A[ok])).sum() >= 3, k
+    got = {}
+    for engine_state in ("fresh", "stepped"):
+        e, s, Sw = engine_in(engine_state, P, quirk=quirk)
+        try:
+            q, st = e.junction_scores_q()
+        finally:
+            e.close()
+        got[engine_state] = (q, st)
+        parts = {}
+        J, rst, A = W.junction_scores(s, parts)
+        linear = s["circ"] == 0
+        lc = int(s["l_cont"][linear].max())
+        stripes = min(16, -(-(-(-lc // 64)) // 8))          # k_jn_mass: waves per 64-slot tile of the longest contig
+        assert Sw == (stripes if engine_state == "stepped" else 1), (engine_state, Sw, stripes)
+        if name == "m1":
+            widest = max(_window_frags(s, W.reach))
+            assert lc > 8192 and stripes == 16 and widest > 1024, (lc, widest)      # the cap, and a second tile per wave
+            assert len(P["coo_row"]) > GRID_CONTACTS and (s["circ"] == 1).any()
+        else:
+            assert lc > 1024 and stripes == 3, lc
+            assert (s["l_cont_bp"][linear] > W.reach).all()                         # every contig leaves the window
+        assert np.array_equal(st, rst)
+        ok = st == JUNCTION_VALID
+        assert ok.sum() >= linear.sum() - 10 and (q[~ok] == 0).all()
+        excess = np.abs(q[ok] - J[ok]) / tol(A[ok])
+        print("%s quirk %d %s: Sw %d, largest |q - J| / tolerance %.3e" % (name, quirk, engine_state, Sw, float(excess.max())))
+        bad = np.nonzero(excess > 1)[0]
+        assert len(bad) == 0, (engine_state, len(bad), np.nonzero(ok)[0][bad[:5]], (q[ok] - J[ok])[bad[:5]])
+        classes = ("contacts", "near", "wide") + (("far",) if quirk and name == "m2" else ())
+        for k in classes:
+            assert (np.abs(parts[k][ok]) > tol(A[ok])).sum() >= 3, k
+    assert np.array_equal(got["fresh"][0], got["stepped"][0]) and np.array_equal(got["fresh"][1], got["stepped"][1])
     if name == "m1" and not quirk:
         # the prefix-sum identity against direct sums, at 64-slot tile boundaries and the ends of the longest contig
         long_c = LR.contigs_of(s)[int(s["id_c"][np.argmax(np.where(linear, s["l_cont"], 0))])]
@@ -119,6 +112,35 @@ def test_junctions_equal_restatement(name, quirk):
         direct = W.junction_direct(s, frags)
         for f in frags:
             assert direct[f] == (J[f], False, A[f]), f
+
+
+def test_junctions_with_stale_stripes():
+    """m1_cut (longest contig 500: one wave per tile would do) uploaded behind a begin_step on m1's layout: k_jn_mass runs 16 waves per
+    tile, of which almost every one finds nothing behind its first tile and leaves.  Equal to the fresh engine's scores word for word,
+    and to the restatement."""
+    P = problem("m1_cut")
+    W = window("m1_cut", False)
+    got = {}
+    for engine_state in ("fresh", "stale"):
+        e, s, Sw = engine_in(engine_state, P, before=problem("m1")["S_o_A_frags"])
+        try:
+            got[engine_state] = e.junction_scores_q()
+        finally:
+            e.close()
+        assert Sw == (16 if engine_state == "stale" else 1)
+        assert stripes_of(s["l_cont"].max(), len(s["id_c"])) == 1 and s["l_cont"].max() == 500
+    q, st = got["stale"]
+    assert np.array_equal(q, got["fresh"][0]) and np.array_equal(st, got["fresh"][1])
+    parts = {}
+    J, rst, A = W.junction_scores(s, parts)
+    assert np.array_equal(st, rst)
+    ok = st == JUNCTION_VALID
+    assert ok.sum() >= 8000 and (q[~ok] == 0).all()
+    excess = np.abs(q[ok] - J[ok]) / tol(A[ok])
+    print("m1_cut stale: Sw 16, largest |q - J| / tolerance %.3e" % float(excess.max()))
+    assert (excess <= 1).all(), int((excess > 1).sum())
+    for k in ("contacts", "near", "wide"):
+        assert (np.abs(parts[k][ok]) > tol(A[ok])).sum() >= 3, k
 
 
 # ---- links ---------------------------------------------------------------------------------------------------------------------------

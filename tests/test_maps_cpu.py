@@ -74,6 +74,39 @@ def test_expected_conserves_the_sum_of_lambda(name, max_px):
     assert R["terms"].sum() == S * (S - 1)
 
 
+@pytest.mark.parametrize("name", CASES)
+def test_chunked_brute_force_equals_the_one_that_holds_every_pair(name):
+    """map_reference.expected_chunked (the mid-size GPU tests' reference) against map_reference.reference on the small cases: the term
+    counts exactly, E to 1e-12 relative (the order of the float64 additions is all that differs), every max_px in one pass, blocks of rows
+    that divide neither the pixels nor the contigs.  Its far parts against a direct sum over the pairs of lambdas()."""
+    P = MR.case(name)
+    s = P["S_o_A_frags"]
+    far_slots = (1, 8)
+    got = MR.expected_chunked(P, s, MR.MAX_PX[name], far_slots, rows=37)
+    a, b, lam = MR.lambdas(name)
+    rec = MR.SR.sub_records(P["np_sub_frags_id"], P["np_sub_frags_len_bp"], P["np_sub_frags_accu"], s)
+    order, slots = MR.order_and_slots(P["np_sub_frags_id"], s)
+    assert np.array_equal(order, MR.order_of(P["np_sub_frags_id"], s))
+    slot_of = np.zeros(len(order), dtype=np.int64)
+    slot_of[order] = slots
+    f32 = np.float32
+    norm = ((rec[2][a] * rec[2][b]).astype(f32) / f32(P["mean_squared_frags_per_bin"])).astype(f32)
+    trans = np.maximum((f32(P["param_simu"][7]) * norm).astype(f32), f32(0)).astype(np.float64)
+    cis = rec[1][a] == rec[1][b]
+    for max_px in MR.MAX_PX[name]:
+        R, G = MR.reference(name, max_px), got[max_px]
+        assert (G["bin"], G["m"]) == (R["bin"], R["m"])
+        assert np.array_equal(G["terms"], R["terms"])
+        assert np.all(np.abs(G["expected"] - R["expected"]) <= 1e-12 * R["expected"])
+        moved = 0
+        for d in far_slots:
+            w = np.where(cis & (np.abs(slot_of[a] - slot_of[b]) >= d), lam - trans, 0.0)
+            want = MR.expected_from_lambda(a, b, w, R["pixel_of_sub"], R["m"])[0]
+            assert np.all(np.abs(G["far"][d] - want) <= 1e-12 * R["expected"]), d
+            moved += int((np.abs(want) > 1e-6 * R["expected"]).sum())
+        assert moved > 0
+
+
 def test_cases_reach_what_they_are_named_for():
     for name in CASES:
         P = MR.case(name)

@@ -87,6 +87,18 @@ def m2():
     return _with_state(P, s, par)
 
 
+def m3():
+    """n_sub 1, 3,000 fragments of ~150 bp -- few enough for a map of one sub-fragment per pixel (S <= 4096) -- and 4,000 contacts, a
+    30 kb window (~200 fragments); contigs of 1,500, 900, 400 (a ring) and 200 fragments, every third fragment reversed.  (The seed is one
+    whose closest pair of fragments expects 6e7 contacts: a pair that expects 2^31 or more does not fit the maps' fixed point.)"""
+    par = synth.make_param_simu(fact=2000.0, v_inter=0.01, d_max=30.0)
+    P = synth.make_problem(n_bins=3000, nnz=4000, n_sub=1, seed=34, contig_weights=(1500, 900, 400, 200), mean_len_bp=150.0, param=par)
+    s = {k: np.array(v) for k, v in P["S_o_A_frags"].items()}
+    s["ori"][1::3] = -1
+    s["circ"][s["id_c"] == 3] = 1
+    return _with_state(P, s, par)
+
+
 MID_PIECES = (3, 120, 1, 40, 2, 260, 4, 1, 75, 9, 2, 180, 1, 3, 60, 4, 1, 320, 2, 5, 7, 1, 150, 6)
 
 
