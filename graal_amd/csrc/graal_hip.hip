@@ -4102,6 +4102,8 @@ struct InBuf;                  // insert.h: graal_insertions' buffers and result
 void in_free(InBuf* b);
 struct FlBuf;                  // flips.h: graal_block_flips' buffers
 void fl_free(FlBuf* b);
+struct SwBuf;                  // swaps.h: graal_block_swaps' buffers
+void sw_free(SwBuf* b);
 struct MpBuf;                  // maps.h: graal_layout_maps' buffers and images
 void mp_free(MpBuf* b);
 
@@ -4308,6 +4310,7 @@ struct Ctx {
     EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
     InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
     FlBuf* fl = nullptr;          // graal_block_flips' buffers (flips.h; allocated by its first call)
+    SwBuf* sw = nullptr;          // graal_block_swaps' buffers (swaps.h; allocated by its first call)
     MpBuf* mp = nullptr;          // graal_layout_maps' buffers and images (maps.h; allocated by its first call)
 };
 
@@ -4885,6 +4888,7 @@ void graal_destroy(graal_ctx* h)
         ed_free(h->ed); h->ed = nullptr;
         in_free(h->ins); h->ins = nullptr;
         fl_free(h->fl); h->fl = nullptr;
+        sw_free(h->sw); h->sw = nullptr;
         mp_free(h->mp); h->mp = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
@@ -6342,5 +6346,6 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "links.h"
 #include "insert.h"
 #include "flips.h"
+#include "swaps.h"
 #include "edit.h"
 #include "maps.h"

@@ -53,6 +53,7 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_set_scan_path", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
            "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
+           "graal_block_swaps",
            "graal_layout_maps", "graal_layout_maps_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
@@ -61,6 +62,7 @@ JUNCTION_VALID, JUNCTION_END, JUNCTION_CIRCULAR, JUNCTION_NONFINITE = 0, 1, 2, 3
 LINK_VALID, LINK_NONFINITE = 0, 1   # graal_end_links' status bytes
 INSERT_VALID, INSERT_NONFINITE = 0, 1   # graal_insertions' status bytes
 FLIP_VALID, FLIP_WHOLE, FLIP_CIRCULAR, FLIP_NONFINITE = 0, 1, 2, 3   # graal_block_flips' status bytes
+SWAP_VALID, SWAP_CIRCULAR, SWAP_NONFINITE = 0, 1, 2   # graal_block_swaps' status bytes
 # graal_edit_layout's status words
 EDIT_OK, EDIT_BAD_CUT, EDIT_DUP_CUT, EDIT_BAD_END, EDIT_CIRCULAR, EDIT_END_TWICE, EDIT_SAME_CONTIG, EDIT_CYCLE = range(8)
 STEPS_ROW = 10   # GRAAL_STEPS_ROW: doubles per step in graal_steps' rows
@@ -143,6 +145,7 @@ def load():
         L.graal_insertions_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, ctypes.POINTER(ctypes.c_uint8), _i64p, _i64p,
                                              ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
         L.graal_block_flips.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
+        L.graal_block_swaps.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
         L.graal_layout_maps.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p]
         L.graal_layout_maps_fetch.argtypes = [ctypes.c_void_p, _f32p, _f32p, _f32p, _i32p]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -501,6 +504,33 @@ class Engine:
         self._ck(self._L.graal_block_flips(self._h, m, first.ctypes.data_as(_i32p), last.ctypes.data_as(_i32p), q.ctypes.data_as(_i64p),
                                            c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
                  "graal_block_flips")
+        return q, c, st
+
+    def block_swaps(self, first, mid, last):
+        """graal_block_swaps: for the disjoint spans (first[k] .. last[k]) of two adjacent runs X = first[k] .. mid[k] and Y = the
+        fragments behind mid[k] up to last[k] (three fragments of one contig in position order, mid before last) the score
+        S = logL(layout with Y in front of X) - logL(layout) in the exact arithmetic, as (S float64, contacts int64, status uint8) in the
+        caller's order; S is NaN unless status is SWAP_VALID (SWAP_CIRCULAR: the runs lie in a ring, SWAP_NONFINITE).  contacts = the
+        summed count among the changed pairs inside the window of the swapped layout.  Same preconditions and refusals as
+        junction_scores; spans that overlap, span two contigs, come in a wrong order or name no fragment raise GraalError.  Leaves the
+        step state alone."""
+        q, c, st = self.block_swaps_q(first, mid, last)
+        return np.where(st == SWAP_VALID, q.astype(np.float64) / Q_SCALE, np.nan), c, st
+
+    def block_swaps_q(self, first, mid, last):
+        """The same with the score as int64 Q: (q, contacts, status)."""
+        first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        mid = np.ascontiguousarray(mid, dtype=np.int32).reshape(-1)
+        last = np.ascontiguousarray(last, dtype=np.int32).reshape(-1)
+        if not len(first) == len(mid) == len(last):
+            raise ValueError("first, mid and last must have the same length")
+        m = len(first)
+        q = np.zeros(m, dtype=np.int64)
+        c = np.zeros(m, dtype=np.int64)
+        st = np.zeros(m, dtype=np.uint8)
+        self._ck(self._L.graal_block_swaps(self._h, m, first.ctypes.data_as(_i32p), mid.ctypes.data_as(_i32p), last.ctypes.data_as(_i32p),
+                                           q.ctypes.data_as(_i64p), c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+                 "graal_block_swaps")
         return q, c, st
 
     def layout_maps(self, max_px=2048):

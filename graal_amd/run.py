@@ -68,6 +68,15 @@ def main(argv=None):
     ap.add_argument("--flips", action="store_true", help="write flips.tsv into the output folder: every run of up to --flip-max-frags "
                                                          "fragments of the final layout with the log-likelihood its reversal in place "
                                                          "would add, the contacts behind it and a status (graal_amd.flips)")
+    ap.add_argument("--swap", action="store_true", help="after --scaffold, --polish and --insert, before --flip: swap the pairs of adjacent runs "
+                                                        "of up to --swap-max-frags fragments together, and of runs between weak junctions, "
+                                                        "that the data prefer in the other order, round by round (graal_amd.swaps); writes "
+                                                        "swap.tsv")
+    ap.add_argument("--swap-max-frags", type=int, default=8, help="with --swap / --swaps: the longest pair of runs tried, in fragments (default 8)")
+    ap.add_argument("--swap-min-score", type=float, default=0.0, help="with --swap: only swaps scoring above this (default 0)")
+    ap.add_argument("--swaps", action="store_true", help="write swaps.tsv into the output folder: every pair of adjacent runs of up to "
+                                                         "--swap-max-frags fragments together of the final layout with the log-likelihood "
+                                                         "their swap would add, the contacts behind it and a status (graal_amd.swaps)")
     ap.add_argument("--insertions", action="store_true", help="write insertions.tsv into the output folder: every insertion of a piece of "
                                                               "up to --insert-max-frags fragments into a junction of the final layout that the "
                                                               "contacts support, with the log-likelihood it would add (graal_amd.insert)")
@@ -151,6 +160,10 @@ def main(argv=None):
         from . import scaffold
         scaffold.write_scaffold_tsv(os.path.join(out, "insert.tsv"),
                                     scaffold.scaffold(smp, insert_max_frags=args.insert_max_frags, insert_min_score=args.insert_min_score))
+    if args.swap:
+        from . import swaps
+        swaps.write_swap_rounds_tsv(os.path.join(out, "swap.tsv"),
+                                    swaps.swap_rounds(smp, max_frags=args.swap_max_frags, min_score=args.swap_min_score))
     if args.flip:
         from . import flips
         flips.write_flip_rounds_tsv(os.path.join(out, "flip.tsv"),
@@ -176,6 +189,11 @@ def main(argv=None):
         eng = scaffold._engine(smp)
         soa = eng.download_frags()
         flips.write_flips_tsv(os.path.join(out, "flips.tsv"), flips.score_table(eng, soa, flips.tilings(soa, None, args.flip_max_frags)))
+    if args.swaps:
+        from . import scaffold, swaps
+        eng = scaffold._engine(smp)
+        soa = eng.download_frags()
+        swaps.write_swaps_tsv(os.path.join(out, "swaps.tsv"), swaps.score_table(eng, soa, swaps.tilings(soa, None, args.swap_max_frags)))
     if args.maps:
         from . import maps
         maps.write_maps(out, "", maps.layout_maps(smp, args.maps_max_px))

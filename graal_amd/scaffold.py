@@ -2,7 +2,8 @@
 
     scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None,
              insert_max_frags=None, insert_min_score=0.0,
-             flip_max_frags=None, flip_min_score=0.0)                                 -- the rounds; returns their record
+             flip_max_frags=None, flip_min_score=0.0,
+             swap_max_frags=None, swap_min_score=0.0)                                 -- the rounds; returns their record
     break_cycles(ea, eb, score, contig_of_end)                                            -- drop the weakest join of every cycle
     write_scaffold_tsv(path, record)                                                      -- one tab-separated row per round
 
@@ -26,6 +27,10 @@ was undone), graal_amd.flips.flip_rounds runs over the result with its own defau
 flip_max_frags fragments scoring above flip_min_score; its unit tilings are delimited by the weak junctions and by the joins made since
 the layout scaffold() started from: a piece joined the wrong way round is one unit).  Its rounds follow in the record, numbered on, their
 cuts and joins those of the flips' edits.
+With swap_max_frags set, under the same condition and BEFORE the flip rounds, graal_amd.swaps.swap_rounds runs over the result (pairs
+of adjacent runs of up to swap_max_frags fragments together scoring above swap_min_score, and unit tilings over the same marks): a run
+that sits a few places from where it belongs is moved there, so that a moved run that is also inverted is at its place when the flips
+look at it.  The joins those rounds made are marks of the flip rounds, as scaffold()'s own are.
 """
 import numpy as np
 
@@ -97,13 +102,13 @@ def plan_joins(mutual, min_score, contig_of_end):
 
 
 def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None, insert_max_frags=None, insert_min_score=0.0,
-             flip_max_frags=None, flip_min_score=0.0):
+             flip_max_frags=None, flip_min_score=0.0, swap_max_frags=None, swap_min_score=0.0):
     """Scaffold (and with cut_below, polish; with insert_max_frags, insert pieces) the engine's current layout; see the module's
     docstring.  Returns the record: a list of dicts with the keys COLUMNS, round 0 the layout as it came (kept 0 marks a round that was
     undone)."""
     obj = sampler_or_engine
     e = _engine(obj)
-    start = e.download_frags() if flip_max_frags is not None else None
+    start = e.download_frags() if flip_max_frags is not None or swap_max_frags is not None else None
     logl, nc = _evaluate(e)
     record = [{"round": 0, "cuts": 0, "joins": 0, "contigs": nc, "logL": logl, "kept": 1}]
     settled = False                # a round found no join, cut or insertion left
@@ -146,6 +151,13 @@ def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below
         if len(a) == 0 and len(icuts) == 0:
             settled = True             # (only cuts: no join and no insertion was on offer behind them)
             break
+    if swap_max_frags is not None and settled:
+        from . import flips, swaps
+        last = record[-1]["round"]
+        for row in swaps.swap_rounds(obj, max_frags=swap_max_frags, min_score=swap_min_score,
+                                     extra_marks=lambda now: flips.joined_marks(start, now))[1:]:
+            record.append({"round": last + row["round"], "cuts": row["cuts"], "joins": row["joins"], "contigs": row["contigs"],
+                           "logL": row["logL"], "kept": row["kept"]})
     if flip_max_frags is not None and settled:
         from . import flips
         last = record[-1]["round"]

@@ -439,6 +439,42 @@ int graal_insertions_fetch(graal_ctx* h, int32_t* piece, int32_t* after, uint8_t
 int graal_block_flips(graal_ctx* h, int32_t n_blocks, const int32_t* first, const int32_t* last, int64_t* q, int64_t* contacts,
                       uint8_t* status);
 
+/* Block swaps: the likelihood each swap of two adjacent runs of a contig would add, for a set of disjoint spans in one pass
+ * (graal_amd/csrc/swaps.h).  Swap k names two adjacent runs of ONE contig in position order: X = the fragments at positions
+ * pos[first[k]] .. pos[mid[k]], Y = those at pos[mid[k]] + 1 .. pos[last[k]] (pos[first[k]] <= pos[mid[k]] < pos[last[k]]; a one-fragment
+ * X has first == mid); the spans first .. last of a call are pairwise disjoint and come in any order.  Anything else -- an index out of
+ * range, two contigs, a wrong order, overlap -- returns GRAAL_E_ARG, the message names the first offending swap, and nothing is written.
+ * n_swaps == 0 returns GRAAL_OK.  Any move of a run inside its contig is a swap of that run with the adjacent run it passes.
+ * The SWAPPED layout of swap k is the current layout with Y first and X behind it inside the same bp interval: every fragment of X gets
+ * start_bp + len_bp(Y) and pos + |Y|, every fragment of Y start_bp - len_bp(X) and pos - |X|, ori is unchanged, prev / next follow;
+ * every other field and fragment keeps its value; the float32 centres through centre_kb from the new integer starts.  It is the layout
+ * graal_edit_layout writes for cuts before X, between X and Y and behind Y and the joins L.tail - Y.head, Y.tail - X.head and X.tail -
+ * R.head (L, R: the contig's pieces before and behind the span), up to the reversal of the whole chain its canonical order may apply (see
+ * graal_insertions).  A span that is its whole contig is VALID: X x Y still changes.
+ *   S(k) = logL(swapped layout) - logL(current layout)
+ * in the exact arithmetic with graal_junction_scores' / graal_end_links' / graal_block_flips' roundings:
+ *   - pairs inside X, pairs inside Y and pairs with no fragment in X u Y count as unchanged;
+ *   - every sub-fragment pair of X x Y, X x (rest of the contig) and Y x (rest of the contig) moves from its cis price to its cis price in
+ *     the swapped layout: a contact's term ob * (ln ex_new - ln ex_old) is rounded to Q once per contact, a fragment pair's mass -(sum of
+ *     ex_new - sum of ex_old), summed in float64 over its sub-fragment pairs with the moved run's fragment outer (X's for X x Y), once per
+ *     fragment pair; a pair beyond the window (reach_bp, as for the junction scores) both before and after is v_inter * norm both times
+ *     and is skipped, so only pairs within reach of one of the three breakpoints in one of the two layouts take part;
+ *   - orientation does not change and cis prices do not use the trans-branch indexing: GRAAL_MODE_REF_TRANS_ACCU changes nothing.
+ * int64 sums: bit-identical from call to call, for any grid and for any order of the swaps in the call.  A swap is scored alone: two
+ * swaps of one call with contacts between them each carry their own term, priced with only that swap applied.
+ * Outputs, n_swaps entries each in the caller's order: q[k] = S in Q; contacts[k] = the summed count of the contacts among the changed
+ * pairs whose centre distance in the swapped layout is below d_max (the evidence behind the score); status[k] one of the codes below
+ * (q = 0 unless VALID).
+ * The contact list may come in any order.  Needs sub-fragments, parameters, fragments and contacts.  Does not relabel and leaves the step
+ * state alone (ranked layout, carried total, a pending commit's correction, the proposal tables).  Device memory is O(fragments +
+ * sub-fragments + n_swaps).  GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats); GRAAL_E_STATE with an exchange or RCCL
+ * attached (one rank only). */
+#define GRAAL_SWAP_VALID 0
+#define GRAAL_SWAP_CIRCULAR 1   /* the runs lie in a circular contig: no score, q = 0 */
+#define GRAAL_SWAP_NONFINITE 2  /* a term was not finite, q = 0 */
+int graal_block_swaps(graal_ctx* h, int32_t n_swaps, const int32_t* first, const int32_t* mid, const int32_t* last, int64_t* q,
+                      int64_t* contacts, uint8_t* status);
+
 /* Layout maps: the observed contacts, the contacts the model expects and their residual, as images in the current genome order
  * (graal_amd/csrc/maps.h).
  * Order: contigs by ascending label, fragments by position inside a contig, a fragment's sub-fragments in stored order, reversed when
