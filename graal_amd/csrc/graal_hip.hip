@@ -4100,10 +4100,8 @@ struct EdBuf;                  // edit.h: graal_edit_layout's buffers
 void ed_free(EdBuf* b);
 struct InBuf;                  // insert.h: graal_insertions' buffers and results
 void in_free(InBuf* b);
-struct FlBuf;                  // flips.h: graal_block_flips' buffers
-void fl_free(FlBuf* b);
-struct SwBuf;                  // swaps.h: graal_block_swaps' buffers
-void sw_free(SwBuf* b);
+struct SpanBuf;                // span_moves.h: graal_block_flips' and graal_block_swaps' buffers
+void sp_free(SpanBuf* b);
 struct MpBuf;                  // maps.h: graal_layout_maps' buffers and images
 void mp_free(MpBuf* b);
 
@@ -4309,8 +4307,7 @@ struct Ctx {
     LnBuf* ln = nullptr;          // graal_end_links' buffers and its last result (links.h; allocated by its first call)
     EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
     InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
-    FlBuf* fl = nullptr;          // graal_block_flips' buffers (flips.h; allocated by its first call)
-    SwBuf* sw = nullptr;          // graal_block_swaps' buffers (swaps.h; allocated by its first call)
+    SpanBuf* sp = nullptr;        // graal_block_flips' and graal_block_swaps' buffers (span_moves.h; allocated by the first call of either)
     MpBuf* mp = nullptr;          // graal_layout_maps' buffers and images (maps.h; allocated by its first call)
 };
 
@@ -4887,8 +4884,7 @@ void graal_destroy(graal_ctx* h)
         ln_free(h->ln); h->ln = nullptr;
         ed_free(h->ed); h->ed = nullptr;
         in_free(h->ins); h->ins = nullptr;
-        fl_free(h->fl); h->fl = nullptr;
-        sw_free(h->sw); h->sw = nullptr;
+        sp_free(h->sp); h->sp = nullptr;
         mp_free(h->mp); h->mp = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
@@ -6345,7 +6341,6 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "junctions.h"
 #include "links.h"
 #include "insert.h"
-#include "flips.h"
-#include "swaps.h"
+#include "span_moves.h"
 #include "edit.h"
 #include "maps.h"

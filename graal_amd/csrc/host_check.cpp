@@ -1,7 +1,7 @@
 // host_check.cpp -- TEST ONLY.  Host build of frag_ops.h / strict_sets.h so that the CPU test-suite can compare the engine's
 // layout algebra (mutations, pieces, per-piece transforms, relation flags; the union set of a step, its classes of equal inputs
 // and its work units) with the oracle and with brute force without a GPU; and of the small pure headers beside them (scan_rows.h,
-// step_plan.h, map_shape.h).
+// step_plan.h, map_shape.h, span_check.h).
 // No likelihood code here and nothing in graal_amd/ loads this library.
 #include <stddef.h>
 #include <stdint.h>
@@ -14,6 +14,7 @@
 #include "scan_rows.h"
 #include "step_plan.h"
 #include "map_shape.h"
+#include "span_check.h"
 
 using namespace graal;
 
@@ -409,6 +410,20 @@ void hc_map_shape(int S, int max_px, const int32_t* ranks, int n_ranks, int32_t*
     const MapShape s = map_shape(S, max_px);
     out[0] = s.bin; out[1] = s.m;
     for (int i = 0; i < n_ranks; i++) out[2 + i] = map_pixel(ranks[i], s.bin);
+}
+
+// ---- the spans of a call (span_check.h).  kind: 0 graal_block_flips, 1 graal_block_swaps; info: nb rows of SpanInfo's twelve fields.
+// Returns -1 for a refused call, out[0..1] = the first offending span and the reason; else the number of scored spans, st[nb] the
+// status bytes and ids[0 .. m) the caller's indices of the scored spans in the records' order.
+int hc_span_check(int kind, int nb, const int32_t* info, int32_t* out, uint8_t* st, int32_t* ids)
+{
+    static_assert(sizeof(SpanInfo) == 12 * sizeof(int32_t), "tests/test_span_check_cpu.py lists the same fields");
+    const SpanChecked c = span_check(reinterpret_cast<const SpanInfo*>(info), nb, kind ? SPAN_SWAPS : SPAN_FLIPS);
+    out[0] = c.off; out[1] = (int32_t)c.why;
+    if (c.off >= 0) return -1;
+    for (int k = 0; k < nb; k++) st[k] = c.st[(size_t)k];
+    for (size_t j = 0; j < c.rec.size(); j++) ids[j] = c.rec[j].id;
+    return (int)c.rec.size();
 }
 
 } // extern "C"

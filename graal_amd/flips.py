@@ -19,19 +19,13 @@ on.  A round that lowers logL all the same (the float32 re-centring of graal_edi
 """
 import numpy as np
 
-from . import scaffold as _sc
-from .lib import FLIP_VALID, JUNCTION_VALID
+from . import scaffold as _sc   # noqa: F401  (part of this module's interface)
+from . import spans as _sp
+from .lib import FLIP_VALID
+from .spans import _contigs, joined_marks, weak_junction_marks   # noqa: F401  (the marks are part of this module's interface)
 
 ROUND_COLUMNS = ("round", "flips", "contigs", "logL", "kept")
 COLUMNS = ("first", "last", "contig", "pos_first", "pos_last", "frags", "score", "contacts", "status")
-
-
-def _contigs(soa):
-    """The linear contigs as arrays of fragments in position order, in label order."""
-    idc, pos, circ = (np.asarray(soa[k]) for k in ("id_c", "pos", "circ"))
-    order = np.lexsort((pos, idc))
-    cut = np.nonzero(np.diff(idc[order]))[0] + 1
-    return [m for m in np.split(order, cut) if len(m) and circ[m[0]] != 1]
 
 
 def tilings(soa, marks=None, max_units=8):
@@ -39,15 +33,7 @@ def tilings(soa, marks=None, max_units=8):
     offset, offset + m, ... units into each linear contig.  marks[f] true: a block may end after fragment f (None: after every
     fragment).  Blocks of a set are disjoint; every run of at most max_units whole units is a block of exactly one set; a block that is
     its whole contig is left out, and so is a set without blocks."""
-    contigs = _contigs(soa)
-    units = []                                   # per contig: the position of each unit's first fragment, and the contig's length
-    for m in contigs:
-        if marks is None:
-            starts = np.arange(len(m))
-        else:
-            mk = np.asarray(marks, dtype=bool)[m[:-1]]
-            starts = np.concatenate([[0], np.nonzero(mk)[0] + 1])
-        units.append(np.append(starts, len(m)))
+    contigs, units = _sp.unit_bounds(soa, marks)
     for m_units in range(1, int(max_units) + 1):
         for offset in range(m_units):
             first, last = [], []
@@ -63,63 +49,11 @@ def tilings(soa, marks=None, max_units=8):
                 yield np.concatenate(first).astype(np.int32), np.concatenate(last).astype(np.int32)
 
 
-def weak_junction_marks(engine, below=0.0):
-    """marks[f] true where the junction after f is scored (JUNCTION_VALID) and its score is below `below`."""
-    J, st = engine.junction_scores()
-    with np.errstate(invalid="ignore"):
-        return (st == JUNCTION_VALID) & (J < float(below))
-
-
-def joined_marks(soa_before, soa_now):
-    """marks[f] true for a junction (f, next[f]) of soa_now unless the two fragments were neighbours in the same relative orientation in
-    soa_before: the boundaries of the pieces joined since then."""
-    nx = np.asarray(soa_now["next"])
-    n = len(nx)
-    f = np.nonzero(nx >= 0)[0]
-    g = nx[f]
-    nb, pb = np.asarray(soa_before["next"]), np.asarray(soa_before["prev"])
-    same_f = np.asarray(soa_before["ori"])[f] == np.asarray(soa_now["ori"])[f]
-    same_g = np.asarray(soa_before["ori"])[g] == np.asarray(soa_now["ori"])[g]
-    kept = ((nb[f] == g) & same_f & same_g) | ((pb[f] == g) & ~same_f & ~same_g)
-    marks = np.zeros(n, dtype=bool)
-    marks[f[~kept]] = True
-    return marks
-
-
-def _stack(candidates):
-    if isinstance(candidates, tuple) and len(candidates) == 4 and not isinstance(candidates[0], tuple):
-        candidates = [candidates]
-    cols = [[np.asarray(c[i]).reshape(-1) for c in candidates] for i in range(4)]
-    if not cols[0]:
-        return (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0), np.zeros(0, np.uint8))
-    return (np.concatenate(cols[0]).astype(np.int64), np.concatenate(cols[1]).astype(np.int64), np.concatenate(cols[2]).astype(np.float64),
-            np.concatenate(cols[3]).astype(np.uint8))
-
-
 def plan_flips(candidates, soa, reach_bp, min_score=0.0):
     """(first, last, score) of the flips to apply.  candidates: one (first, last, score, status) tuple of arrays per scored call (or a
     single such tuple).  Taken: FLIP_VALID blocks with score > min_score, best first (ties: the lower (first, last)); a block that
     overlaps an accepted block of its contig, or whose bp interval lies within reach_bp of one, is skipped."""
-    first, last, score, st = _stack(candidates)
-    with np.errstate(invalid="ignore"):
-        ok = (st == FLIP_VALID) & (score > float(min_score))
-    first, last, score = first[ok], last[ok], score[ok]
-    idc, start, ln = (np.asarray(soa[k], dtype=np.int64) for k in ("id_c", "start_bp", "len_bp"))
-    order = np.lexsort((last, first, -score))
-    taken = {}                                   # contig -> accepted (s0, e1)
-    out = []
-    for i in order:
-        f, l = int(first[i]), int(last[i])
-        s0, e1 = int(start[f]), int(start[l] + ln[l])
-        mine = taken.setdefault(int(idc[f]), [])
-        if any(s0 - b <= reach_bp and a - e1 <= reach_bp for a, b in mine):   # (overlap: both gaps negative)
-            continue
-        mine.append((s0, e1))
-        out.append((f, l, float(score[i])))
-    if not out:
-        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0)
-    a, b, c = zip(*out)
-    return np.array(a, np.int64), np.array(b, np.int64), np.array(c, np.float64)
+    return _sp.plan(candidates, 4, FLIP_VALID, soa, reach_bp, min_score)
 
 
 def flip_edit(soa, first, last):
@@ -169,60 +103,15 @@ def flip_rounds(sampler_or_engine, max_frags=8, junction_below=0.0, max_units=3,
     (plan_flips), applies them in one edit_layout call and evaluates the layout in full.  A round that lowers logL is undone and the
     rounds stop there; they also stop when nothing is planned.  reach_bp: the window in bp (default: from the engine's parameters).
     Returns the record: a list of dicts with the keys ROUND_COLUMNS (and the cuts and joins of the edit), round 0 the layout as it came."""
-    obj = sampler_or_engine
-    e = _sc._engine(obj)
-    if reach_bp is None:
-        par = getattr(e, "param", None)
-        if par is None:
-            raise ValueError("flip_rounds: reach_bp is needed (the engine's parameters were not set through this Engine object)")
-        # (the engine's reach_bp(h) in csrc/graal_hip.hip, restated: ceil(d_max * 1000) + 1000 from the float32 d_max.  The planner
-        # only needs a bound that is not smaller: a larger one keeps accepted flips further apart, never closer.)
-        reach_bp = int(np.ceil(np.float64(np.float32(par[5])) * 1000.0)) + 1000
-    logl, nc = _sc._evaluate(e)
-    record = [{"round": 0, "flips": 0, "cuts": 0, "joins": 0, "contigs": nc, "logL": logl, "kept": 1}]
-    for r in range(1, int(rounds) + 1):
-        before = e.download_frags()
-        marks = weak_junction_marks(e, junction_below)
-        if extra_marks is not None:
-            marks = marks | np.asarray(extra_marks(before), dtype=bool)
-        cands = []
-        for sets in (tilings(before, None, max_frags), tilings(before, marks, max_units) if marks.any() else ()):
-            for first, last in sets:
-                F, _, st = e.block_flips(first, last)
-                cands.append((first, last, F, st))
-        first, last, _ = plan_flips(cands, before, reach_bp, min_score)
-        if len(first) == 0:
-            break
-        cuts, joins = flip_edit(before, first, last)
-        _sc._edit(obj, e, cuts, joins)
-        new_logl, nc = _sc._evaluate(e)
-        row = {"round": r, "flips": int(len(first)), "cuts": int(len(cuts)), "joins": int(len(joins)), "contigs": nc, "logL": new_logl,
-               "kept": 1}
-        if not new_logl >= logl:       # (NaN included)
-            row["kept"] = 0
-            record.append(row)
-            _sc._restore(obj, e, before)
-            _sc._evaluate(e)
-            break
-        record.append(row)
-        logl = new_logl
-    return record
+    return _sp.run_rounds(sampler_or_engine, "flip", "block_flips", tilings, plan_flips, flip_edit, max_frags, junction_below, max_units,
+                          min_score, rounds, reach_bp, extra_marks)
 
 
 def write_flip_rounds_tsv(path, record):
     """flip_rounds' record as a TSV file with a header line; logL with 17 significant digits."""
-    with open(path, "w") as fh:
-        fh.write("\t".join(ROUND_COLUMNS) + "\n")
-        for row in record:
-            fh.write("\t".join([str(int(row[c])) for c in ROUND_COLUMNS[:3]] + [repr(float(row["logL"])), str(int(row["kept"]))]) + "\n")
-    return len(record)
+    return _sp.write_rounds_tsv(path, record, ROUND_COLUMNS)
 
 
 def write_flips_tsv(path, table):
     """score_table's columns as a TSV file with a header line; scores with 17 significant digits (nan where there is none)."""
-    n = len(table["first"])
-    with open(path, "w") as fh:
-        fh.write("\t".join(COLUMNS) + "\n")
-        for i in range(n):
-            fh.write("\t".join(repr(float(table[c][i])) if c == "score" else str(int(table[c][i])) for c in COLUMNS) + "\n")
-    return n
+    return _sp.write_table_tsv(path, table, COLUMNS)

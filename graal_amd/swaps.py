@@ -20,9 +20,9 @@ round that lowers logL all the same (the float32 re-centring of graal_edit_layou
 """
 import numpy as np
 
-from . import scaffold as _sc
-from .flips import _contigs, joined_marks, weak_junction_marks   # noqa: F401  (the marks are part of this module's interface too)
+from . import spans as _sp
 from .lib import SWAP_VALID
+from .spans import _contigs, joined_marks, weak_junction_marks   # noqa: F401  (the marks are part of this module's interface too)
 
 ROUND_COLUMNS = ("round", "swaps", "contigs", "logL", "kept")
 COLUMNS = ("first", "mid", "last", "contig", "pos_first", "pos_mid", "pos_last", "frags_x", "frags_y", "score", "contacts", "status")
@@ -34,15 +34,7 @@ def tilings(soa, marks=None, max_units=8):
     run may end after fragment f (None: after every fragment).  Spans of a set are disjoint; every pair of adjacent runs of at most
     max_units whole units together is a swap of exactly one set (a span that is its whole contig too); a set without swaps is left
     out."""
-    contigs = _contigs(soa)
-    units = []                                   # per contig: the position of each unit's first fragment, and the contig's length
-    for m in contigs:
-        if marks is None:
-            starts = np.arange(len(m))
-        else:
-            mk = np.asarray(marks, dtype=bool)[m[:-1]]
-            starts = np.concatenate([[0], np.nonzero(mk)[0] + 1])
-        units.append(np.append(starts, len(m)))
+    contigs, units = _sp.unit_bounds(soa, marks)
     for m_units in range(2, int(max_units) + 1):
         for split in range(1, m_units):
             for offset in range(m_units):
@@ -56,41 +48,11 @@ def tilings(soa, marks=None, max_units=8):
                     yield tuple(np.concatenate(x).astype(np.int32) for x in (first, mid, last))
 
 
-def _stack(candidates):
-    if isinstance(candidates, tuple) and len(candidates) == 5 and not isinstance(candidates[0], tuple):
-        candidates = [candidates]
-    cols = [[np.asarray(c[i]).reshape(-1) for c in candidates] for i in range(5)]
-    if not cols[0]:
-        z = np.zeros(0, np.int64)
-        return z, z, z, np.zeros(0), np.zeros(0, np.uint8)
-    return tuple(np.concatenate(cols[i]).astype(t) for i, t in enumerate((np.int64, np.int64, np.int64, np.float64, np.uint8)))
-
-
 def plan_swaps(candidates, soa, reach_bp, min_score=0.0):
     """(first, mid, last, score) of the swaps to apply.  candidates: one (first, mid, last, score, status) tuple of arrays per scored
     call (or a single such tuple).  Taken: SWAP_VALID swaps with score > min_score, best first (ties: the lower (first, mid, last)); a
     swap whose span overlaps an accepted span of its contig, or whose bp interval lies within reach_bp of one, is skipped."""
-    first, mid, last, score, st = _stack(candidates)
-    with np.errstate(invalid="ignore"):
-        ok = (st == SWAP_VALID) & (score > float(min_score))
-    first, mid, last, score = first[ok], mid[ok], last[ok], score[ok]
-    idc, start, ln = (np.asarray(soa[k], dtype=np.int64) for k in ("id_c", "start_bp", "len_bp"))
-    order = np.lexsort((last, mid, first, -score))
-    taken = {}                                   # contig -> accepted (s0, e1)
-    out = []
-    for i in order:
-        f, m, l = int(first[i]), int(mid[i]), int(last[i])
-        s0, e1 = int(start[f]), int(start[l] + ln[l])
-        mine = taken.setdefault(int(idc[f]), [])
-        if any(s0 - b <= reach_bp and a - e1 <= reach_bp for a, b in mine):   # (overlap: both gaps negative)
-            continue
-        mine.append((s0, e1))
-        out.append((f, m, l, float(score[i])))
-    if not out:
-        z = np.zeros(0, np.int64)
-        return z, z, z, np.zeros(0)
-    a, b, c, d = zip(*out)
-    return np.array(a, np.int64), np.array(b, np.int64), np.array(c, np.int64), np.array(d, np.float64)
+    return _sp.plan(candidates, 5, SWAP_VALID, soa, reach_bp, min_score)
 
 
 def swap_edit(soa, first, mid, last):
@@ -142,59 +104,15 @@ def swap_rounds(sampler_or_engine, max_frags=8, junction_below=0.0, max_units=3,
     (plan_swaps), applies them in one edit_layout call and evaluates the layout in full.  A round that lowers logL is undone and the
     rounds stop there; they also stop when nothing is planned.  reach_bp: the window in bp (default: from the engine's parameters).
     Returns the record: a list of dicts with the keys ROUND_COLUMNS (and the cuts and joins of the edit), round 0 the layout as it came."""
-    obj = sampler_or_engine
-    e = _sc._engine(obj)
-    if reach_bp is None:
-        par = getattr(e, "param", None)
-        if par is None:
-            raise ValueError("swap_rounds: reach_bp is needed (the engine's parameters were not set through this Engine object)")
-        # (the engine's reach_bp(h) restated, as in flips.flip_rounds: a larger bound keeps accepted swaps further apart, never closer)
-        reach_bp = int(np.ceil(np.float64(np.float32(par[5])) * 1000.0)) + 1000
-    logl, nc = _sc._evaluate(e)
-    record = [{"round": 0, "swaps": 0, "cuts": 0, "joins": 0, "contigs": nc, "logL": logl, "kept": 1}]
-    for r in range(1, int(rounds) + 1):
-        before = e.download_frags()
-        marks = weak_junction_marks(e, junction_below)
-        if extra_marks is not None:
-            marks = marks | np.asarray(extra_marks(before), dtype=bool)
-        cands = []
-        for sets in (tilings(before, None, max_frags), tilings(before, marks, max_units) if marks.any() else ()):
-            for first, mid, last in sets:
-                S, _, st = e.block_swaps(first, mid, last)
-                cands.append((first, mid, last, S, st))
-        first, mid, last, _ = plan_swaps(cands, before, reach_bp, min_score)
-        if len(first) == 0:
-            break
-        cuts, joins = swap_edit(before, first, mid, last)
-        _sc._edit(obj, e, cuts, joins)
-        new_logl, nc = _sc._evaluate(e)
-        row = {"round": r, "swaps": int(len(first)), "cuts": int(len(cuts)), "joins": int(len(joins)), "contigs": nc, "logL": new_logl,
-               "kept": 1}
-        if not new_logl >= logl:       # (NaN included)
-            row["kept"] = 0
-            record.append(row)
-            _sc._restore(obj, e, before)
-            _sc._evaluate(e)
-            break
-        record.append(row)
-        logl = new_logl
-    return record
+    return _sp.run_rounds(sampler_or_engine, "swap", "block_swaps", tilings, plan_swaps, swap_edit, max_frags, junction_below, max_units,
+                          min_score, rounds, reach_bp, extra_marks)
 
 
 def write_swap_rounds_tsv(path, record):
     """swap_rounds' record as a TSV file with a header line; logL with 17 significant digits."""
-    with open(path, "w") as fh:
-        fh.write("\t".join(ROUND_COLUMNS) + "\n")
-        for row in record:
-            fh.write("\t".join([str(int(row[c])) for c in ROUND_COLUMNS[:3]] + [repr(float(row["logL"])), str(int(row["kept"]))]) + "\n")
-    return len(record)
+    return _sp.write_rounds_tsv(path, record, ROUND_COLUMNS)
 
 
 def write_swaps_tsv(path, table):
     """score_table's columns as a TSV file with a header line; scores with 17 significant digits (nan where there is none)."""
-    n = len(table["first"])
-    with open(path, "w") as fh:
-        fh.write("\t".join(COLUMNS) + "\n")
-        for i in range(n):
-            fh.write("\t".join(repr(float(table[c][i])) if c == "score" else str(int(table[c][i])) for c in COLUMNS) + "\n")
-    return n
+    return _sp.write_table_tsv(path, table, COLUMNS)

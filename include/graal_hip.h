@@ -405,7 +405,7 @@ int graal_insertions_fetch(graal_ctx* h, int32_t* piece, int32_t* after, uint8_t
                            int64_t cap);
 
 /* Block flips: the likelihood each in-place reversal of a block of fragments would add, for a set of disjoint blocks in one pass
- * (graal_amd/csrc/flips.h).  Block k holds the fragments of ONE contig at positions pos[first[k]] .. pos[last[k]] (pos[first[k]] <=
+ * (graal_amd/csrc/span_moves.h).  Block k holds the fragments of ONE contig at positions pos[first[k]] .. pos[last[k]] (pos[first[k]] <=
  * pos[last[k]]; a one-fragment block has first == last); the blocks of a call are pairwise disjoint and come in any order.  Anything else
  * -- an index out of range, two contigs, reversed order, overlap -- returns GRAAL_E_ARG, the message names the first offending block, and
  * nothing is written.  n_blocks == 0 returns GRAAL_OK.
@@ -440,7 +440,7 @@ int graal_block_flips(graal_ctx* h, int32_t n_blocks, const int32_t* first, cons
                       uint8_t* status);
 
 /* Block swaps: the likelihood each swap of two adjacent runs of a contig would add, for a set of disjoint spans in one pass
- * (graal_amd/csrc/swaps.h).  Swap k names two adjacent runs of ONE contig in position order: X = the fragments at positions
+ * (graal_amd/csrc/span_moves.h).  Swap k names two adjacent runs of ONE contig in position order: X = the fragments at positions
  * pos[first[k]] .. pos[mid[k]], Y = those at pos[mid[k]] + 1 .. pos[last[k]] (pos[first[k]] <= pos[mid[k]] < pos[last[k]]; a one-fragment
  * X has first == mid); the spans first .. last of a call are pairwise disjoint and come in any order.  Anything else -- an index out of
  * range, two contigs, a wrong order, overlap -- returns GRAAL_E_ARG, the message names the first offending swap, and nothing is written.
