@@ -2,7 +2,9 @@
 same draws in the same double-precision operation order.  Where the two can still differ -- the GPU's exp / log (model_math.h) and the
 float32 pow / exp of the contact model round differently from libm in the last place -- the reference FLAGS the draw: a uniform within
 1e-6 relative of the boundary it was compared with.  A flagged window pair may differ; a flagged background chunk may differ as a whole
-(one tipped decision shifts the rest of its stream).  Not product code."""
+(one tipped decision shifts the rest of its stream).  A background skip g = -ln(u) / Lmax is flagged near an integer >= 1 and near the
+chunk's remaining width only: g > 0 always, so floor(g) = 0 cannot tip at 0, and flagging there (as an earlier version did) excused
+almost every chunk of a row with a large Lmax.  That makes the reference stricter, never laxer.  Not product code."""
 import math
 
 import numpy as np
@@ -67,18 +69,28 @@ def uniforms_from_words(w):
 
 
 class Stream:
-    """The uniform stream of one counter family (c0, c1, tag, n = 0, 1, ...)."""
+    """The uniform stream of one counter family (c0, c1, tag, n = 0, 1, ...).  batch > 1 computes that many counters ahead in one
+    vectorised call, twice as many at every refill up to 1024 (the same values: the stream is a function of the counter alone) -- for
+    the long streams of background chunks."""
 
-    def __init__(self, c0, c1, tag, seed):
+    def __init__(self, c0, c1, tag, seed, batch=1):
         self.c0, self.c1, self.tag, self.seed, self.n, self.buf = int(c0), int(c1), int(tag), int(seed), 0, []
+        self.batch = int(batch)
         self.flag = False
 
     def next(self):
         if not self.buf:
-            w = philox_scalar((self.c0, self.c1, self.tag, self.n), (self.seed & M32, (self.seed >> 32) & M32))
-            self.n += 1
-            u0, u1 = uniforms_from_words([np.uint64(x) for x in w])
-            self.buf = [float(u1), float(u0)]
+            if self.batch > 1:
+                n = np.arange(self.n, self.n + self.batch, dtype=np.uint64)
+                u0, u1 = uniforms_from_words(philox4x32(self.c0, self.c1, self.tag, n, self.seed))
+                self.n += self.batch
+                self.batch = min(2 * self.batch, 1024)
+                self.buf = np.stack([u0, u1], axis=1).ravel()[::-1].tolist()
+            else:
+                w = philox_scalar((self.c0, self.c1, self.tag, self.n), (self.seed & M32, (self.seed >> 32) & M32))
+                self.n += 1
+                u0, u1 = uniforms_from_words([np.uint64(x) for x in w])
+                self.buf = [float(u1), float(u0)]
         return self.buf.pop()
 
     def near(self, x, y, scale=None):
@@ -197,9 +209,11 @@ def pair_lambda(rec, a, b, nfpb, param):
     return np.maximum(lam, f32(0)).astype(np.float64)
 
 
-def simulate(sub_id, sub_len_kb, sub_accu, nfpb, param, state, seed):
+def simulate(sub_id, sub_len_kb, sub_accu, nfpb, param, state, seed, rows=None):
     """-> (row, col, count, flagged_pairs, flagged_chunks): the list graal_simulate_contacts returns, and the draws that may differ
-    from the GPU's by a last-place rounding (window pairs (a, b); background chunks (a, k))."""
+    from the GPU's by a last-place rounding (window pairs (a, b); background chunks (a, k)).
+    rows: restate these rows only (rows are independent: the counters are (a, b, 0, .) and (a, k, 1, .)) -- the same five values,
+    restricted to them.  For layouts whose dense rows make the loop over every row too slow."""
     param = np.asarray(param, dtype=np.float32).reshape(8)
     rec = sub_records(sub_id, sub_len_kb, sub_accu, state)
     centre, label, acc, lbp = rec
@@ -209,8 +223,10 @@ def simulate(sub_id, sub_len_kb, sub_accu, nfpb, param, state, seed):
     amax = max(amax, 1)
     out = {}
     flagged_pairs, flagged_chunks = set(), set()
+    todo = range(S) if rows is None else sorted({int(a) for a in rows})
+    assert all(0 <= a < S for a in todo)
     # window pairs, vectorised over each row's columns: the first uniform decides most of them (count 0)
-    for a in range(S):
+    for a in todo:
         if label[a] < 0:
             continue
         b = np.arange(a + 1, S)
@@ -234,7 +250,7 @@ def simulate(sub_id, sub_len_kb, sub_accu, nfpb, param, state, seed):
                 out[(a, int(w[j]))] = c
     # background chunks
     v_inter = param[7]
-    for a in range(S):
+    for a in todo:
         if label[a] < 0:
             continue
         lmax_f = f32(v_inter * f32(f32(acc[a] * amax) / f32(nfpb)))
@@ -244,13 +260,14 @@ def simulate(sub_id, sub_len_kb, sub_accu, nfpb, param, state, seed):
         pm = 1.0 - math.exp(-lmax)
         for k in range((a + 1) // CHUNK, (S - 1) // CHUNK + 1):
             c_begin, c_end = max(a + 1, k * CHUNK), min(S, (k + 1) * CHUNK)
-            st = Stream(a, k, 1, seed)
+            st = Stream(a, k, 1, seed, batch=16)
             j = c_begin - 1
             while True:
                 g = -math.log(st.next()) / lmax
                 # (lambda_max is the same float32 on both sides and log's error is ~1e-16 relative: a skip can only tip within a few
-                # 1e-16 g of an integer; flag 1e-9 g)
-                st.near(g, round(g), SKIP_TOL / TOL * max(1.0, g))
+                # 1e-16 g of an integer >= 1; flag 1e-9 g.  Not at 0: g > 0, floor(g) = 0 holds on both sides)
+                if round(g) >= 1:
+                    st.near(g, round(g), SKIP_TOL / TOL * max(1.0, g))
                 st.near(g, float(c_end - j - 1), SKIP_TOL / TOL * max(1.0, g))
                 if not g < float(c_end - j - 1):
                     break

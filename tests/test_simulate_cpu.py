@@ -115,6 +115,79 @@ def test_inactive_fragments_get_nothing():
     assert len(r) > 0 and not np.isin(r, dead).any() and not np.isin(c, dead).any()
 
 
+def test_restricted_rows_equal_full():
+    """R.simulate(rows=...) returns, for every row of a small case, exactly what the full call returns for that row -- entries in order
+    and flags -- and nothing of any other row."""
+    P, par = _small(n_bins=20, n_sub=3, accu=("random", 1, 4), v_inter=0.3, fact=2000.0)
+    s = {k: np.array(v) for k, v in P["S_o_A_frags"].items()}
+    s["ori"][::3] = -1
+    s["activ"][4] = 0
+    args = (P["np_sub_frags_id"], P["np_sub_frags_len_bp"], P["np_sub_frags_accu"], P["mean_squared_frags_per_bin"], par, s)
+    S = P["init_n_sub_frags"]
+
+    def of_rows(full, rows):
+        r, c, v, fp, fc = full
+        m = np.isin(r, rows)
+        return r[m], c[m], v[m], {x for x in fp if x[0] in rows}, {x for x in fc if x[0] in rows}
+
+    def same(x, y):
+        return all(np.array_equal(a, b) and a.dtype == b.dtype for a, b in zip(x[:3], y[:3])) and x[3] == y[3] and x[4] == y[4]
+
+    # (TOL widened for this test alone, so that flags exist to be compared: at 1e-6 this small case has none)
+    full = R.simulate(*args, seed=9)
+    tol = R.TOL
+    R.TOL = 1e-2
+    try:
+        flagged = R.simulate(*args, seed=9)
+        assert len(flagged[3]) > 3 and len(flagged[4]) > 3 and len(flagged[0]) == len(full[0]) > 300
+        for a in range(S):
+            assert same(R.simulate(*args, seed=9, rows=[a]), of_rows(flagged, [a])), a
+        some = [S - 1, 0, 17, 17, 30]
+        assert same(R.simulate(*args, seed=9, rows=some), of_rows(flagged, some))
+    finally:
+        R.TOL = tol
+    assert same(R.simulate(*args, seed=9, rows=range(S)), full)
+    assert len(R.simulate(*args, seed=9, rows=[])[0]) == 0
+
+
+def test_skip_near_zero_is_not_flagged():
+    """A skip g > 0 cannot tip floor(g) = 0, so a row whose Lmax makes every skip tiny has no chunk flagged for it: the hubs layout's
+    row 3 (Lmax = 125000, g ~ 1e-5, about 9000 skips within the old 1e-9 of 0 by chance ~ 1e-4 each)."""
+    from tests.test_simulate_rows_gpu import hubs_reference
+    assert not any(k[0] == 3 for k in hubs_reference()[4])
+
+
+def test_hubs_layout_reaches_every_branch():
+    """The conditions tests/test_simulate_rows_gpu.py relies on, on the reference alone: the row lengths its constants name, one row in
+    each branch of the GPU's row sorter and at each edge between them, no flagged draw in a hub row, a background pair in the rejection
+    loop of the zero-truncated Poisson, and thinning under heavy rejection."""
+    from tests.test_simulate_rows_gpu import HUBS, ORDINARY, ROWS, hubs_problem, hubs_reference, reference_row
+    P, par = hubs_problem()
+    r, c, v, fp, fc = hubs_reference()
+    assert set(np.unique(r)) <= set(ROWS)
+    assert np.all(r < c) and np.all(v > 0) and np.all(np.diff(r.astype(np.int64) * P["init_n_sub_frags"] + c) > 0)
+    n = {a: len(reference_row(a)[0]) for a in ROWS}
+    assert {h: n[h] for h in HUBS} == {h: x[1] for h, x in HUBS.items()}
+    lengths = sorted(n[h] for h in HUBS)
+    assert 256 in lengths and 257 in lengths and 4096 in lengths and 4097 in lengths
+    assert any(257 <= x <= 4096 and x & (x - 1) for x in lengths)          # bitonic padding
+    assert any(4097 <= x <= 8192 for x in lengths) and any(x > 8192 for x in lengths)
+    # exact equality on the GPU needs hub rows without a flagged draw: if this fails, choose another hub id or seed
+    assert not [p for p in fp if p[0] in HUBS] and not [k for k in fc if k[0] in HUBS], (fp, fc)
+    # background pairs (not in the cis window) with lambda >= 10 and a count: sim_ztp's rejection loop around sim_poisson
+    centre, label, acc, lbp = R.sub_records(P["np_sub_frags_id"], P["np_sub_frags_len_bp"], P["np_sub_frags_accu"], P["S_o_A_frags"])
+    window = (label[r] == label[c]) & (np.abs(centre[c] - centre[r]).astype(np.float32) < par[5])
+    lam_b = float(par[7]) * acc[r] * acc[c]
+    assert (~window & (lam_b >= R.PTRS_MIN)).sum() >= 10 and lam_b[~window].max() > 1e5
+    # ordinary rows: RF count 1, Lmax = v_inter * 25000 = 5 against lambda_b = 2e-4 for all but the hub columns
+    assert all(acc[a] == 1 for a in ORDINARY) and np.median(acc) == 1
+    assert acc.max() / np.median(acc) >= 1000                              # = Lmax / lambda_b: v_inter and the row's RF count cancel
+    assert sum(n[a] > 0 for a in ORDINARY) >= 8
+    # ... and they accept: a background entry in an ordinary row, in a column of RF count 1 (acceptance 4e-5 per candidate) or not
+    m = np.isin(r, ORDINARY) & ~window
+    assert m.sum() >= 4, m.sum()
+
+
 def _failed_handle():
     """A handle whose graal_create failed for lack of a GPU (it is returned anyway, so that graal_last_error works)."""
     import ctypes

@@ -51,6 +51,7 @@ def test_equals_reference(name):
     assert nnz > 500
     assert unexplained == [], unexplained[:10]
     assert len(diff) <= math.ceil(1e-4 * nnz), (len(diff), nnz)
+    _well_formed(*got, P["init_n_sub_frags"])            # (R.compare ignores order and duplicates)
     if name == "chunks":
         S = P["init_n_sub_frags"]
         assert S > 2 * R.CHUNK
