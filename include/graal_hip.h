@@ -118,6 +118,9 @@ int graal_eval_full_params(graal_ctx* h, const float* param8, int64_t stats[8], 
  * the step gave up waiting for another, a work list overflowed) adds 2^32 to the FIRST flag word: a summed first flag >= 2^32 means "no scores
  * this step, on any rank" -- every rank sees it, none may use the sums (graal_eval_candidates_x with graal_attach_rccl returns an error then).
  * max_id must be the value returned by graal_relabel_contigs for the current layout.
+ * A neighbour fB[k] == fA scores 0 for all 13 candidates -- also for ops 0, 1 and 8, which never look at fB and which
+ * sub_compute_likelihood prices like any other (a deliberate deviation: DESIGN.md section 2, item 4;
+ * tests/test_ref_kernels_gpu.py holds it against the reference's recorded values).
  * Replaces new_perform_modificationS + 13 x sub_compute_likelihood per neighbour
  * (cuda_lib_gl.py:2392-2546). */
 int graal_eval_candidates_q(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int32_t max_id, int32_t rank,

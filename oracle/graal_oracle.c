@@ -6,13 +6,15 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library;
  * the product path (graal_amd/) never does.
  *
- * Parity pin: the reference is CUDA + PyCUDA (Python 2) and cannot be built or run in this
- * image without writing stand-ins for <curand_kernel.h> and the CUDA runtime, which is not
- * allowed; the reference ships no tests or golden vectors.  This restatement is pinned to the
- * worked known answers recorded from the reference's own kernels in SURVEY.md Appendix E
- * (tests/golden/appendix_e.json, tests/test_oracle_golden.py) and to the reference's implied
- * invariants (delta kernel == full-after - full-before; structural checks of
- * cuda_lib_gl.py:1530-1537).  Host libm (powf/expf/log) differs from CUDA's by a few ulp.
+ * Parity pin: the reference's kernel file itself, compiled for the host (oracle/ref_host/,
+ * oracle/ref_kernels.py; recipe in oracle/Makefile).  tests/test_ref_kernels_cpu.py holds every
+ * function below to it: integer results equal, float32 model values and per-pixel float64
+ * log-likelihoods bit for bit, sums to their summation order -- live where the reference's
+ * sources are, and everywhere against outputs recorded from it (tests/golden/ref_*.npz).  Also
+ * the worked answers of SURVEY.md Appendix E (tests/golden/appendix_e.json) and the reference's
+ * implied invariants (delta kernel == full-after - full-before; structural checks of
+ * cuda_lib_gl.py:1530-1537).  Not pinned on either side: nvcc's FMA contraction and CUDA's libm,
+ * which differ from the host's powf/expf/log by a few ulp.
  *
  * Layout conventions (all int32 unless stated):
  *   frag SoA  : 14 arrays of n_frags, order = struct frag (kernels3.cu:9-24)
@@ -740,3 +742,4 @@ float or_rippe_circ(float s, float s_tot, const float *param)
     return rippe_contacts_circ(s, s_tot, (const param_t *)param);
 }
 double or_lik(double ex, double ob) { return lik_double(ex, ob); }
+float or_factorial(float n) { return factorial_f(n); }

@@ -56,6 +56,7 @@ def lib():
         L.or_rippe.restype = ctypes.c_float
         L.or_rippe_circ.restype = ctypes.c_float
         L.or_lik.restype = ctypes.c_double
+        L.or_factorial.restype = ctypes.c_float
         _lib = L
     return _lib
 
@@ -190,6 +191,10 @@ def lik(ex, ob):
     return float(lib().or_lik(ctypes.c_double(ex), ctypes.c_double(ob)))
 
 
+def factorial(n):
+    return float(lib().or_factorial(ctypes.c_float(n)))
+
+
 class OracleSampler:
     """Host logic of cuda_lib_gl.sampler (start_EM path), restated literally over DenseOracle.
 
@@ -200,7 +205,7 @@ class OracleSampler:
     mean_value_trans, plus param_simu (8 floats; SURVEY H6: the fit is an input of the hot path).
     """
 
-    def __init__(self, problem, rng, fix_trans_accu=False):
+    def __init__(self, problem, rng, fix_trans_accu=False, dev_class=DenseOracle):
         p = problem
         self.rng = rng
         self.o = 0
@@ -232,7 +237,7 @@ class OracleSampler:
             for i in range(0, da[3]):
                 self.hic_matrix[da[i], :] = self.mean_value_trans
                 self.hic_matrix[:, da[i]] = self.mean_value_trans
-        self.dev = DenseOracle(self.hic_matrix, p["np_sub_frags_id"], p["np_sub_frags_len_bp"],
+        self.dev = dev_class(self.hic_matrix, p["np_sub_frags_id"], p["np_sub_frags_len_bp"],
                                p["np_sub_frags_accu"], self.frag_dispatcher, self.collector_id_repeats,
                                int(self.n_frags), p["mean_squared_frags_per_bin"], p["param_simu"],
                                fix_trans_accu=fix_trans_accu)

@@ -3,8 +3,9 @@
 ORACLE (the literal CPU restatement of cuda_lib_gl.sampler over the dense C restatement of kernels3.cu, oracle/), for a few
 seeded synthetic problems.  The problems themselves are regenerated from their seeds by graal_amd/synth.py, so the fixture
 only stores what to expect.  Run from the repo root:  python tests/golden/make_traces.py
-(The reference itself cannot run here -- PyCUDA + an NVIDIA GPU -- so these vectors pin the oracle/engine pair to each
-other across rounds; the oracle in turn is pinned to the reference's known answers in appendix_e.json.)"""
+(The reference's host code cannot run here -- PyCUDA + an NVIDIA GPU -- so these vectors pin the oracle/engine pair to each
+other across rounds.  Its kernels can: tests/test_ref_kernels_cpu.py reruns every one of these problems with the reference's
+own kernels, compiled for the host, under the oracle's host logic, and must reproduce this file.)"""
 import json
 import os
 import sys

@@ -69,12 +69,25 @@ def check_invariants(c):
 def oracle_candidate(state, fA, fB, op, max_id):
     """The reference's kernel sequence for one candidate (cuda_lib_gl.py:841-954) on fresh slots.
     Returns (candidate state, stale flag)."""
+    out, n_stale, _ = kernel_candidate(O.DenseOracle, state, fA, fB, op, max_id)
+    return out, n_stale > 0
+
+
+def kernel_candidate(D, state, fA, fB, op, max_id, fill=None):
+    """oracle_candidate's kernel sequence over the kernel class ``D`` (oracle.DenseOracle or ref_kernels.RefKernels).
+    ``fill``: value the output slot holds before the last kernel runs (default: a fresh slot), so that the entries
+    paste_contigs leaves unwritten stay recognisable.  Returns (candidate state, number of unwritten entries, the
+    pop_id_contigs / split_id_contigs vectors the sequence produced, in order)."""
     n = len(state["pos"])
-    D = O.DenseOracle
     out, ids = O.new_state(n), np.zeros(n, np.int32)
+    if fill is not None:
+        for k in FIELDS:
+            out[k][:] = fill
+    id_vectors = []
     if op <= 8:
         pop = O.new_state(n)
         D.pop_out(pop, state, ids, fA, max_id)
+        id_vectors.append(ids.copy())
         m2 = ids.max()
         if op == 0:
             D.copy(out, pop)
@@ -88,15 +101,17 @@ def oracle_candidate(state, fA, fB, op, max_id):
             D.pop_in(3, out, pop, fA, fB, m2, 1 if op == 6 else -1)
         else:
             D.swap_activity(out, pop, fA, m2)
-        return out, False
+        return out, 0, id_vectors
     upA, upB = (op - 9) >> 1, (op - 9) & 1
     t1, t2 = O.new_state(n), O.new_state(n)
     D.split(t1, state, ids, fA, upA, max_id)
+    id_vectors.append(ids.copy())
     m1 = ids.max()
     D.split(t2, t1, ids, fB, upB, m1)
+    id_vectors.append(ids.copy())
     m2 = ids.max()
     stale = D.paste(out, t2, fA, fB, m2)
-    return out, stale > 0
+    return out, int(stale), id_vectors
 
 
 # ---- ctypes access to the TEST-ONLY host build of frag_ops.h ---------------------------------------------
