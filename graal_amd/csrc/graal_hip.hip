@@ -4102,6 +4102,8 @@ struct InBuf;                  // insert.h: graal_insertions' buffers and result
 void in_free(InBuf* b);
 struct SpanBuf;                // span_moves.h: graal_block_flips' and graal_block_swaps' buffers
 void sp_free(SpanBuf* b);
+struct ExBuf;                  // excise.h: graal_block_excisions' buffers
+void ex_free(ExBuf* b);
 struct MpBuf;                  // maps.h: graal_layout_maps' buffers and images
 void mp_free(MpBuf* b);
 
@@ -4308,6 +4310,7 @@ struct Ctx {
     EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
     InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
     SpanBuf* sp = nullptr;        // graal_block_flips' and graal_block_swaps' buffers (span_moves.h; allocated by the first call of either)
+    ExBuf* ex = nullptr;          // graal_block_excisions' buffers (excise.h; allocated by its first call)
     MpBuf* mp = nullptr;          // graal_layout_maps' buffers and images (maps.h; allocated by its first call)
 };
 
@@ -4885,6 +4888,7 @@ void graal_destroy(graal_ctx* h)
         ed_free(h->ed); h->ed = nullptr;
         in_free(h->ins); h->ins = nullptr;
         sp_free(h->sp); h->sp = nullptr;
+        ex_free(h->ex); h->ex = nullptr;
         mp_free(h->mp); h->mp = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
@@ -6342,5 +6346,6 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "links.h"
 #include "insert.h"
 #include "span_moves.h"
+#include "excise.h"
 #include "edit.h"
 #include "maps.h"

@@ -412,13 +412,13 @@ void hc_map_shape(int S, int max_px, const int32_t* ranks, int n_ranks, int32_t*
     for (int i = 0; i < n_ranks; i++) out[2 + i] = map_pixel(ranks[i], s.bin);
 }
 
-// ---- the spans of a call (span_check.h).  kind: 0 graal_block_flips, 1 graal_block_swaps; info: nb rows of SpanInfo's twelve fields.
+// ---- the spans of a call (span_check.h).  kind: 0 graal_block_flips, 1 graal_block_swaps, 2 graal_block_excisions; info: nb rows of SpanInfo's twelve fields.
 // Returns -1 for a refused call, out[0..1] = the first offending span and the reason; else the number of scored spans, st[nb] the
 // status bytes and ids[0 .. m) the caller's indices of the scored spans in the records' order.
 int hc_span_check(int kind, int nb, const int32_t* info, int32_t* out, uint8_t* st, int32_t* ids)
 {
     static_assert(sizeof(SpanInfo) == 12 * sizeof(int32_t), "tests/test_span_check_cpu.py lists the same fields");
-    const SpanChecked c = span_check(reinterpret_cast<const SpanInfo*>(info), nb, kind ? SPAN_SWAPS : SPAN_FLIPS);
+    const SpanChecked c = span_check(reinterpret_cast<const SpanInfo*>(info), nb, kind == 2 ? SPAN_EXCISE : kind ? SPAN_SWAPS : SPAN_FLIPS);
     out[0] = c.off; out[1] = (int32_t)c.why;
     if (c.off >= 0) return -1;
     for (int k = 0; k < nb; k++) st[k] = c.st[(size_t)k];

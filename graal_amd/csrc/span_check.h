@@ -1,4 +1,5 @@
-// span_check.h -- what the host decides about a caller's spans before graal_block_flips / graal_block_swaps score them (span_moves.h):
+// span_check.h -- what the host decides about a caller's spans before graal_block_flips / graal_block_swaps (span_moves.h) or
+// graal_block_excisions (excise.h) score them:
 // the first span the call is refused for, or every span's status and the scored spans sorted by first slot.  Pure arithmetic on the rows
 // k_sp_gather wrote: no HIP calls, no handle, no side effects.  Shared with host_check.cpp, so that the CPU tests pin every refusal and
 // the order of the records without a device (tests/test_span_check_cpu.py).
@@ -29,6 +30,9 @@ struct SpanKind {
 };
 constexpr SpanKind SPAN_FLIPS = {"graal_block_flips", "block", false, 1, GRAAL_FLIP_WHOLE, GRAAL_FLIP_VALID, GRAAL_FLIP_CIRCULAR, GRAAL_FLIP_NONFINITE};
 constexpr SpanKind SPAN_SWAPS = {"graal_block_swaps", "swap", true, 0, -1, GRAAL_SWAP_VALID, GRAAL_SWAP_CIRCULAR, GRAAL_SWAP_NONFINITE};
+// (graal_block_excisions, excise.h: the span is cut out of its contig; the spans are checked and ordered the same way)
+constexpr SpanKind SPAN_EXCISE = {"graal_block_excisions", "span", false, 0, GRAAL_EXCISE_WHOLE, GRAAL_EXCISE_VALID, GRAAL_EXCISE_CIRCULAR,
+                                  GRAAL_EXCISE_NONFINITE};
 
 // why a call is refused, in the order the checks are made on a span
 enum SpanReason { SPAN_OK = 0, SPAN_NO_SLOT, SPAN_TWO_CONTIGS, SPAN_MID_BEFORE_FIRST, SPAN_LAST_NOT_BEHIND_MID, SPAN_OVERLAP };

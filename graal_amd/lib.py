@@ -53,7 +53,7 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_set_scan_path", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
            "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
-           "graal_block_swaps",
+           "graal_block_swaps", "graal_block_excisions",
            "graal_layout_maps", "graal_layout_maps_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
@@ -63,6 +63,7 @@ LINK_VALID, LINK_NONFINITE = 0, 1   # graal_end_links' status bytes
 INSERT_VALID, INSERT_NONFINITE = 0, 1   # graal_insertions' status bytes
 FLIP_VALID, FLIP_WHOLE, FLIP_CIRCULAR, FLIP_NONFINITE = 0, 1, 2, 3   # graal_block_flips' status bytes
 SWAP_VALID, SWAP_CIRCULAR, SWAP_NONFINITE = 0, 1, 2   # graal_block_swaps' status bytes
+EXCISE_VALID, EXCISE_WHOLE, EXCISE_CIRCULAR, EXCISE_NONFINITE = 0, 1, 2, 3   # graal_block_excisions' status bytes
 # graal_edit_layout's status words
 EDIT_OK, EDIT_BAD_CUT, EDIT_DUP_CUT, EDIT_BAD_END, EDIT_CIRCULAR, EDIT_END_TWICE, EDIT_SAME_CONTIG, EDIT_CYCLE = range(8)
 STEPS_ROW = 10   # GRAAL_STEPS_ROW: doubles per step in graal_steps' rows
@@ -146,6 +147,7 @@ def load():
                                              ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
         L.graal_block_flips.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
         L.graal_block_swaps.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
+        L.graal_block_excisions.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
         L.graal_layout_maps.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p]
         L.graal_layout_maps_fetch.argtypes = [ctypes.c_void_p, _f32p, _f32p, _f32p, _i32p]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -531,6 +533,32 @@ class Engine:
         self._ck(self._L.graal_block_swaps(self._h, m, first.ctypes.data_as(_i32p), mid.ctypes.data_as(_i32p), last.ctypes.data_as(_i32p),
                                            q.ctypes.data_as(_i64p), c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
                  "graal_block_swaps")
+        return q, c, st
+
+    def block_excisions(self, first, last):
+        """graal_block_excisions: for the disjoint spans (first[k] .. last[k], two fragments of one contig in position order) the score
+        E = logL(layout with the span cut out of its contig, the gap closed behind it and the span a contig of its own) - logL(layout)
+        in the exact arithmetic, as (E float64, contacts int64, status uint8) in the caller's order; E is NaN unless status is
+        EXCISE_VALID (EXCISE_WHOLE: the span is its whole contig, EXCISE_CIRCULAR: it lies in a ring, EXCISE_NONFINITE).  contacts = the
+        summed count between the span and the rest of its contig inside the window of the current layout: what the cut severs.  Same
+        preconditions and refusals as junction_scores; spans that overlap, span two contigs, run backwards or name no fragment raise
+        GraalError.  Leaves the step state alone."""
+        q, c, st = self.block_excisions_q(first, last)
+        return np.where(st == EXCISE_VALID, q.astype(np.float64) / Q_SCALE, np.nan), c, st
+
+    def block_excisions_q(self, first, last):
+        """The same with the score as int64 Q: (q, contacts, status)."""
+        first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        last = np.ascontiguousarray(last, dtype=np.int32).reshape(-1)
+        if len(first) != len(last):
+            raise ValueError("first and last must have the same length")
+        m = len(first)
+        q = np.zeros(m, dtype=np.int64)
+        c = np.zeros(m, dtype=np.int64)
+        st = np.zeros(m, dtype=np.uint8)
+        self._ck(self._L.graal_block_excisions(self._h, m, first.ctypes.data_as(_i32p), last.ctypes.data_as(_i32p), q.ctypes.data_as(_i64p),
+                                               c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+                 "graal_block_excisions")
         return q, c, st
 
     def layout_maps(self, max_px=2048):

@@ -77,6 +77,16 @@ def main(argv=None):
     ap.add_argument("--swaps", action="store_true", help="write swaps.tsv into the output folder: every pair of adjacent runs of up to "
                                                          "--swap-max-frags fragments together of the final layout with the log-likelihood "
                                                          "their swap would add, the contacts behind it and a status (graal_amd.swaps)")
+    ap.add_argument("--excise", action="store_true", help="after --polish and before --insert: cut the runs of up to --excise-max-frags "
+                                                          "fragments, and the runs between weak junctions, that the data prefer out of "
+                                                          "their contig, closing the gap behind them, round by round (graal_amd.excise): "
+                                                          "the freed pieces are what --insert places; writes excise.tsv")
+    ap.add_argument("--excise-max-frags", type=int, default=3, help="with --excise / --excisions: the longest run of fragments tried (default 3)")
+    ap.add_argument("--excise-min-score", type=float, default=0.0, help="with --excise: only excisions scoring above this (default 0)")
+    ap.add_argument("--excisions", action="store_true", help="write excisions.tsv into the output folder: every run of up to "
+                                                             "--excise-max-frags fragments of the final layout with the log-likelihood "
+                                                             "cutting it out of its contig would add, the contacts the cut severs and a "
+                                                             "status (graal_amd.excise)")
     ap.add_argument("--insertions", action="store_true", help="write insertions.tsv into the output folder: every insertion of a piece of "
                                                               "up to --insert-max-frags fragments into a junction of the final layout that the "
                                                               "contacts support, with the log-likelihood it would add (graal_amd.insert)")
@@ -156,6 +166,10 @@ def main(argv=None):
     if args.polish:
         from . import scaffold
         scaffold.write_scaffold_tsv(os.path.join(out, "polish.tsv"), scaffold.scaffold(smp, cut_below=args.polish_cut_below))
+    if args.excise:
+        from . import excise
+        excise.write_excise_rounds_tsv(os.path.join(out, "excise.tsv"),
+                                       excise.excise_rounds(smp, max_frags=args.excise_max_frags, min_score=args.excise_min_score))
     if args.insert:
         from . import scaffold
         scaffold.write_scaffold_tsv(os.path.join(out, "insert.tsv"),
@@ -194,6 +208,12 @@ def main(argv=None):
         eng = scaffold._engine(smp)
         soa = eng.download_frags()
         swaps.write_swaps_tsv(os.path.join(out, "swaps.tsv"), swaps.score_table(eng, soa, swaps.tilings(soa, None, args.swap_max_frags)))
+    if args.excisions:
+        from . import excise, scaffold
+        eng = scaffold._engine(smp)
+        soa = eng.download_frags()
+        excise.write_excisions_tsv(os.path.join(out, "excisions.tsv"),
+                                   excise.score_table(eng, soa, excise.tilings(soa, None, args.excise_max_frags)))
     if args.maps:
         from . import maps
         maps.write_maps(out, "", maps.layout_maps(smp, args.maps_max_px))

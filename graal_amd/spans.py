@@ -1,5 +1,5 @@
-"""What flips.py and swaps.py share: a move of a span of one linear contig is named by its fragments (first, last for a flip; first, mid,
-last for a swap), scored a disjoint set per call, planned best first and applied in rounds.
+"""What flips.py, swaps.py and excise.py share: a move of a span of one linear contig is named by its fragments (first, last for a flip
+or an excision; first, mid, last for a swap), scored a disjoint set per call, planned best first and applied in rounds.
 
     unit_bounds(soa, marks=None)                                  -- the linear contigs and each one's unit boundaries
     weak_junction_marks(engine, below=0.0)                        -- marks from the junction scores

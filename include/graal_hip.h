@@ -478,6 +478,44 @@ int graal_block_flips(graal_ctx* h, int32_t n_blocks, const int32_t* first, cons
 int graal_block_swaps(graal_ctx* h, int32_t n_swaps, const int32_t* first, const int32_t* mid, const int32_t* last, int64_t* q,
                       int64_t* contacts, uint8_t* status);
 
+/* Block excisions: the likelihood cutting a run of fragments out of its contig, and closing the gap behind it, would add, for a set of
+ * disjoint spans in one pass (graal_amd/csrc/excise.h): the inverse of an insertion.  The span contract is graal_block_flips': span k holds
+ * the fragments of ONE contig at positions pos[first[k]] .. pos[last[k]] (a one-fragment span has first == last); the spans of a call are
+ * pairwise disjoint and come in any order.  Anything else -- an index out of range, two contigs, reversed order, overlap -- returns
+ * GRAAL_E_ARG, the message names the first offending span, and nothing is written.  n_spans == 0 returns GRAAL_OK.
+ * The EXCISED layout of span k.  X = the span, bp interval [s0, e1), lx = e1 - s0; L = the contig's fragments before X, R = those behind
+ * it.  L keeps every field; every fragment of R gets start_bp - lx and pos - |X|; X becomes a linear contig of its own, direction and
+ * orientations kept, start_bp counted from 0; the float32 centres through centre_kb from the new integer starts.  It is the layout
+ * graal_edit_layout writes for cuts in front of X and behind X and the join L.tail - R.head, up to the reversal of the whole chain its
+ * canonical order may apply (see graal_insertions); E is defined on the contig's own direction.  A span at the head of its contig (L
+ * empty) or at its tail (R empty) is VALID: a plain cut.
+ *   E(k) = logL(excised layout) - logL(current layout)
+ * in the exact arithmetic under the current mode flags, with graal_junction_scores' / graal_end_links' / graal_insertions' roundings:
+ *   - pairs inside X, inside L and inside R count as unchanged;
+ *   - every sub-fragment pair of X x (L u R) moves from its cis price to its trans price (v_inter * norm, with the trans-branch RF-count
+ *     indexing under GRAAL_MODE_REF_TRANS_ACCU): a contact's term ob * (ln ex_new - ln ex_old) is rounded to Q once per contact, a
+ *     fragment pair's mass -(sum of ex_new - sum of ex_old), summed in float64 over its sub-fragment pairs with X's fragment outer, once
+ *     per fragment pair;
+ *   - every pair of L x R moves from its cis price at distance d to its cis price at d - lx, same roundings, L's fragment outer.  A pair
+ *     whose gap after the excision -- the left fragment's distance to s0 plus the right one's to e1 -- is beyond reach_bp is v_inter *
+ *     norm both times and contributes exactly 0; a contact whose old distance is >= d_max but whose new one is below it does contribute;
+ *   - under GRAAL_MODE_REF_TRANS_ACCU with bins of mixed RF counts, the X x (L u R) pairs beyond the window that involve such a bin
+ *     (graal_junction_scores' quirk term with the sign of a cut); nothing is reversed, so there is no mirror term.
+ * int64 sums: bit-identical from call to call, for any grid and for any order of the spans in the call.  A span is scored alone: the
+ * other spans of the call are part of its L and R, unmoved.
+ * Outputs, n_spans entries each in the caller's order: q[k] = E in Q; contacts[k] = the summed count of the X x (L u R) contacts whose
+ * current centre distance is below d_max (what the cut severs); status[k] one of the codes below (q = 0 unless VALID).
+ * The contact list may come in any order.  Needs sub-fragments, parameters, fragments and contacts.  Does not relabel and leaves the step
+ * state alone (ranked layout, carried total, a pending commit's correction, the proposal tables).  Device memory is O(fragments +
+ * sub-fragments + n_spans).  GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats); GRAAL_E_STATE with an exchange or RCCL
+ * attached (one rank only). */
+#define GRAAL_EXCISE_VALID 0
+#define GRAAL_EXCISE_WHOLE 1      /* the span is its whole contig: nothing changes, q = 0 */
+#define GRAAL_EXCISE_CIRCULAR 2   /* the span lies in a circular contig: no score, q = 0 */
+#define GRAAL_EXCISE_NONFINITE 3  /* a term was not finite, q = 0 */
+int graal_block_excisions(graal_ctx* h, int32_t n_spans, const int32_t* first, const int32_t* last, int64_t* q, int64_t* contacts,
+                          uint8_t* status);
+
 /* Layout maps: the observed contacts, the contacts the model expects and their residual, as images in the current genome order
  * (graal_amd/csrc/maps.h).
  * Order: contigs by ascending label, fragments by position inside a contig, a fragment's sub-fragments in stored order, reversed when
