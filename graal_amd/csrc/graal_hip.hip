@@ -4104,6 +4104,8 @@ struct SpanBuf;                // span_moves.h: graal_block_flips' and graal_blo
 void sp_free(SpanBuf* b);
 struct ExBuf;                  // excise.h: graal_block_excisions' buffers
 void ex_free(ExBuf* b);
+struct RgBuf;                  // rings.h: graal_ring_scores' and graal_close_rings' buffers
+void rg_free(RgBuf* b);
 struct MpBuf;                  // maps.h: graal_layout_maps' buffers and images
 void mp_free(MpBuf* b);
 
@@ -4311,6 +4313,7 @@ struct Ctx {
     InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
     SpanBuf* sp = nullptr;        // graal_block_flips' and graal_block_swaps' buffers (span_moves.h; allocated by the first call of either)
     ExBuf* ex = nullptr;          // graal_block_excisions' buffers (excise.h; allocated by its first call)
+    RgBuf* rg = nullptr;          // graal_ring_scores' and graal_close_rings' buffers (rings.h; allocated by the first call of either)
     MpBuf* mp = nullptr;          // graal_layout_maps' buffers and images (maps.h; allocated by its first call)
 };
 
@@ -4889,6 +4892,7 @@ void graal_destroy(graal_ctx* h)
         in_free(h->ins); h->ins = nullptr;
         sp_free(h->sp); h->sp = nullptr;
         ex_free(h->ex); h->ex = nullptr;
+        rg_free(h->rg); h->rg = nullptr;
         mp_free(h->mp); h->mp = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
@@ -6343,6 +6347,7 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "simulate.h"
 #include "score_common.h"
 #include "junctions.h"
+#include "rings.h"
 #include "links.h"
 #include "insert.h"
 #include "span_moves.h"

@@ -53,7 +53,7 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_set_scan_path", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
            "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
-           "graal_block_swaps", "graal_block_excisions",
+           "graal_block_swaps", "graal_block_excisions", "graal_ring_scores", "graal_close_rings",
            "graal_layout_maps", "graal_layout_maps_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
@@ -64,6 +64,8 @@ INSERT_VALID, INSERT_NONFINITE = 0, 1   # graal_insertions' status bytes
 FLIP_VALID, FLIP_WHOLE, FLIP_CIRCULAR, FLIP_NONFINITE = 0, 1, 2, 3   # graal_block_flips' status bytes
 SWAP_VALID, SWAP_CIRCULAR, SWAP_NONFINITE = 0, 1, 2   # graal_block_swaps' status bytes
 EXCISE_VALID, EXCISE_WHOLE, EXCISE_CIRCULAR, EXCISE_NONFINITE = 0, 1, 2, 3   # graal_block_excisions' status bytes
+RING_CLOSE, RING_OPEN, RING_SINGLE, RING_NONFINITE = 0, 1, 2, 3   # graal_ring_scores' status bytes
+RINGEDIT_OK, RINGEDIT_BAD_FRAG, RINGEDIT_CIRCULAR, RINGEDIT_SINGLE, RINGEDIT_TWICE = range(5)   # graal_close_rings' status words
 # graal_edit_layout's status words
 EDIT_OK, EDIT_BAD_CUT, EDIT_DUP_CUT, EDIT_BAD_END, EDIT_CIRCULAR, EDIT_END_TWICE, EDIT_SAME_CONTIG, EDIT_CYCLE = range(8)
 STEPS_ROW = 10   # GRAAL_STEPS_ROW: doubles per step in graal_steps' rows
@@ -148,6 +150,8 @@ def load():
         L.graal_block_flips.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
         L.graal_block_swaps.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
         L.graal_block_excisions.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
+        L.graal_ring_scores.argtypes = [ctypes.c_void_p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
+        L.graal_close_rings.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p]
         L.graal_layout_maps.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p]
         L.graal_layout_maps_fetch.argtypes = [ctypes.c_void_p, _f32p, _f32p, _f32p, _i32p]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -560,6 +564,42 @@ class Engine:
                                                c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
                  "graal_block_excisions")
         return q, c, st
+
+    def ring_scores(self):
+        """graal_ring_scores: (R float64[n], contacts int64[n], status uint8[n]), indexed by fragment, every fragment carrying its
+        contig's values.  R = logL(layout with the contig in the other topology, every coordinate kept) - logL(layout) in the exact
+        arithmetic: closing a linear contig of >= 2 fragments (RING_CLOSE), opening a ring at its wrap (RING_OPEN); NaN for RING_SINGLE
+        and RING_NONFINITE.  contacts = the summed count of the contig's contacts closer across the wrap than along the contig (s <
+        d_max and 2 s > s_tot).  The ring price is the reference's: only pairs less than d_max apart along the contig change.  Same
+        preconditions and refusals as junction_scores.  Leaves the step state alone."""
+        q, c, st = self.ring_scores_q()
+        return np.where(st <= RING_OPEN, q.astype(np.float64) / Q_SCALE, np.nan), c, st
+
+    def ring_scores_q(self):
+        """The same with the score as int64 Q: (q, contacts, status)."""
+        n = int(self.n)
+        q = np.zeros(n, dtype=np.int64)
+        c = np.zeros(n, dtype=np.int64)
+        st = np.zeros(n, dtype=np.uint8)
+        self._ck(self._L.graal_ring_scores(self._h, q.ctypes.data_as(_i64p), c.ctypes.data_as(_i64p),
+                                           st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))), "graal_ring_scores")
+        return q, c, st
+
+    def close_rings(self, frags):
+        """graal_close_rings: every contig named by one of its fragments in `frags` (linear, >= 2 fragments, named once) becomes a ring:
+        circ = 1, the head's prev = the tail, the tail's next = the head, every other field kept.  Returns the status array (int32,
+        RINGEDIT_OK everywhere).  A refusal raises GraalError (layout unchanged) with the status array as its .status attribute.
+        Afterwards the engine is as after edit_layout.  A ring is opened by edit_layout: a cut after its last-position fragment."""
+        f = _c(np.asarray(frags, dtype=np.int64).reshape(-1), np.int32)
+        st = np.zeros(len(f), dtype=np.int32)
+        rc = self._L.graal_close_rings(self._h, len(f), f.ctypes.data_as(_i32p), st.ctypes.data_as(_i32p))
+        if rc != 0:
+            try:
+                self._ck(rc, "graal_close_rings")
+            except GraalError as err:
+                err.status, err.code = st, rc
+                raise
+        return st
 
     def layout_maps(self, max_px=2048):
         """graal_layout_maps + graal_layout_maps_fetch: (observed, expected, residual, pixel_of_sub, bin, bad_pixels).  The three images

@@ -87,6 +87,15 @@ def main(argv=None):
                                                              "--excise-max-frags fragments of the final layout with the log-likelihood "
                                                              "cutting it out of its contig would add, the contacts the cut severs and a "
                                                              "status (graal_amd.excise)")
+    ap.add_argument("--circularise", action="store_true", help="after --polish, --excise, --insert, --swap and --flip, before the outputs: "
+                                                               "close into a ring every linear contig whose ring score is above "
+                                                               "--circularise-min-score (graal_amd.rings); the ring model is the "
+                                                               "reference's, which prices only pairs less than d_max apart along the "
+                                                               "contig; writes circularise.tsv")
+    ap.add_argument("--circularise-min-score", type=float, default=0.0, help="with --circularise: only closures scoring above this (default 0)")
+    ap.add_argument("--rings", action="store_true", help="write rings.tsv into the output folder: every contig of the final layout with the "
+                                                         "log-likelihood closing it into a ring (or, for a ring, opening it at its wrap) "
+                                                         "would add, the contacts across the wrap and a status (graal_amd.rings)")
     ap.add_argument("--insertions", action="store_true", help="write insertions.tsv into the output folder: every insertion of a piece of "
                                                               "up to --insert-max-frags fragments into a junction of the final layout that the "
                                                               "contacts support, with the log-likelihood it would add (graal_amd.insert)")
@@ -182,6 +191,9 @@ def main(argv=None):
         from . import flips
         flips.write_flip_rounds_tsv(os.path.join(out, "flip.tsv"),
                                     flips.flip_rounds(smp, max_frags=args.flip_max_frags, min_score=args.flip_min_score))
+    if args.circularise:
+        from . import rings
+        rings.write_close_rings_tsv(os.path.join(out, "circularise.tsv"), rings.close_rings(smp, min_score=args.circularise_min_score))
     lev = P.get_level(args.level)
     if args.fasta:
         P.load_reference_sequence(args.fasta)
@@ -214,6 +226,9 @@ def main(argv=None):
         soa = eng.download_frags()
         excise.write_excisions_tsv(os.path.join(out, "excisions.tsv"),
                                    excise.score_table(eng, soa, excise.tilings(soa, None, args.excise_max_frags)))
+    if args.rings:
+        from . import rings, scaffold
+        rings.write_rings_tsv(os.path.join(out, "rings.tsv"), rings.ring_table(scaffold._engine(smp)))
     if args.maps:
         from . import maps
         maps.write_maps(out, "", maps.layout_maps(smp, args.maps_max_px))

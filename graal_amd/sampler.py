@@ -765,6 +765,12 @@ class sampler(object):
         self.likelihood_t = None                     # (a layout change outside step_max_likelihood, as explode_genome)
         return st
 
+    def close_rings(self, frags):
+        """Close contigs into rings on the device (Engine.close_rings, graal_close_rings); returns its status array."""
+        st = self.engine.close_rings(frags)
+        self.likelihood_t = None                     # (a layout change outside step_max_likelihood, as edit_layout)
+        return st
+
     def define_repeats(self):
         """``cuda_lib_gl.py:452-473``: every copy of a duplicated bin (the original included) is a "repeat"."""
         self._black_set = set(int(x) for x in self.id_frags_blacklisted)

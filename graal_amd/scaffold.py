@@ -3,7 +3,7 @@
     scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None,
              insert_max_frags=None, insert_min_score=0.0,
              flip_max_frags=None, flip_min_score=0.0,
-             swap_max_frags=None, swap_min_score=0.0)                                 -- the rounds; returns their record
+             swap_max_frags=None, swap_min_score=0.0, close_rings_min_score=None)     -- the rounds; returns their record
     break_cycles(ea, eb, score, contig_of_end)                                            -- drop the weakest join of every cycle
     write_scaffold_tsv(path, record)                                                      -- one tab-separated row per round
 
@@ -31,6 +31,10 @@ With swap_max_frags set, under the same condition and BEFORE the flip rounds, gr
 of adjacent runs of up to swap_max_frags fragments together scoring above swap_min_score, and unit tilings over the same marks): a run
 that sits a few places from where it belongs is moved there, so that a moved run that is also inverted is at its place when the flips
 look at it.  The joins those rounds made are marks of the flip rounds, as scaffold()'s own are.
+With close_rings_min_score set, under the same condition and BEFORE the swap and flip rounds, graal_amd.rings.close_rings runs over the
+result: step 3 opens every cycle of contigs, so a circular replicon ends the rounds as a linear chain, and this closes the chains whose
+ring score (graal_ring_scores) is above close_rings_min_score, all at once (their scores add exactly).  Its row follows in the record:
+joins = the contigs closed, kept 0 when logL did not rise by the summed scores and the closures were undone.
 """
 import numpy as np
 
@@ -102,7 +106,7 @@ def plan_joins(mutual, min_score, contig_of_end):
 
 
 def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below=None, insert_max_frags=None, insert_min_score=0.0,
-             flip_max_frags=None, flip_min_score=0.0, swap_max_frags=None, swap_min_score=0.0):
+             flip_max_frags=None, flip_min_score=0.0, swap_max_frags=None, swap_min_score=0.0, close_rings_min_score=None):
     """Scaffold (and with cut_below, polish; with insert_max_frags, insert pieces) the engine's current layout; see the module's
     docstring.  Returns the record: a list of dicts with the keys COLUMNS, round 0 the layout as it came (kept 0 marks a round that was
     undone)."""
@@ -151,6 +155,11 @@ def scaffold(sampler_or_engine, rounds=50, min_score=0.0, min_frags=1, cut_below
         if len(a) == 0 and len(icuts) == 0:
             settled = True             # (only cuts: no join and no insertion was on offer behind them)
             break
+    if close_rings_min_score is not None and settled:
+        from . import rings
+        rec = rings.close_rings(obj, min_score=close_rings_min_score)
+        record.append({"round": record[-1]["round"] + 1, "cuts": 0, "joins": rec["closed"], "contigs": rec["contigs"],
+                       "logL": rec["logL"], "kept": rec["kept"]})
     if swap_max_frags is not None and settled:
         from . import flips, swaps
         last = record[-1]["round"]

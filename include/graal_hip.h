@@ -308,7 +308,7 @@ int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status);
  * the data prefer the join.  int64 sums: bit-identical from call to call and for any grid.
  * Listed: the pairs of ends with at least one contact between A and B inside the window (sub-fragment centre distance < d_max) in the
  * joined orientation, both contigs linear with >= min_frags (>= 1) fragments.  Any other pair of ends would score only its negative
- * expected mass and is NOT listed.  Not covered: joining a contig's two ends (circularisation), circular contigs.
+ * expected mass and is NOT listed.  Not covered: joining a contig's two ends (graal_ring_scores prices that), circular contigs.
  * graal_end_links computes the table and returns its size in *n_links; graal_end_links_fetch copies the last table out, sorted by
  * (end_a, end_b) with end_a < end_b: q in Q, contacts = the summed count inside the window (the evidence behind the score),
  * status GRAAL_LINK_VALID or GRAAL_LINK_NONFINITE (a term was not finite; q = 0).  cap < n_links: GRAAL_E_ARG.
@@ -363,7 +363,7 @@ int graal_end_links_mutual_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, i
 #define GRAAL_EDIT_BAD_END 3       /* an end out of range or not an end of a contig after the cuts */
 #define GRAAL_EDIT_CIRCULAR 4      /* an end of a circular contig that no cut opens */
 #define GRAAL_EDIT_END_TWICE 5     /* an end used by two joins */
-#define GRAAL_EDIT_SAME_CONTIG 6   /* both ends on one contig (circularisation is not offered) */
+#define GRAAL_EDIT_SAME_CONTIG 6   /* both ends on one contig (closing a contig into a ring is graal_close_rings) */
 #define GRAAL_EDIT_CYCLE 7         /* the join closes a cycle of contigs */
 int graal_edit_layout(graal_ctx* h, int32_t n_cuts, const int32_t* cut_after, int32_t n_joins, const int32_t* end_a, const int32_t* end_b,
                       int32_t* status);
@@ -515,6 +515,59 @@ int graal_block_swaps(graal_ctx* h, int32_t n_swaps, const int32_t* first, const
 #define GRAAL_EXCISE_NONFINITE 3  /* a term was not finite, q = 0 */
 int graal_block_excisions(graal_ctx* h, int32_t n_spans, const int32_t* first, const int32_t* last, int64_t* q, int64_t* contacts,
                           uint8_t* status);
+
+/* Ring scores: the likelihood closing each linear contig into a ring, or opening each ring at its wrap, would add, for every contig of
+ * the current layout in one pass (graal_amd/csrc/rings.h).
+ *   R[c] = logL(layout with contig c in the OTHER topology, every coordinate kept) - logL(current layout)
+ * A linear contig of at least 2 fragments is CLOSED: circ becomes 1 on its fragments, the head's prev becomes the tail and the tail's
+ * next the head, as graal_apply_move writes a paste of a contig's own two ends (graal_close_rings below writes it).  A ring is OPENED at
+ * its wrap, between its last-position and its position-0 fragment: what graal_edit_layout writes for a cut after the last-position
+ * fragment.  No start_bp changes and nothing is re-centred, so R carries no re-centring noise, and R(open) of the closed layout is
+ * -R(close) bit for bit.
+ * In the exact arithmetic, with graal_junction_scores' roundings:
+ *   - every pair of DIFFERENT sub-fragments of c (two of one bin included) whose linear centre distance s, from the centres of the
+ *     current layout, lies in 0 < s < d_max moves between rippe(s) * norm and rippe_circ(s, l_cont_bp / 1000) * norm; every other
+ *     pair contributes exactly 0;
+ *   - a contact's term ob * (ln ex_new - ln ex_old) is rounded to Q once per contact; a fragment pair's mass -(sum of ex_new - ex_old)
+ *     over its sub-fragment pairs, in float64 with the lower-position fragment outer, once per fragment pair; a bin's own sub-fragment
+ *     pairs (a < b in stored order) count as one such pair;
+ *   - GRAAL_MODE_REF_TRANS_ACCU does not enter: it re-indexes trans prices only, and a cis pair beyond the window is v_inter * the
+ *     plain norm in both topologies.
+ * int64 sums: bit-identical from call to call and for any grid.
+ * THE MODEL'S LIMIT.  The ring price of the reference (rippe_contacts_circ, kernels3.cu:135-160) applies only to pairs whose LINEAR
+ * distance is below d_max: n = K s (s_tot - s) / s_tot there, v_inter * norm -- the linear price -- everywhere else.  A contig shorter
+ * than d_max gets a true ring model, symmetric in s and s_tot - s.  In a longer contig only the in-window pairs change, and contacts
+ * between head and tail more than d_max apart along the contig carry nothing: R is what graal_eval_full_q prices, nothing better.
+ * Outputs, n entries each, indexed by fragment; every fragment carries its contig's values: q = R in Q; contacts = the summed count
+ * of the contig's contacts with s < d_max and 2 s > s_tot -- those closer across the wrap than along the contig, the evidence behind a
+ * closure; status one of the codes below (q = 0 unless CLOSE or OPEN).  GRAAL_RING_NONFINITE is reachable: powf(n, slope) grows without
+ * bound as s -> s_tot in a ring shorter than d_max.
+ * Not covered: opening a ring anywhere but at its wrap (re-basing moves every float32 centre); repeated bins; more than one rank.
+ * The contact list may come in any order.  Needs sub-fragments, parameters, fragments and contacts.  Does not relabel and leaves the
+ * step state alone (ranked layout, carried total, a pending commit's correction, the proposal tables).  Device memory is O(fragments +
+ * sub-fragments).  GRAAL_E_UNSUPPORTED with repeated bins (graal_upload_repeats); GRAAL_E_STATE with an exchange or RCCL attached (one
+ * rank only) and for a corrupt layout. */
+#define GRAAL_RING_CLOSE 0      /* a linear contig: q scores closing it */
+#define GRAAL_RING_OPEN 1       /* a ring: q scores opening it at the wrap */
+#define GRAAL_RING_SINGLE 2     /* a one-fragment linear contig: no score, q = 0 */
+#define GRAAL_RING_NONFINITE 3  /* a term was not finite or did not fit, q = 0 */
+int graal_ring_scores(graal_ctx* h, int64_t* q_out, int64_t* contacts_out, uint8_t* status);
+
+/* Close contigs into rings, in one call (graal_amd/csrc/rings.h).  frag[k] is ANY fragment of a linear contig of at least 2 fragments:
+ * the contig becomes a ring -- circ = 1 on every fragment, the head's prev = the tail, the tail's next = the head; every other field of
+ * every fragment is kept, labels included.  status[k] is GRAAL_RINGEDIT_OK or why entry k was refused; any refusal returns GRAAL_E_ARG
+ * and leaves the layout as it was.  n_rings == 0 returns GRAAL_OK.
+ * OPENING a ring stays with graal_edit_layout: a cut after the ring's last-position fragment opens it at the wrap and keeps every
+ * coordinate (the inverse of this call, and the layout graal_ring_scores prices for a ring).
+ * Afterwards the engine is in the state graal_edit_layout leaves it in: the next graal_begin_step relabels; the carried total and a
+ * pending commit's correction are void.  GRAAL_E_UNSUPPORTED with repeated bins; GRAAL_E_STATE before the fragments are uploaded, with
+ * an exchange or RCCL attached (one rank only) and for a corrupt layout. */
+#define GRAAL_RINGEDIT_OK 0
+#define GRAAL_RINGEDIT_BAD_FRAG 1   /* fragment out of range */
+#define GRAAL_RINGEDIT_CIRCULAR 2   /* the contig is a ring already */
+#define GRAAL_RINGEDIT_SINGLE 3     /* a one-fragment contig */
+#define GRAAL_RINGEDIT_TWICE 4      /* the contig is named by two entries */
+int graal_close_rings(graal_ctx* h, int32_t n_rings, const int32_t* frag, int32_t* status);
 
 /* Layout maps: the observed contacts, the contacts the model expects and their residual, as images in the current genome order
  * (graal_amd/csrc/maps.h).
