@@ -1,6 +1,6 @@
 // edit.h -- a batch of cuts and joins applied to the layout in one call (graal_edit_layout).
-// Included by graal_hip.hip after insert.h (it uses Ctx, SoaPtr, the F_* field indices, fail, wait_own, refresh, sync_args and
-// score_common.h's free_null).
+// Included by graal_hip.hip after excise.h (it uses Ctx, SoaPtr, the F_* field indices, fail, wait_own and score_common.h's free_null
+// and layout_replaced).
 //
 // The rules are those of include/graal_hip.h (graal_edit_layout); tests/edit_reference.py restates them in numpy.  Kernels, all on the
 // engine's stream:
@@ -429,16 +429,7 @@ int graal_edit_layout(graal_ctx* h, int32_t n_cuts, const int32_t* cut_after, in
     k_ed_write<<<nb, 256, 0, s>>>(sp, h->soa[out], n, E->base, E->at, E->cnt, E->ncut, E->ph, E->pp, E->pob, E->pcnt, E->plbp, E->ptail, E->plab,
                                   E->ejc, E->ejo, E->agg[cur]);
     CK(hipGetLastError());
-    if (out != 0) CK(hipMemcpyAsync(h->soa_mem[0], h->soa_mem[out], sizeof(int) * (size_t)n * GRAAL_N_FIELDS, hipMemcpyDeviceToDevice, s));
-    CK(hipStreamSynchronize(s));
-    // ---- the engine's state: that of graal_upload_frags (the stat_frag table is unchanged: no fragment changes its bin)
-    h->cur = 0; h->ranks_valid = false; h->pending_commits = 0; h->begin_launched = false; h->stats_from_apply = false;
-    h->order_valid = false;
-    h->carry_q = 0; h->carry_bad = true;
-    int rc = refresh(h);
-    if (rc) return rc;
-    CK(hipStreamSynchronize(s));
-    return sync_args(h);
+    return layout_replaced(h, out);
 }
 
 } // extern "C"

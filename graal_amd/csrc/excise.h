@@ -1,8 +1,8 @@
 // excise.h -- the likelihood cutting a run of fragments out of its contig would add, for a caller's set of disjoint spans in one pass
-// (graal_block_excisions): the inverse of an insertion.  Included by graal_hip.hip after span_moves.h (it uses LayoutRecs with
-// recs_reserve / recs_build, the records LnFrag / LnCtg, ln_run_sum, ln_block_add, ln_pair_mass, ln_quirk_pair, insert.h's in_shift_mass,
-// span_moves.h's k_sp_gather, sp_span_of, sp_add, sp_run_edges and k_sp_out, span_check.h and score_common.h's score_entry, score_exit,
-// STEP_CK and free_null).
+// (graal_block_excisions): the inverse of an insertion.  Included by graal_hip.hip after span_moves.h (it uses the records LnFrag /
+// LnCtg, ln_block_add, ln_pair_mass, ln_quirk_pair, insert.h's in_shift_mass, span_moves.h's frame span_moves with SpanBuf and
+// sp_unit_total, its sp_span_of, sp_add, sp_run_edges and sp_span_of_unit, span_check.h's SPAN_EXCISE and score_common.h's STEP_CK and
+// stream_blocks).
 //
 // Span k = the fragments X of one linear contig at slots first .. last, bp interval [s0, e1), lx = e1 - s0; L = the contig's fragments
 // before it, R = those behind it.  The excised layout leaves L as it is, gives every fragment of R start_bp - lx and pos - |X|, and makes X
@@ -31,7 +31,7 @@
 // same contig: contacts up to the long span's length apart walk the short spans between their sides and feed none.
 //
 // Kernels, all on the engine's stream:
-//   k_jn_count / scan / k_ln_prep (recs_build) -- slots and per-slot records, as for links, insertions and span moves;
+//   span_moves' frame: k_jn_count / scan / k_ln_prep (recs_build) -- slots and per-slot records, as for links, insertions and span moves;
 //   k_sp_gather -- per span of the caller its slots, labels, bp interval and contig; the host decides (span_check.h, kind 2): refuses the
 //                 call, or sets aside the spans in a ring and those that are a whole contig and uploads the others sorted by first slot;
 //   k_ex_sub    -- per fragment: the number of scored spans that start at or before its slot, its span and, per sub-fragment, a 32-byte
@@ -58,37 +58,7 @@ namespace {
 // ub: the scored spans whose first slot is <= this fragment's slot; span: the one that holds it, or -1
 // acc: RF count | the bin's last RF count << 16; meta: sub k | fwd << 4
 struct ExSub { float c_old; int label, slot, ub, span, frag, acc, meta; };
-static_assert(sizeof(ExSub) == 32, "a sub-fragment's record is two 16-byte loads");
-
-struct ExBuf {
-    LayoutRecs R;
-    ExSub* sub = nullptr; int n = 0, S = 0;                           // per sub-fragment
-    int *first = nullptr, *last = nullptr; SpanInfo* info = nullptr; SpanRec* rec = nullptr;
-    long long *qb = nullptr, *cb = nullptr, *q = nullptr, *c = nullptr, *ne = nullptr, *noff = nullptr; int* bad = nullptr; int4* nx = nullptr;
-    unsigned char* st = nullptr;
-    void* tmp = nullptr; size_t tmp_bytes = 0;
-    size_t bcap = 0;                                                  // spans the per-span arrays hold
-};
-
-void ex_free_spans(ExBuf* b)
-{
-    free_null({(void**)&b->first, (void**)&b->last, (void**)&b->info, (void**)&b->rec, (void**)&b->qb, (void**)&b->cb, (void**)&b->q,
-               (void**)&b->c, (void**)&b->ne, (void**)&b->noff, (void**)&b->bad, (void**)&b->nx, (void**)&b->st, &b->tmp});
-    b->bcap = 0; b->tmp_bytes = 0;
-}
-
-void ex_free_subs(ExBuf* b)
-{
-    free_null({(void**)&b->sub});
-    b->n = 0; b->S = 0;
-}
-
-void ex_free(ExBuf* b)
-{
-    if (!b) return;
-    recs_free(b->R); ex_free_subs(b); ex_free_spans(b);
-    delete b;
-}
+static_assert(sizeof(ExSub) == SPAN_SUB_BYTES, "a sub-fragment's record is two 16-byte loads");
 
 __global__ __launch_bounds__(256) void k_ex_sub(int n, int m, const SpanRec* __restrict__ rec, const int* __restrict__ slot_of,
                                                 const int* __restrict__ lab, const LnFrag* __restrict__ fr, const int* __restrict__ sub_ids,
@@ -99,12 +69,8 @@ __global__ __launch_bounds__(256) void k_ex_sub(int n, int m, const SpanRec* __r
     const int slot = slot_of[f];
     if (slot < 0 || slot >= n) return;                               // (a corrupt layout: refused before anything reads the records)
     const LnFrag x = fr[slot];
-    int lo = 0, hi = m;                                              // first span with .first > slot
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (rec[mid].first <= slot) lo = mid + 1; else hi = mid;
-    }
-    const int j = (lo > 0 && slot <= rec[lo - 1].last) ? lo - 1 : -1;
+    int lo = 0;
+    const int j = sp_span_of(rec, m, slot, &lo);
     const bool fo = x.fwd != 0;
     const int last = stat_accu(x.st, x.st.n - 1);
     int4 ids = make_int4(f, 0, 0, 1);
@@ -211,17 +177,6 @@ __global__ void k_ex_edges(int m, const SpanRec* __restrict__ rec, const LnFrag*
     nx[j] = make_int4(x.x, x.y, lo, 0);
 }
 
-// the unit's span: the last j with noff[j] <= W (every scored span has at least one unit: a fragment of X)
-__device__ __forceinline__ int ex_span_of_unit(const long long* __restrict__ noff, int m, long long W)
-{
-    int lo = 0, hi = m - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (noff[mid] <= W) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // One walk of a unit's fragment x: partners from slot `from` in steps of `dir` while inside [lo_slot, hi_slot] and their gap to the
 // boundary `edge` they are walked away from is <= budget (the gap only grows).  lx 0: x in X, the pair goes from cis to trans; lx > 0: x
 // in L, the partner in R moves lx bp down, cis both times.
@@ -255,7 +210,7 @@ __global__ __launch_bounds__(256) void k_ex_mass(long long total, int m, const S
 {
     const long long W = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (W >= total) return;                                          // (wave-uniform)
-    const int j = ex_span_of_unit(noff, m, W);
+    const int j = sp_span_of_unit(noff, m, W);
     const long long u = W - noff[j];
     if (u < 0 || u >= ne[j]) return;
     const SpanRec b = rec[j];
@@ -310,119 +265,48 @@ __global__ __launch_bounds__(256) void k_ex_quirk(int m, const SpanRec* __restri
     ln_block_add(sum, nb, &qb[W], &badb[W]);
 }
 
-int excise_spans(graal_ctx* h, int nb, const int32_t* first, const int32_t* last, int64_t* q, int64_t* contacts, uint8_t* status)
+// The kernels of an excision: what span_moves runs between the upload of the scored spans `rec` and k_sp_out.
+int ex_score(graal_ctx* h, const SpanKind& K, SpanBuf* B, const std::vector<SpanRec>& rec, std::string& unsupported)
 {
-    const SpanKind& K = SPAN_EXCISE;
-    if (const int rc = score_entry(h, K.fn)) return rc;
-    if (nb == 0) return GRAAL_OK;
-    const int n = h->n, S = h->n_sub_total;
-    char msg[240], why[64];
-    for (int k = 0; k < nb; k++)
-        if (first[k] < 0 || first[k] >= n || last[k] < 0 || last[k] >= n) {
-            snprintf(msg, sizeof msg, "%s: %s %d: fragment index out of range (%d, %d; %d fragments)", K.fn, K.noun, k, first[k], last[k], n);
-            return fail(h, GRAAL_E_ARG, msg);
-        }
-    if (!h->ex) h->ex = new ExBuf();
-    ExBuf* B = h->ex;
-    LayoutRecs& R = B->R;
+    const int n = h->n, m = (int)rec.size();
+    const LayoutRecs& R = B->R;
+    ExSub* const sub = (ExSub*)B->sub;
     hipStream_t s = h->stream;
-    if (const int rc = recs_reserve(h, R)) return rc;
-    if (B->n != n || B->S != S) {                                     // (B->n stays 0 until the set is allocated)
-        ex_free_subs(B);
-        CK(hipMalloc(&B->sub, sizeof(ExSub) * (size_t)std::max(S, 1)));
-        B->n = n; B->S = S;
-    }
-    if ((size_t)nb > B->bcap) {                                       // (grows to the largest call; bcap stays 0 until the set is allocated)
-        ex_free_spans(B);
-        const size_t cap = (size_t)nb + 1;
-        for (int** p : {&B->first, &B->last, &B->bad}) CK(hipMalloc(p, sizeof(int) * cap));
-        for (long long** p : {&B->qb, &B->cb, &B->q, &B->c, &B->ne, &B->noff}) CK(hipMalloc(p, sizeof(long long) * cap));
-        CK(hipMalloc(&B->info, sizeof(SpanInfo) * cap));
-        CK(hipMalloc(&B->rec, sizeof(SpanRec) * cap));
-        CK(hipMalloc(&B->nx, sizeof(int4) * cap));
-        CK(hipMalloc(&B->st, cap));
-        size_t tb = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, B->ne, B->noff, (int)cap, s));
-        CK(hipMalloc(&B->tmp, tb));
-        B->tmp_bytes = tb;
-        B->bcap = (size_t)nb;
-    }
     const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     const int reach = reach_bp(h);
+    long long max_lx = 0;
+    for (const SpanRec& r : rec) max_lx = std::max(max_lx, (long long)r.e1 - r.s0);
+    const float far_kb = (float)((double)max_lx / 1000.0 + 1.0);
     int rc = GRAAL_OK;
-    unsigned err = 0;
-    bool refused = false;
-    const char* unsupported = nullptr;
-    std::vector<SpanInfo> info((size_t)nb);
     do {
-        if ((rc = recs_build(h, R, 1))) break;
-        STEP_CK(hipMemcpyAsync(B->first, first, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
-        STEP_CK(hipMemcpyAsync(B->last, last, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
-        k_sp_gather<<<blocks_for(nb, 256), 256, 0, s>>>(nb, n, B->first, nullptr, B->last, R.slot, R.lab, R.fr, R.ctg, B->info);
+        k_ex_sub<<<blocks_for(n, 256), 256, 0, s>>>(n, m, B->rec, R.L.slot, R.lab, R.fr, h->d_sub_ids, sub);
         STEP_CK(hipGetLastError());
-        STEP_CK(hipMemcpyAsync(&err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        STEP_CK(hipMemcpyAsync(info.data(), B->info, sizeof(SpanInfo) * (size_t)nb, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (err) break;   // (a corrupt layout: the slots are not to be trusted, nothing reads them)
-        const SpanChecked C = span_check(info.data(), nb, K);
-        if (C.off >= 0) {
-            span_reason_text(K, C.why, why, sizeof why);
-            snprintf(msg, sizeof msg, "%s: %s %d (fragments %d .. %d): %s", K.fn, K.noun, C.off, first[C.off], last[C.off], why);
-            refused = true;
+        if (h->nnz > 0) {
+            k_ex_nnz<<<stream_blocks(h->nnz), 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, sub, B->rec, R.fr, h->nfpb, h->par, quirk, far_kb, B->qb,
+                                                           B->cb, B->bad);
+            STEP_CK(hipGetLastError());
+        }
+        k_ex_edges<<<blocks_for(m + 1, 256), 256, 0, s>>>(m, B->rec, R.fr, reach, B->ne, B->nx);
+        STEP_CK(hipGetLastError());
+        long long total = 0;                                          // (<= fragments of the spans + spans x a window's fragments)
+        if ((rc = sp_unit_total(h, B, m, total))) break;
+        if ((total + 3) / 4 > (long long)INT_MAX) {
+            char msg[240];
+            snprintf(msg, sizeof msg, "%s: %lld work units exceed one launch: score fewer spans per call", K.fn, total);
+            unsupported = msg;
             break;
         }
-        const int m = (int)C.rec.size();
-        STEP_CK(hipMemsetAsync(B->q, 0, sizeof(long long) * (size_t)nb, s));
-        STEP_CK(hipMemsetAsync(B->c, 0, sizeof(long long) * (size_t)nb, s));
-        STEP_CK(hipMemcpyAsync(B->st, C.st.data(), (size_t)nb, hipMemcpyHostToDevice, s));
-        if (m > 0) {
-            long long max_lx = 0;
-            for (const SpanRec& r : C.rec) max_lx = std::max(max_lx, (long long)r.e1 - r.s0);
-            const float far_kb = (float)((double)max_lx / 1000.0 + 1.0);
-            STEP_CK(hipMemcpyAsync(B->rec, C.rec.data(), sizeof(SpanRec) * (size_t)m, hipMemcpyHostToDevice, s));
-            STEP_CK(hipMemsetAsync(B->qb, 0, sizeof(long long) * (size_t)m, s));
-            STEP_CK(hipMemsetAsync(B->cb, 0, sizeof(long long) * (size_t)m, s));
-            STEP_CK(hipMemsetAsync(B->bad, 0, sizeof(int) * (size_t)m, s));
-            k_ex_sub<<<blocks_for(n, 256), 256, 0, s>>>(n, m, B->rec, R.slot, R.lab, R.fr, h->d_sub_ids, B->sub);
-            STEP_CK(hipGetLastError());
-            if (h->nnz > 0) {
-                const long long waves = (h->nnz + 63) / 64;
-                const int g = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
-                k_ex_nnz<<<g, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, B->sub, B->rec, R.fr, h->nfpb, h->par, quirk, far_kb, B->qb, B->cb,
-                                           B->bad);
-                STEP_CK(hipGetLastError());
-            }
-            k_ex_edges<<<blocks_for(m + 1, 256), 256, 0, s>>>(m, B->rec, R.fr, reach, B->ne, B->nx);
-            STEP_CK(hipGetLastError());
-            size_t tb = B->tmp_bytes;
-            STEP_CK(hipcub::DeviceScan::ExclusiveSum(B->tmp, tb, B->ne, B->noff, m + 1, s));
-            long long total = 0;                                      // (<= fragments of the spans + spans x a window's fragments)
-            STEP_CK(hipMemcpyAsync(&total, B->noff + m, sizeof(long long), hipMemcpyDeviceToHost, s));
-            STEP_CK(hipStreamSynchronize(s));
-            if ((total + 3) / 4 > (long long)INT_MAX) {
-                snprintf(msg, sizeof msg, "%s: %lld work units exceed one launch: score fewer spans per call", K.fn, total);
-                unsupported = msg;
-                break;
-            }
-            if (total > 0) {
-                k_ex_mass<<<(unsigned)((total + 3) / 4), 256, 0, s>>>(total, m, B->rec, B->noff, B->ne, B->nx, R.fr, h->nfpb, h->par, quirk, reach,
-                                                                     B->qb, B->bad);
-                STEP_CK(hipGetLastError());
-            }
-            if (quirk && h->n_ubins) {
-                k_ex_quirk<<<blocks_for(m, 4), 256, 0, s>>>(m, B->rec, R.fr, R.lab, R.ctg, h->nfpb, h->par, reach, B->qb, B->bad);
-                STEP_CK(hipGetLastError());
-            }
-            k_sp_out<<<blocks_for(m, 256), 256, 0, s>>>(m, B->rec, B->qb, B->cb, B->bad, K.valid, K.nonfinite, B->q, B->c, B->st);
+        if (total > 0) {
+            k_ex_mass<<<(unsigned)((total + 3) / 4), 256, 0, s>>>(total, m, B->rec, B->noff, B->ne, B->nx, R.fr, h->nfpb, h->par, quirk, reach,
+                                                                 B->qb, B->bad);
             STEP_CK(hipGetLastError());
         }
-        STEP_CK(hipMemcpyAsync(q, B->q, sizeof(long long) * (size_t)nb, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipMemcpyAsync(contacts, B->c, sizeof(long long) * (size_t)nb, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipMemcpyAsync(status, B->st, (size_t)nb, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
+        if (quirk && h->n_ubins) {
+            k_ex_quirk<<<blocks_for(m, 4), 256, 0, s>>>(m, B->rec, R.fr, R.lab, R.ctg, h->nfpb, h->par, reach, B->qb, B->bad);
+            STEP_CK(hipGetLastError());
+        }
     } while (false);
-    if (refused) return fail(h, GRAAL_E_ARG, msg);
-    return score_exit(h, K.fn, rc, unsupported, err);
+    return rc;
 }
 
 } // namespace
@@ -434,7 +318,7 @@ int graal_block_excisions(graal_ctx* h, int32_t n_spans, const int32_t* first, c
     if (!h) return GRAAL_E_ARG;
     if (n_spans < 0 || (n_spans > 0 && (!first || !last || !q || !contacts || !status)))
         return fail(h, GRAAL_E_ARG, "graal_block_excisions: n_spans < 0 or a null array");
-    return excise_spans(h, n_spans, first, last, q, contacts, status);
+    return span_moves(h, SPAN_EXCISE, n_spans, first, nullptr, last, q, contacts, status, ex_score);
 }
 
 } // extern "C"

@@ -4100,10 +4100,8 @@ struct EdBuf;                  // edit.h: graal_edit_layout's buffers
 void ed_free(EdBuf* b);
 struct InBuf;                  // insert.h: graal_insertions' buffers and results
 void in_free(InBuf* b);
-struct SpanBuf;                // span_moves.h: graal_block_flips' and graal_block_swaps' buffers
+struct SpanBuf;                // span_moves.h: graal_block_flips', graal_block_swaps' and graal_block_excisions' buffers
 void sp_free(SpanBuf* b);
-struct ExBuf;                  // excise.h: graal_block_excisions' buffers
-void ex_free(ExBuf* b);
 struct RgBuf;                  // rings.h: graal_ring_scores' and graal_close_rings' buffers
 void rg_free(RgBuf* b);
 struct MpBuf;                  // maps.h: graal_layout_maps' buffers and images
@@ -4311,8 +4309,8 @@ struct Ctx {
     LnBuf* ln = nullptr;          // graal_end_links' buffers and its last result (links.h; allocated by its first call)
     EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
     InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
-    SpanBuf* sp = nullptr;        // graal_block_flips' and graal_block_swaps' buffers (span_moves.h; allocated by the first call of either)
-    ExBuf* ex = nullptr;          // graal_block_excisions' buffers (excise.h; allocated by its first call)
+    SpanBuf* sp = nullptr;        // graal_block_flips', graal_block_swaps' and graal_block_excisions' buffers (span_moves.h; allocated by
+                                  // the first call of any of them)
     RgBuf* rg = nullptr;          // graal_ring_scores' and graal_close_rings' buffers (rings.h; allocated by the first call of either)
     MpBuf* mp = nullptr;          // graal_layout_maps' buffers and images (maps.h; allocated by its first call)
 };
@@ -4891,7 +4889,6 @@ void graal_destroy(graal_ctx* h)
         ed_free(h->ed); h->ed = nullptr;
         in_free(h->ins); h->ins = nullptr;
         sp_free(h->sp); h->sp = nullptr;
-        ex_free(h->ex); h->ex = nullptr;
         rg_free(h->rg); h->rg = nullptr;
         mp_free(h->mp); h->mp = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
@@ -6346,6 +6343,7 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 
 #include "simulate.h"
 #include "score_common.h"
+#include "layout_slots.h"
 #include "junctions.h"
 #include "rings.h"
 #include "links.h"

@@ -1,7 +1,7 @@
 // insert.h -- the likelihood every insertion of a small contig into a junction would add, for every (piece, junction, orientation) the
 // contacts support (graal_insertions).  Included by graal_hip.hip after links.h (it uses LayoutRecs with recs_reserve / recs_build, the
 // records LnSub / LnFrag / LnCtg, ln_slot, ln_run_sum, ln_pair_mass, ln_quirk_pair, ln_mirror_q, k_ln_mirror, k_ln_flag and k_ln_keys, and
-// score_common.h's score_entry, score_exit, STEP_CK, free_null and CandTable).
+// score_common.h's score_entry, score_exit, STEP_CK, free_null, stream_blocks and CandTable).
 //
 // A PIECE is a linear contig P of 1 .. max_piece_frags fragments; a TARGET junction is a fragment f with next[f] = g != -1 of a linear
 // contig T != P.  The inserted layout cuts T between f and g into T1 (.. f) and T2 (g ..) and writes T1, P, T2 as one contig: T1 and T2
@@ -17,7 +17,7 @@
 // ob * (ln ex_plain - ln ex_trans) (zero unless the trans indexing differs): so every candidate (P, f, rev) gets the far terms of ALL P x T
 // contacts, a per-(P, T) sum, plus, for each contact inside the window at its junction, Q(term) - Q(far term) -- the same Q-rounded terms.
 // Kernels, all on the engine's stream:
-//   k_jn_count / scan / k_ln_prep(min_frags 1) / k_in_piece -- links.h's slots and records; a contig record's `elig` then marks a piece;
+//   recs_build (k_jn_count / scan / k_ln_prep, min_frags 1) / k_in_piece -- links.h's slots and records; a contig record's `elig` then marks a piece;
 //   row offsets of the contact list by row, for k_in_shift: the engine's own row index when the list was uploaded sorted by row (built
 //                 once per upload, k_rowptr); the upload takes the list in any order: k_in_unsorted checks it, an unsorted list is
 //                 radix-sorted by row into a permutation first and k_rowptr runs over that copy;
@@ -583,7 +583,7 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
             STEP_CK(hipGetLastError());
         }
         unsigned uns = 0;
-        STEP_CK(hipMemcpyAsync(&err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(&err, R.L.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
         STEP_CK(hipMemcpyAsync(&uns, B->uns, sizeof(unsigned), hipMemcpyDeviceToHost, s));
         STEP_CK(hipStreamSynchronize(s));
         if (err) break;   // (a corrupt layout: the slots and the sub-fragment records are not to be trusted, nothing reads them)
@@ -623,15 +623,14 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
             STEP_CK(hipGetLastError());
         }
         // ---- count pass: upper bounds of the distinct keys of the two tables
-        const long long waves = (h->nnz + 63) / 64;
-        const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
+        const int nb = stream_blocks(h->nnz);
         if (h->nnz > 0) {
-            k_in_nnz<true><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, R.fr, R.slot, h->nfpb, h->par, quirk,
+            k_in_nnz<true><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, R.fr, R.L.slot, h->nfpb, h->par, quirk,
                                               mq, reach, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                              nullptr, R.ctr, R.err);
+                                              nullptr, R.ctr, R.L.err);
             STEP_CK(hipGetLastError());
         }
-        STEP_CK(hipMemcpyAsync(&err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(&err, R.L.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
         STEP_CK(hipMemcpyAsync(ctr, R.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
         STEP_CK(hipStreamSynchronize(s));
         if (err) break;
@@ -689,9 +688,9 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
         }
         // ---- insert pass, selection of the listed slots, sort by key
         if (h->nnz > 0) {
-            k_in_nnz<false><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, R.fr, R.slot, h->nfpb, h->par, quirk,
+            k_in_nnz<false><<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, R.fr, R.L.slot, h->nfpb, h->par, quirk,
                                                mq, reach, cap, T.keys, T.tq, T.tc, T.tf, cap2, B->keys2, B->pf, B->pm, B->pb, R.mir,
-                                               R.mirbad, R.ctr, R.err);
+                                               R.mirbad, R.ctr, R.L.err);
             STEP_CK(hipGetLastError());
         }
         k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(T.keys, T.tf, (long long)cap, T.tsel);
@@ -700,7 +699,7 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
         STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)T.tsel, B->vo, &R.ctr[1],
                                             (int)cap, s));
         STEP_CK(hipMemcpyAsync(ctr, R.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
-        STEP_CK(hipMemcpyAsync(&err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(&err, R.L.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
         STEP_CK(hipStreamSynchronize(s));
         if (err) break;
         m = (long long)ctr[1];
@@ -721,16 +720,16 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
         STEP_CK(hipGetLastError());
         // ---- the mass passes, the quirk's passes, the result
         const unsigned wblocks = (unsigned)((m + 3) / 4);            // a wave per candidate, 4 waves per block
-        k_in_mass<<<wblocks, 256, 0, s>>>(m, B->piece, B->after, B->rev, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, quirk, reach, B->q,
+        k_in_mass<<<wblocks, 256, 0, s>>>(m, B->piece, B->after, B->rev, R.L.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, quirk, reach, B->q,
                                           B->bad);
         STEP_CK(hipGetLastError());
-        k_in_shift<<<wblocks, 256, 0, s>>>(m, B->lead, B->piece, B->after, R.slot, R.lab, R.ctg, R.fr, R.sub, h->stat_frag, h->d_sub_ids,
+        k_in_shift<<<wblocks, 256, 0, s>>>(m, B->lead, B->piece, B->after, R.L.slot, R.lab, R.ctg, R.fr, R.sub, h->stat_frag, h->d_sub_ids,
                                            rowptr, perm, h->col, h->cnt, h->nfpb, h->par, reach, B->sh, B->shbad);
         STEP_CK(hipGetLastError());
         if (mq) {
-            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, R.mir, R.mirbad);
+            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, R.L.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, R.mir, R.mirbad);
             STEP_CK(hipGetLastError());
-            k_in_quirk<<<wblocks, 256, 0, s>>>(m, B->piece, B->after, B->rev, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, reach, B->q, B->bad);
+            k_in_quirk<<<wblocks, 256, 0, s>>>(m, B->piece, B->after, B->rev, R.L.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, reach, B->q, B->bad);
             STEP_CK(hipGetLastError());
         }
         k_in_out<<<blocks_for(m, 256), 256, 0, s>>>(m, B->piece, B->after, B->rev, B->lead, R.lab, B->sh, B->shbad, mq, R.mir, R.mirbad, cap2,

@@ -1,6 +1,7 @@
 // junctions.h -- the likelihood each join of the current layout carries, for every junction in one pass (graal_junction_scores).
-// Included by graal_hip.hip after score_common.h (it uses Ctx, Stat, centre_kb, rippe, to_q, WAVE_LDS_SYNC, model_math.h, and
-// score_common.h's score_entry, score_exit, STEP_CK and free_null).
+// Included by graal_hip.hip after layout_slots.h (it uses Ctx, Stat, centre_kb, rippe, to_q, WAVE_LDS_SYNC, model_math.h,
+// score_common.h's score_entry, score_exit, STEP_CK, free_null, stream_blocks and mass_stripes, and layout_slots.h's LayoutSlots and
+// slot_claim).
 //
 // J[f] = logL(layout) - logL(layout cut between f and next[f]), for f in a LINEAR contig with next[f] != -1, in the engine's exact
 // arithmetic: pairs on one side of the cut are exactly unchanged, so only the pairs that STRADDLE the cut contribute -- they go from their cis
@@ -13,10 +14,10 @@
 // exactly the pairs with i <= k < j, so J = the inclusive prefix sum of D at f's slot.  Every pair adds and removes its term inside its own
 // contig, so one inclusive scan over all slots is the per-contig scan (int64 sums wrap, the differences are exact).
 //
-// The slot numbering is built here from the layout itself (contig label -> member count -> exclusive scan -> offset + position), not taken
-// from the engine's position index: the call does not relabel, and so leaves the ranked layout, the carried total and a pending commit's
-// correction exactly as they were.  Kernels, all on the engine's stream (behind any commit or relabel the host has launched):
-//   k_jn_count / scan / k_jn_prep  -- slots, a 48-byte record per slot and a 16-byte record per sub-fragment (centre as the pricing has it);
+// The slot numbering is layout_slots.h's, built from the layout itself: the call does not relabel.  Kernels, all on the engine's stream
+// (behind any commit or relabel the host has launched):
+//   slots_count (k_jn_count / scan) / k_jn_prep  -- slots, a 48-byte record per slot and a 16-byte record per sub-fragment (centre as the
+//                 pricing has it);
 //   k_jn_nnz   -- streams the row-sorted COO list, 64 consecutive contacts per wave; terms are summed per run of equal slots inside the wave
 //                 (a segmented shuffle scan) and only a run's last lane touches D: a row's contacts share its slot, so the row side costs
 //                 about one atomic per row and wave; the column side one per run of equal column slots;
@@ -36,21 +37,19 @@ struct JnFrag { int frag, start_bp, len_bp, flags; int n, a0, a1, a2; float c0, 
 
 struct JnBuf {
     int n = 0, S = 0;
-    int *cnt = nullptr, *base = nullptr, *slot = nullptr;
+    LayoutSlots L;                                         // (its tmp also serves the two inclusive scans)
     JnFrag* fr = nullptr;
     JnSub* sub = nullptr;
     long long *D = nullptr, *P = nullptr;
     int *B = nullptr, *PB = nullptr;
     long long* q = nullptr; unsigned char* st = nullptr;   // the results, fragment-indexed
-    void* tmp = nullptr; size_t tmp_bytes = 0;
-    unsigned* err = nullptr;
 };
 
 void jn_free_all(JnBuf* b)
 {
-    free_null({(void**)&b->cnt, (void**)&b->base, (void**)&b->slot, (void**)&b->fr, (void**)&b->sub, (void**)&b->D, (void**)&b->P, (void**)&b->B,
-               (void**)&b->PB, (void**)&b->q, (void**)&b->st, &b->tmp, (void**)&b->err});
-    b->tmp_bytes = 0; b->n = 0; b->S = 0;
+    slots_free(b->L);
+    free_null({(void**)&b->fr, (void**)&b->sub, (void**)&b->D, (void**)&b->P, (void**)&b->B, (void**)&b->PB, (void**)&b->q, (void**)&b->st});
+    b->n = 0; b->S = 0;
 }
 
 void jn_free(JnBuf* b)
@@ -60,14 +59,20 @@ void jn_free(JnBuf* b)
     delete b;
 }
 
-// members per contig label (labels lie in [0, n + 2]: the mutations keep them in [0, n_contigs + 2])
-__global__ void k_jn_count(SoaPtr s, int n, int* __restrict__ cnt, unsigned* __restrict__ err)
+// What k_jn_prep and k_rg_prep read of fragment f: its bp interval, orientation and topology, its Stat, and the centres of its (up to
+// three) sub-fragments as the pricing has them.
+struct JnLoad { Stat st; int start, len; bool fwd, circ; float c0, c1, c2; };
+
+__device__ __forceinline__ JnLoad jn_load(SoaPtr s, const Stat* __restrict__ stat, int f)
 {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n) return;
-    const int c = s.p[F_IDC][f];
-    if (c < 0 || c > n + 2) { atomicOr(err, 1u); return; }
-    atomicAdd(&cnt[c], 1);
+    JnLoad x;
+    x.st = stat[f];
+    x.fwd = s.p[F_ORI][f] == 1; x.circ = s.p[F_CIRC][f] == 1;
+    x.start = s.p[F_START][f]; x.len = s.p[F_LEN][f];
+    x.c0 = x.st.n > 0 ? centre_kb(x.start, x.fwd, x.st, 0) : 0.0f;
+    x.c1 = x.st.n > 1 ? centre_kb(x.start, x.fwd, x.st, 1) : 0.0f;
+    x.c2 = x.st.n > 2 ? centre_kb(x.start, x.fwd, x.st, 2) : 0.0f;
+    return x;
 }
 
 __global__ __launch_bounds__(256) void k_jn_prep(SoaPtr s, int n, const Stat* __restrict__ stat, const int* __restrict__ sub_ids,
@@ -76,20 +81,15 @@ __global__ __launch_bounds__(256) void k_jn_prep(SoaPtr s, int n, const Stat* __
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
-    const int c = s.p[F_IDC][f], pos = s.p[F_POS][f];
-    if (c < 0 || c > n + 2 || pos < 0 || pos >= cnt[c]) { atomicOr(err, 2u); slot_of[f] = -1; return; }
-    const int slot = base[c] + pos;
-    if (slot < 0 || slot >= n) { atomicOr(err, 2u); slot_of[f] = -1; return; }
-    slot_of[f] = slot;
-    const Stat st = stat[f];
-    const bool fwd = s.p[F_ORI][f] == 1, circ = s.p[F_CIRC][f] == 1;
-    const int start = s.p[F_START][f];
+    const int slot = slot_claim(s, n, f, cnt, base, slot_of, err);
+    if (slot < 0) return;
+    const int c = s.p[F_IDC][f];
+    const JnLoad x = jn_load(s, stat, f);
+    const Stat& st = x.st;
     JnFrag r;
-    r.frag = f; r.start_bp = start; r.len_bp = s.p[F_LEN][f]; r.flags = (fwd ? 1 : 0) | (circ ? 2 : 0);
+    r.frag = f; r.start_bp = x.start; r.len_bp = x.len; r.flags = (x.fwd ? 1 : 0) | (x.circ ? 2 : 0);
     r.n = st.n; r.a0 = st.a0; r.a1 = st.a1; r.a2 = st.a2;
-    r.c0 = st.n > 0 ? centre_kb(start, fwd, st, 0) : 0.0f;
-    r.c1 = st.n > 1 ? centre_kb(start, fwd, st, 1) : 0.0f;
-    r.c2 = st.n > 2 ? centre_kb(start, fwd, st, 2) : 0.0f;
+    r.c0 = x.c0; r.c1 = x.c1; r.c2 = x.c2;
     r.last = base[c] + cnt[c] - 1;
     fr[slot] = r;
     int4 ids = make_int4(f, 0, 0, 1);
@@ -98,8 +98,8 @@ __global__ __launch_bounds__(256) void k_jn_prep(SoaPtr s, int n, const Stat* __
         JnSub u;
         u.label = c;
         u.centre = sel3(r.c0, r.c1, r.c2, k);
-        u.accu = stat_accu(st, k) | ((fwd ? stat_accu(st, k) : stat_accu(st, st.n - 1)) << 16);   // (RF counts are <= 30000)
-        u.slot = circ ? -1 : slot;
+        u.accu = stat_accu(st, k) | ((x.fwd ? stat_accu(st, k) : stat_accu(st, st.n - 1)) << 16);   // (RF counts are <= 30000)
+        u.slot = x.circ ? -1 : slot;
         sub[sel3(ids.x, ids.y, ids.z, k)] = u;
     }
 }
@@ -298,10 +298,11 @@ int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status)
     JnBuf* J = h->jn;
     hipStream_t s = h->stream;
     if (J->n != n || J->S != S) {
-        jn_free_all(J);   // (J->n stays 0 until the whole set is allocated: free_null)
-        CK(hipMalloc(&J->cnt, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&J->base, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&J->slot, sizeof(int) * (size_t)n));
+        jn_free_all(J);
+        size_t b2 = 0, b3 = 0;
+        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b2, J->D, J->P, n, s));
+        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b3, J->B, J->PB, n, s));
+        if (const int rc = slots_reserve(h, J->L, std::max(b2, b3))) return rc;
         CK(hipMalloc(&J->fr, sizeof(JnFrag) * (size_t)n));
         CK(hipMalloc(&J->sub, sizeof(JnSub) * (size_t)std::max(S, 1)));
         CK(hipMalloc(&J->D, sizeof(long long) * (size_t)n));
@@ -310,55 +311,39 @@ int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status)
         CK(hipMalloc(&J->PB, sizeof(int) * (size_t)n));
         CK(hipMalloc(&J->q, sizeof(long long) * (size_t)n));
         CK(hipMalloc(&J->st, (size_t)n));
-        CK(hipMalloc(&J->err, sizeof(unsigned)));
-        size_t b1 = 0, b2 = 0, b3 = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, J->cnt, J->base, n + 3, s));
-        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b2, J->D, J->P, n, s));
-        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b3, J->B, J->PB, n, s));
-        const size_t tb = std::max(b1, std::max(b2, b3));
-        CK(hipMalloc(&J->tmp, tb));
-        J->tmp_bytes = tb;
         J->n = n; J->S = S;
     }
+    LayoutSlots& L = J->L;
     const SoaPtr sp = h->soa[h->cur];
     const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     int rc = GRAAL_OK;
     unsigned err = 0;
     do {
-        STEP_CK(hipMemsetAsync(J->err, 0, sizeof(unsigned), s));
-        STEP_CK(hipMemsetAsync(J->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
         STEP_CK(hipMemsetAsync(J->D, 0, sizeof(long long) * (size_t)n, s));
         STEP_CK(hipMemsetAsync(J->B, 0, sizeof(int) * (size_t)n, s));
         STEP_CK(hipMemsetAsync(J->fr, 0, sizeof(JnFrag) * (size_t)n, s));   // (a slot no fragment claims -- a corrupt layout -- reads as empty)
-        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, J->cnt, J->err);
+        if ((rc = slots_count(h, L))) break;
+        k_jn_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, h->stat_frag, h->d_sub_ids, L.cnt, L.base, L.slot, J->fr, J->sub, L.err);
         STEP_CK(hipGetLastError());
-        size_t tb = J->tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(J->tmp, tb, J->cnt, J->base, n + 3, s));
-        k_jn_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, h->stat_frag, h->d_sub_ids, J->cnt, J->base, J->slot, J->fr, J->sub, J->err);
-        STEP_CK(hipGetLastError());
-        STEP_CK(hipMemcpyAsync(&err, J->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (err) break;   // (a corrupt layout: the slots are not to be trusted, nothing reads them)
+        if ((rc = slots_read_err(h, L, err)) || err) break;
         if (h->nnz > 0) {
-            const long long waves = (h->nnz + 63) / 64;
-            const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
-            k_jn_nnz<<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, J->sub, J->fr, h->nfpb, h->par, quirk, J->D, J->B);
+            k_jn_nnz<<<stream_blocks(h->nnz), 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, J->sub, J->fr, h->nfpb, h->par, quirk, J->D, J->B);
             STEP_CK(hipGetLastError());
         }
         const int lc = std::min(std::max(std::max(h->max_lcont, h->lcont_bound), 1), n);
         const int n_tiles = (n + 63) / 64;
-        const int Sw = std::min(16, std::max(1, ((lc + 63) / 64 + 7) / 8));
+        const int Sw = mass_stripes(lc);
         k_jn_mass<<<(n_tiles * Sw + 3) / 4, 256, 0, s>>>(n, J->fr, h->nfpb, h->par, quirk, reach_bp(h), Sw, J->D, J->B);
         STEP_CK(hipGetLastError());
         if (quirk && h->n_ubins) {
-            k_jn_quirk<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, J->slot, J->fr, h->nfpb, h->par, reach_bp(h), J->D, J->B);
+            k_jn_quirk<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, L.slot, J->fr, h->nfpb, h->par, reach_bp(h), J->D, J->B);
             STEP_CK(hipGetLastError());
         }
-        tb = J->tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::InclusiveSum(J->tmp, tb, J->D, J->P, n, s));
-        tb = J->tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::InclusiveSum(J->tmp, tb, J->B, J->PB, n, s));
-        k_jn_out<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, J->slot, J->P, J->PB, J->q, J->st);
+        size_t tb = L.tmp_bytes;
+        STEP_CK(hipcub::DeviceScan::InclusiveSum(L.tmp, tb, J->D, J->P, n, s));
+        tb = L.tmp_bytes;
+        STEP_CK(hipcub::DeviceScan::InclusiveSum(L.tmp, tb, J->B, J->PB, n, s));
+        k_jn_out<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, L.slot, J->P, J->PB, J->q, J->st);
         STEP_CK(hipGetLastError());
         STEP_CK(hipMemcpyAsync(q_out, J->q, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, s));
         STEP_CK(hipMemcpyAsync(status, J->st, (size_t)n, hipMemcpyDeviceToHost, s));

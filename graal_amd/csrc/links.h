@@ -1,6 +1,7 @@
 // links.h -- the likelihood every join between two contig ends would add, for every pair of ends the contacts support (graal_end_links).
-// Included by graal_hip.hip after junctions.h (it uses Ctx, Stat, centre_kb, rippe, to_q, k_jn_count, jn_trans, model_math.h, and
-// score_common.h's score_entry, score_exit, STEP_CK, free_null and CandTable).  LayoutRecs, below, is shared with insert.h.
+// Included by graal_hip.hip after rings.h (it uses Ctx, Stat, centre_kb, rippe, to_q, jn_trans, model_math.h, score_common.h's
+// score_entry, score_exit, STEP_CK, free_null, stream_blocks and CandTable, and layout_slots.h's LayoutSlots and slot_claim).
+// LayoutRecs, below, is shared with insert.h, span_moves.h and excise.h.
 //
 // Ends.  end = 2 * f + side of a LINEAR contig: side 0 its head (position 0), side 1 its tail (position l_cont - 1), f the fragment there.
 // For ends eA < eB of different contigs A, B the joined layout is canonical: A oriented so that eA is its tail (A reversed iff eA is a head),
@@ -17,7 +18,7 @@
 //
 // Which links are listed: the pairs of ends with at least one contact between their contigs inside the window (sub-fragment centre
 // distance < d_max) in the joined orientation.  Kernels, all on the engine's stream:
-//   k_jn_count / scan / k_ln_prep -- slots (junctions.h's numbering: label -> count -> exclusive scan -> offset + position), a 48-byte
+//   slots_count (k_jn_count / scan) / k_ln_prep -- slots (layout_slots.h's numbering), a 48-byte
 //                 record per slot, a 32-byte record per sub-fragment and a 32-byte record per contig label (end fragments, bp length,
 //                 eligibility: linear with >= min_frags fragments);
 //   k_ln_nnz<COUNT> -- streams the row-sorted COO list, 64 contacts per wave; for a contact between two eligible contigs each of the 4
@@ -51,11 +52,9 @@ __global__ __launch_bounds__(256) void k_ln_prep(SoaPtr s, int n, int min_frags,
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
+    const int slot = slot_claim(s, n, f, cnt, base, slot_of, err);
+    if (slot < 0) { lab[f] = -1; return; }
     const int c = s.p[F_IDC][f], pos = s.p[F_POS][f];
-    if (c < 0 || c > n + 2 || pos < 0 || pos >= cnt[c]) { atomicOr(err, 2u); slot_of[f] = -1; lab[f] = -1; return; }
-    const int slot = base[c] + pos;
-    if (slot < 0 || slot >= n) { atomicOr(err, 2u); slot_of[f] = -1; lab[f] = -1; return; }
-    slot_of[f] = slot;
     lab[f] = c;
     const Stat st = stat[f];
     const bool fwd = s.p[F_ORI][f] == 1, circ = s.p[F_CIRC][f] == 1;
@@ -83,73 +82,60 @@ __global__ __launch_bounds__(256) void k_ln_prep(SoaPtr s, int n, int min_frags,
     }
 }
 
-// The slots and records of a layout (k_jn_count / scan / k_ln_prep) and what is summed per contig label.  links.h and insert.h each own
-// one instance: no state is shared between their calls.
+// The slots and records of a layout (slots_count / k_ln_prep) and what is summed per contig label.  links.h, insert.h and span_moves.h
+// each own one instance: no state is shared between their calls.
 struct LayoutRecs {
     int n = 0, S = 0;
-    int *cnt = nullptr, *base = nullptr, *slot = nullptr, *lab = nullptr;
+    LayoutSlots L;
+    int* lab = nullptr;
     LnFrag* fr = nullptr;
     LnSub* sub = nullptr;
     LnCtg* ctg = nullptr;
     long long* mir = nullptr; int* mirbad = nullptr;
-    unsigned* err = nullptr;
     unsigned long long* ctr = nullptr;   // [0] records counted, [1] listed keys, [2] eligible contigs, [3] insert.h's pair records
-    void* tmp = nullptr; size_t tmp_bytes = 0;
 };
 
 void recs_free(LayoutRecs& R)
 {
-    free_null({(void**)&R.cnt, (void**)&R.base, (void**)&R.slot, (void**)&R.lab, (void**)&R.fr, (void**)&R.sub, (void**)&R.ctg, (void**)&R.mir,
-               (void**)&R.mirbad, (void**)&R.err, (void**)&R.ctr, &R.tmp});
-    R.tmp_bytes = 0; R.n = 0; R.S = 0;
+    slots_free(R.L);
+    free_null({(void**)&R.lab, (void**)&R.fr, (void**)&R.sub, (void**)&R.ctg, (void**)&R.mir, (void**)&R.mirbad, (void**)&R.ctr});
+    R.n = 0; R.S = 0;
 }
 
-// Sized to the engine's (n, S), reallocated when they change.  R.n stays 0 until the whole set is allocated (free_null).
+// Sized to the engine's (n, S), reallocated when they change.
 int recs_reserve(Ctx* h, LayoutRecs& R)
 {
     const int n = h->n, S = h->n_sub_total;
     if (R.n == n && R.S == S) return GRAAL_OK;
     recs_free(R);
-    CK(hipMalloc(&R.cnt, sizeof(int) * (size_t)(n + 3)));
-    CK(hipMalloc(&R.base, sizeof(int) * (size_t)(n + 3)));
-    CK(hipMalloc(&R.slot, sizeof(int) * (size_t)n));
+    if (const int rc = slots_reserve(h, R.L)) return rc;
     CK(hipMalloc(&R.lab, sizeof(int) * (size_t)n));
     CK(hipMalloc(&R.fr, sizeof(LnFrag) * (size_t)n));
     CK(hipMalloc(&R.sub, sizeof(LnSub) * (size_t)std::max(S, 1)));
     CK(hipMalloc(&R.ctg, sizeof(LnCtg) * (size_t)(n + 3)));
     CK(hipMalloc(&R.mir, sizeof(long long) * (size_t)(n + 3)));
     CK(hipMalloc(&R.mirbad, sizeof(int) * (size_t)(n + 3)));
-    CK(hipMalloc(&R.err, sizeof(unsigned)));
     CK(hipMalloc(&R.ctr, sizeof(unsigned long long) * 4));
-    size_t b1 = 0;
-    CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, R.cnt, R.base, n + 3, h->stream));
-    CK(hipMalloc(&R.tmp, b1));
-    R.tmp_bytes = b1;
     R.n = n; R.S = S;
     return GRAAL_OK;
 }
 
-// The records of the current layout, on the engine's stream.  R.err collects the flags of a corrupt layout: the caller reads it back
-// before anything trusts the slots or the sub-fragment records.
+// The records of the current layout, on the engine's stream.  R.L.err collects the flags of a corrupt layout: the caller reads it back
+// (slots_read_err) before anything trusts the slots or the sub-fragment records.
 int recs_build(Ctx* h, LayoutRecs& R, int min_frags)
 {
     const int n = R.n;
     hipStream_t s = h->stream;
     int rc = GRAAL_OK;
     do {
-        STEP_CK(hipMemsetAsync(R.err, 0, sizeof(unsigned), s));
         STEP_CK(hipMemsetAsync(R.ctr, 0, sizeof(unsigned long long) * 4, s));
-        STEP_CK(hipMemsetAsync(R.cnt, 0, sizeof(int) * (size_t)(n + 3), s));
         STEP_CK(hipMemsetAsync(R.ctg, 0, sizeof(LnCtg) * (size_t)(n + 3), s));   // (labels no fragment holds: not eligible)
         STEP_CK(hipMemsetAsync(R.fr, 0, sizeof(LnFrag) * (size_t)n, s));
         STEP_CK(hipMemsetAsync(R.mir, 0, sizeof(long long) * (size_t)(n + 3), s));
         STEP_CK(hipMemsetAsync(R.mirbad, 0, sizeof(int) * (size_t)(n + 3), s));
-        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(h->soa[h->cur], n, R.cnt, R.err);
-        STEP_CK(hipGetLastError());
-        size_t tb = R.tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(R.tmp, tb, R.cnt, R.base, n + 3, s));
-        k_ln_prep<<<blocks_for(n, 256), 256, 0, s>>>(h->soa[h->cur], n, min_frags, h->stat_frag, h->d_sub_ids, R.cnt, R.base, R.slot, R.lab, R.fr,
-                                                     R.sub, R.ctg, &R.ctr[2], R.err);
+        if ((rc = slots_count(h, R.L))) break;
+        k_ln_prep<<<blocks_for(n, 256), 256, 0, s>>>(h->soa[h->cur], n, min_frags, h->stat_frag, h->d_sub_ids, R.L.cnt, R.L.base, R.L.slot, R.lab,
+                                                     R.fr, R.sub, R.ctg, &R.ctr[2], R.L.err);
         STEP_CK(hipGetLastError());
     } while (false);
     return rc;
@@ -745,21 +731,15 @@ int ln_count(Ctx* h, LayoutRecs& R, int min_frags, int quirk, LnCount& C)
     hipStream_t s = h->stream;
     int rc = GRAAL_OK;
     do {
-        if ((rc = recs_build(h, R, min_frags))) break;
-        STEP_CK(hipMemcpyAsync(&C.err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (C.err) break;
-        const long long waves = (h->nnz + 63) / 64;
-        C.nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
+        if ((rc = recs_build(h, R, min_frags)) || (rc = slots_read_err(h, R.L, C.err)) || C.err) break;
+        C.nb = stream_blocks(h->nnz);
         if (h->nnz > 0) {
             k_ln_nnz<true><<<C.nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, h->nfpb, h->par, quirk, 0, nullptr,
-                                                nullptr, nullptr, nullptr, nullptr, nullptr, &R.ctr[0], R.err);
+                                                nullptr, nullptr, nullptr, nullptr, nullptr, &R.ctr[0], R.L.err);
             STEP_CK(hipGetLastError());
         }
-        STEP_CK(hipMemcpyAsync(&C.err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
         STEP_CK(hipMemcpyAsync(C.ctr, R.ctr, sizeof C.ctr, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (C.err) break;
+        if ((rc = slots_read_err(h, R.L, C.err)) || C.err) break;
         const unsigned long long E = 2ull * C.ctr[2];
         C.bound = std::min<unsigned long long>(C.ctr[0], E * (E > 0 ? E - 1 : 0) / 2);
         C.cap = table_cap(C.bound);
@@ -831,7 +811,7 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
         // ---- insert pass, selection of the listed slots, sort by key
         if (h->nnz > 0) {
             k_ln_nnz<false><<<C.nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, h->nfpb, h->par, quirk, cap, T.keys,
-                                                 T.tq, T.tc, T.tf, R.mir, R.mirbad, &R.ctr[0], R.err);
+                                                 T.tq, T.tc, T.tf, R.mir, R.mirbad, &R.ctr[0], R.L.err);
             STEP_CK(hipGetLastError());
         }
         k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(T.keys, T.tf, (long long)cap, T.tsel);
@@ -840,9 +820,7 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
         STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)T.tsel, Lb->vo, &R.ctr[1],
                                               (int)cap, s));
         STEP_CK(hipMemcpyAsync(C.ctr, R.ctr, sizeof C.ctr, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipMemcpyAsync(&C.err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (C.err) break;
+        if ((rc = slots_read_err(h, R.L, C.err)) || C.err) break;
         m = (long long)C.ctr[1];
         if (m == 0) break;
         k_ln_keys<<<blocks_for(m, 256), 256, 0, s>>>(m, T.keys, Lb->vo, Lb->ko);
@@ -871,7 +849,7 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
             STEP_CK(hipGetLastError());
         }
         if (mq) {
-            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, R.mir, R.mirbad);
+            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, R.L.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, R.mir, R.mirbad);
             STEP_CK(hipGetLastError());
             if (groups > 0)
                 k_ln_quirk<<<(unsigned)((groups + 3) / 4), 256, 0, s>>>(m, groups, Lb->choff, Lb->ch, Lb->ea, Lb->eb, R.lab, R.ctg, R.fr, h->nfpb,
@@ -960,14 +938,14 @@ int graal_end_links_best(graal_ctx* h, int32_t min_frags, int32_t* best_end, int
         // ---- insert pass, then the scores in place: mass, the quirk's passes, mirrors and status
         if (h->nnz > 0) {
             k_ln_nnz<false><<<C.nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R.sub, h->stat_frag, R.ctg, h->nfpb, h->par, quirk, cap, T.keys,
-                                                 T.tq, T.tc, T.tf, R.mir, R.mirbad, &R.ctr[0], R.err);
+                                                 T.tq, T.tc, T.tf, R.mir, R.mirbad, &R.ctr[0], R.L.err);
             STEP_CK(hipGetLastError());
         }
         const unsigned wblocks = (unsigned)((cap + 3) / 4);          // a wave per slot, 4 waves per block
         k_lb_mass<<<wblocks, 256, 0, s>>>((long long)cap, T.keys, T.tf, R.lab, R.ctg, R.fr, h->nfpb, h->par, quirk, reach_bp(h), T.tq);
         STEP_CK(hipGetLastError());
         if (mq) {
-            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, R.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, R.mir, R.mirbad);
+            k_ln_mirror<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, R.L.slot, R.lab, R.ctg, R.fr, h->nfpb, h->par, R.mir, R.mirbad);
             STEP_CK(hipGetLastError());
             k_lb_quirk<<<wblocks, 256, 0, s>>>((long long)cap, T.keys, T.tf, R.lab, R.ctg, R.fr, h->nfpb, h->par, reach_bp(h), T.tq);
             STEP_CK(hipGetLastError());
@@ -983,9 +961,7 @@ int graal_end_links_best(graal_ctx* h, int32_t min_frags, int32_t* best_end, int
         STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)Lb->bflag, Lb->bsel,
                                               &R.ctr[1], (int)n2, s));
         STEP_CK(hipMemcpyAsync(C.ctr, R.ctr, sizeof C.ctr, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipMemcpyAsync(&C.err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (C.err) break;
+        if ((rc = slots_read_err(h, R.L, C.err)) || C.err) break;
         m = (long long)C.ctr[1];
         if (m > 0) {
             k_lb_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->bsel, Lb->bq, Lb->be, Lb->mea, Lb->meb, Lb->mq);

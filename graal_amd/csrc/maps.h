@@ -1,7 +1,7 @@
 // maps.h -- the observed contacts, the contacts the model expects and their residual as images in the current genome order
 // (graal_layout_maps / graal_layout_maps_fetch; semantics in include/graal_hip.h).
-// Included by graal_hip.hip after junctions.h (it uses score_common.h, map_shape.h, and junctions.h's slot numbering: k_jn_count, k_jn_prep,
-// JnFrag, jn_run_sum).
+// Included by graal_hip.hip after edit.h (it uses score_common.h, map_shape.h, layout_slots.h's LayoutSlots, and junctions.h's
+// records of the slots: k_jn_prep, JnFrag, jn_run_sum).
 //
 // Order.  Slots as for the junction scores (contig label -> member count -> exclusive scan -> offset + position: contigs by ascending label,
 // fragments by position), built from the layout fields, not from the engine's position index: the call does not relabel.  One more
@@ -9,7 +9,7 @@
 // reversed when ori == -1.  Rank u lies in pixel u / bin (map_shape.h).
 //
 // Kernels, all on the engine's stream:
-//   k_jn_count / scan / k_jn_prep / k_mp_slots / scan / k_mp_rank -- slots, ranks, pixel_of_sub, and per pixel the sum of the RF counts and of
+//   slots_count (k_jn_count / scan) / k_jn_prep / k_mp_slots / scan / k_mp_rank -- slots, ranks, pixel_of_sub, and per pixel the sum of the RF counts and of
 //                their squares (int64, exact);
 //   k_mp_obs  -- streams the contact list, 64 consecutive contacts per wave; count * 2^24 rounded once, summed per run of equal pixels inside
 //                the wave (jn_run_sum), one int64 atomic per run into the upper triangle;
@@ -31,12 +31,11 @@ struct MpTile { int start_bp, n, r0, fwd; float c0, c1, c2; int a0, a1, a2, pad0
 
 struct MpBuf {
     int n = 0, S = 0;                         // the layout buffers' sizes
-    int *cnt = nullptr, *base = nullptr, *slot = nullptr, *nsub = nullptr, *rank0 = nullptr, *lbp = nullptr, *pix = nullptr;
+    LayoutSlots L;                            // (its tmp also serves the scan of nsub)
+    int *nsub = nullptr, *rank0 = nullptr, *lbp = nullptr, *pix = nullptr;
     JnFrag* fr = nullptr;
     JnSub* sub = nullptr;
     long long *A = nullptr, *A2 = nullptr;    // per pixel: sum of RF counts, sum of their squares
-    void* tmp = nullptr; size_t tmp_bytes = 0;
-    unsigned* err = nullptr;
     unsigned long long* nbad = nullptr;
     size_t px_cap = 0;                        // pixels the image buffers hold (they only grow)
     long long *O = nullptr, *E = nullptr;
@@ -48,9 +47,10 @@ struct MpBuf {
 
 void mp_free_layout(MpBuf* b)
 {
-    free_null({(void**)&b->cnt, (void**)&b->base, (void**)&b->slot, (void**)&b->nsub, (void**)&b->rank0, (void**)&b->lbp, (void**)&b->pix,
-               (void**)&b->fr, (void**)&b->sub, (void**)&b->A, (void**)&b->A2, &b->tmp, (void**)&b->err, (void**)&b->nbad});
-    b->tmp_bytes = 0; b->n = 0; b->S = 0;
+    slots_free(b->L);
+    free_null({(void**)&b->nsub, (void**)&b->rank0, (void**)&b->lbp, (void**)&b->pix, (void**)&b->fr, (void**)&b->sub, (void**)&b->A,
+               (void**)&b->A2, (void**)&b->nbad});
+    b->n = 0; b->S = 0;
 }
 
 void mp_free_images(MpBuf* b)
@@ -278,10 +278,10 @@ int graal_layout_maps(graal_ctx* h, int32_t max_px, int32_t* m_out, int32_t* bin
     if (n < 1 || S < 1) { M->m = 0; M->bin = 1; M->valid = true; if (m_out) *m_out = 0; return GRAAL_OK; }
     hipStream_t s = h->stream;
     if (M->n != n || M->S != S) {
-        mp_free_layout(M);   // (M->n stays 0 until the whole set is allocated: free_null)
-        CK(hipMalloc(&M->cnt, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&M->base, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&M->slot, sizeof(int) * (size_t)n));
+        mp_free_layout(M);
+        size_t b2 = 0;
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, M->nsub, M->rank0, n, s));
+        if (const int rc = slots_reserve(h, M->L, b2)) return rc;
         CK(hipMalloc(&M->nsub, sizeof(int) * (size_t)n));
         CK(hipMalloc(&M->rank0, sizeof(int) * (size_t)n));
         CK(hipMalloc(&M->lbp, sizeof(int) * (size_t)n));
@@ -290,13 +290,7 @@ int graal_layout_maps(graal_ctx* h, int32_t max_px, int32_t* m_out, int32_t* bin
         CK(hipMalloc(&M->sub, sizeof(JnSub) * (size_t)S));
         CK(hipMalloc(&M->A, sizeof(long long) * (size_t)S));      // (m <= S)
         CK(hipMalloc(&M->A2, sizeof(long long) * (size_t)S));
-        CK(hipMalloc(&M->err, sizeof(unsigned)));
         CK(hipMalloc(&M->nbad, sizeof(unsigned long long)));
-        size_t b1 = 0, b2 = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, M->cnt, M->base, n + 3, s));
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, M->nsub, M->rank0, n, s));
-        CK(hipMalloc(&M->tmp, std::max(b1, b2)));
-        M->tmp_bytes = std::max(b1, b2);
         M->n = n; M->S = S;
     }
     const size_t px = (size_t)m * (size_t)m, bad_words = (px + 31) / 32;
@@ -310,14 +304,13 @@ int graal_layout_maps(graal_ctx* h, int32_t max_px, int32_t* m_out, int32_t* bin
         CK(hipMalloc(&M->res, sizeof(float) * px));
         M->px_cap = px;
     }
+    LayoutSlots& L = M->L;
     const SoaPtr sp = h->soa[h->cur];
     int rc = GRAAL_OK;
     unsigned err = 0;
     unsigned long long nbad = 0;
     do {
-        STEP_CK(hipMemsetAsync(M->err, 0, sizeof(unsigned), s));
         STEP_CK(hipMemsetAsync(M->nbad, 0, sizeof(unsigned long long), s));
-        STEP_CK(hipMemsetAsync(M->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
         STEP_CK(hipMemsetAsync(M->nsub, 0, sizeof(int) * (size_t)n, s));
         STEP_CK(hipMemsetAsync(M->lbp, 0, sizeof(int) * (size_t)n, s));
         STEP_CK(hipMemsetAsync(M->fr, 0, sizeof(JnFrag) * (size_t)n, s));   // (a slot no fragment claims -- a corrupt layout -- reads as empty)
@@ -327,33 +320,24 @@ int graal_layout_maps(graal_ctx* h, int32_t max_px, int32_t* m_out, int32_t* bin
         STEP_CK(hipMemsetAsync(M->O, 0, sizeof(long long) * px, s));
         STEP_CK(hipMemsetAsync(M->E, 0, sizeof(long long) * px, s));
         STEP_CK(hipMemsetAsync(M->badmap, 0, sizeof(unsigned) * bad_words, s));
-        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, M->cnt, M->err);
+        if ((rc = slots_count(h, L))) break;
+        k_jn_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, h->stat_frag, h->d_sub_ids, L.cnt, L.base, L.slot, M->fr, M->sub, L.err);
         STEP_CK(hipGetLastError());
-        size_t tb = M->tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(M->tmp, tb, M->cnt, M->base, n + 3, s));
-        k_jn_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, h->stat_frag, h->d_sub_ids, M->cnt, M->base, M->slot, M->fr, M->sub, M->err);
+        k_mp_slots<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, L.slot, h->stat_frag, M->nsub, M->lbp, L.err);
         STEP_CK(hipGetLastError());
-        k_mp_slots<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, M->slot, h->stat_frag, M->nsub, M->lbp, M->err);
+        if ((rc = slots_read_err(h, L, err)) || err) break;   // (a corrupt layout or an inactive fragment)
+        size_t tb = L.tmp_bytes;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp, tb, M->nsub, M->rank0, n, s));
+        k_mp_rank<<<blocks_for(n, 256), 256, 0, s>>>(n, S, bin, M->fr, M->nsub, M->rank0, h->d_sub_ids, M->pix, M->A, M->A2, L.err);
         STEP_CK(hipGetLastError());
-        STEP_CK(hipMemcpyAsync(&err, M->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (err) break;   // (a corrupt layout or an inactive fragment: the slots are not to be trusted, nothing reads them)
-        tb = M->tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(M->tmp, tb, M->nsub, M->rank0, n, s));
-        k_mp_rank<<<blocks_for(n, 256), 256, 0, s>>>(n, S, bin, M->fr, M->nsub, M->rank0, h->d_sub_ids, M->pix, M->A, M->A2, M->err);
-        STEP_CK(hipGetLastError());
-        STEP_CK(hipMemcpyAsync(&err, M->err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (err) break;   // (the ranks do not cover the sub-fragments: no pixel is to be trusted)
+        if ((rc = slots_read_err(h, L, err)) || err) break;   // (the ranks do not cover the sub-fragments: no pixel is to be trusted)
         if (h->nnz > 0) {
-            const long long waves = (h->nnz + 63) / 64;
-            const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
-            k_mp_obs<<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, M->pix, m, M->O);
+            k_mp_obs<<<stream_blocks(h->nnz), 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, M->pix, m, M->O);
             STEP_CK(hipGetLastError());
         }
         const int lc = std::min(std::max(std::max(h->max_lcont, h->lcont_bound), 1), n);
         const int n_tiles = (n + 63) / 64;
-        const int Sw = std::min(16, std::max(1, ((lc + 63) / 64 + 7) / 8));
+        const int Sw = mass_stripes(lc);
         k_mp_cis<<<(n_tiles * Sw + 3) / 4, 256, 0, s>>>(n, M->fr, M->rank0, M->lbp, h->nfpb, h->par, reach_bp(h), Sw, bin, m, M->E, M->badmap);
         STEP_CK(hipGetLastError());
         const double v = h->par.v_inter < 0.0f ? 0.0 : (double)h->par.v_inter;   // (a negative expected value counts as 0)

@@ -1,7 +1,8 @@
 // rings.h -- the likelihood closing each linear contig into a ring, or opening each ring at its wrap, would add, for every contig in one
 // pass (graal_ring_scores); and the commit that closes contigs (graal_close_rings).
-// Included by graal_hip.hip after junctions.h (it uses Ctx, Stat, centre_kb, rippe, to_q, WAVE_LDS_SYNC, model_math.h, score_common.h's
-// score_entry, score_exit, STEP_CK and free_null, and junctions.h's k_jn_count and jn_run_sum).
+// Included by graal_hip.hip after junctions.h (it uses Ctx, Stat, rippe, to_q, WAVE_LDS_SYNC, model_math.h, score_common.h's score_entry,
+// layout_refusal, score_exit, STEP_CK, free_null, stream_blocks, mass_stripes and layout_replaced, layout_slots.h's LayoutSlots and
+// slot_claim, and junctions.h's jn_load and jn_run_sum).
 //
 // R[c] = logL(layout with contig c in the OTHER topology, every coordinate kept) - logL(layout), in the engine's exact arithmetic.  Nothing
 // moves, so only the price of c's own pairs changes, and only where the two topologies are priced apart: rippe_circ (graal_hip.hip)
@@ -16,8 +17,8 @@
 // GRAAL_MODE_REF_TRANS_ACCU does not enter: it re-indexes trans prices only, and a cis pair beyond the window is v_inter * the plain norm
 // in both topologies.
 //
-// The slot numbering is built from the layout itself, as junctions.h builds it (k_jn_count -> exclusive scan -> k_rg_prep): the call does
-// not relabel and leaves the step state alone.  A contig is keyed by its LAST slot.  Kernels, all on the engine's stream:
+// The slot numbering is layout_slots.h's, built from the layout itself (slots_count -> k_rg_prep): the call does not relabel and leaves
+// the step state alone.  A contig is keyed by its LAST slot.  Kernels, all on the engine's stream:
 //   k_rg_prep -- a 48-byte record per slot and a 16-byte record per sub-fragment (both carry the contig's key and s_tot; rings are scored
 //                here, so the junction scorer's records, which mark rings out, do not serve); the longest contig of THIS layout, which
 //                sizes k_rg_mass's grid (the handle's own statistic is that of its last graal_begin_step);
@@ -44,22 +45,20 @@ struct RgPre { float K, k3, norm_circ; };
 
 struct RgBuf {
     int n = 0, S = 0;
-    int *cnt = nullptr, *base = nullptr, *slot = nullptr;
+    LayoutSlots L;                                              // (err[1]: the longest contig)
     RgFrag* fr = nullptr;
     RgSub* sub = nullptr;
     long long *sum = nullptr, *con = nullptr, *bad = nullptr;   // per slot, used at a contig's last slot (one allocation of 3n)
     long long *q = nullptr, *c = nullptr; unsigned char* st = nullptr;   // the results, fragment-indexed
-    void* tmp = nullptr; size_t tmp_bytes = 0;
-    unsigned* err = nullptr;                                    // [0] layout-error flags, [1] the longest contig
     int *mark = nullptr, *head = nullptr, *tail = nullptr, *d_frag = nullptr, *d_st = nullptr; int n_lab = 0, fcap = 0;   // graal_close_rings
 };
 
 void rg_free_score(RgBuf* b)
 {
-    free_null({(void**)&b->cnt, (void**)&b->base, (void**)&b->slot, (void**)&b->fr, (void**)&b->sub, (void**)&b->sum, (void**)&b->q, (void**)&b->c,
-               (void**)&b->st, &b->tmp, (void**)&b->err});
+    slots_free(b->L);
+    free_null({(void**)&b->fr, (void**)&b->sub, (void**)&b->sum, (void**)&b->q, (void**)&b->c, (void**)&b->st});
     b->con = b->bad = nullptr;
-    b->tmp_bytes = 0; b->n = 0; b->S = 0;
+    b->n = 0; b->S = 0;
 }
 
 void rg_free_close(RgBuf* b)
@@ -110,21 +109,17 @@ __global__ __launch_bounds__(256) void k_rg_prep(SoaPtr s, int n, const Stat* __
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
-    const int c = s.p[F_IDC][f], pos = s.p[F_POS][f];
-    if (c < 0 || c > n + 2 || pos < 0 || pos >= cnt[c]) { atomicOr(&err[0], 2u); slot_of[f] = -1; return; }
-    const int slot = base[c] + pos;
-    if (slot < 0 || slot >= n) { atomicOr(&err[0], 2u); slot_of[f] = -1; return; }
-    slot_of[f] = slot;
-    if (pos == 0) atomicMax(&err[1], (unsigned)cnt[c]);
-    const Stat st = stat[f];
-    const bool fwd = s.p[F_ORI][f] == 1, ring = s.p[F_CIRC][f] == 1;
-    const int start = s.p[F_START][f];
+    const int slot = slot_claim(s, n, f, cnt, base, slot_of, &err[0]);
+    if (slot < 0) return;
+    const int c = s.p[F_IDC][f];
+    if (s.p[F_POS][f] == 0) atomicMax(&err[1], (unsigned)cnt[c]);
+    const JnLoad x = jn_load(s, stat, f);
+    const Stat& st = x.st;
+    const bool ring = x.circ;
     RgFrag r;
-    r.start_bp = start; r.len_bp = s.p[F_LEN][f]; r.flags = (fwd ? 1 : 0) | (ring ? 2 : 0);
+    r.start_bp = x.start; r.len_bp = x.len; r.flags = (x.fwd ? 1 : 0) | (ring ? 2 : 0);
     r.n = st.n; r.a0 = st.a0; r.a1 = st.a1; r.a2 = st.a2;
-    r.c0 = st.n > 0 ? centre_kb(start, fwd, st, 0) : 0.0f;
-    r.c1 = st.n > 1 ? centre_kb(start, fwd, st, 1) : 0.0f;
-    r.c2 = st.n > 2 ? centre_kb(start, fwd, st, 2) : 0.0f;
+    r.c0 = x.c0; r.c1 = x.c1; r.c2 = x.c2;
     r.last = min(base[c] + cnt[c] - 1, n - 1);
     r.s_tot = (float)s.p[F_LCONTBP][f] / 1000.0f;
     fr[slot] = r;
@@ -323,68 +318,52 @@ int graal_ring_scores(graal_ctx* h, int64_t* q_out, int64_t* contacts_out, uint8
     RgBuf* R = h->rg;
     hipStream_t s = h->stream;
     if (R->n != n || R->S != S) {
-        rg_free_score(R);   // (R->n stays 0 until the whole set is allocated: free_null)
-        CK(hipMalloc(&R->cnt, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&R->base, sizeof(int) * (size_t)(n + 3)));
-        CK(hipMalloc(&R->slot, sizeof(int) * (size_t)n));
+        rg_free_score(R);
+        if (const int rc = slots_reserve(h, R->L)) return rc;
         CK(hipMalloc(&R->fr, sizeof(RgFrag) * (size_t)n));
         CK(hipMalloc(&R->sub, sizeof(RgSub) * (size_t)std::max(S, 1)));
         CK(hipMalloc(&R->sum, sizeof(long long) * 3 * (size_t)n));
         CK(hipMalloc(&R->q, sizeof(long long) * (size_t)n));
         CK(hipMalloc(&R->c, sizeof(long long) * (size_t)n));
         CK(hipMalloc(&R->st, (size_t)n));
-        CK(hipMalloc(&R->err, sizeof(unsigned) * 2));
-        size_t tb = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, R->cnt, R->base, n + 3, s));
-        CK(hipMalloc(&R->tmp, tb));
-        R->tmp_bytes = tb;
         R->n = n; R->S = S;
     }
     R->con = R->sum + n; R->bad = R->sum + 2 * (size_t)n;
+    LayoutSlots& L = R->L;
     const SoaPtr sp = h->soa[h->cur];
     int rc = GRAAL_OK;
-    unsigned err[2] = {0, 0};
+    unsigned err = 0, longest = 0;
     do {
-        STEP_CK(hipMemsetAsync(R->err, 0, sizeof(unsigned) * 2, s));
-        STEP_CK(hipMemsetAsync(R->cnt, 0, sizeof(int) * (size_t)(n + 3), s));
         STEP_CK(hipMemsetAsync(R->sum, 0, sizeof(long long) * 3 * (size_t)n, s));
         STEP_CK(hipMemsetAsync(R->fr, 0, sizeof(RgFrag) * (size_t)n, s));   // (a slot no fragment claims -- a corrupt layout -- reads as empty)
-        k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, R->cnt, R->err);
+        if ((rc = slots_count(h, L))) break;
+        k_rg_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, h->stat_frag, h->d_sub_ids, L.cnt, L.base, L.slot, R->fr, R->sub, L.err);
         STEP_CK(hipGetLastError());
-        size_t tb = R->tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(R->tmp, tb, R->cnt, R->base, n + 3, s));
-        k_rg_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, h->stat_frag, h->d_sub_ids, R->cnt, R->base, R->slot, R->fr, R->sub, R->err);
-        STEP_CK(hipGetLastError());
-        STEP_CK(hipMemcpyAsync(err, R->err, sizeof err, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (err[0]) break;   // (a corrupt layout: the slots are not to be trusted, nothing reads them)
+        if ((rc = slots_read_err(h, L, err, &longest)) || err) break;
         if (h->nnz > 0) {
-            const long long waves = (h->nnz + 63) / 64;
-            const int nb = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
-            k_rg_nnz<<<nb, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R->sub, h->nfpb, h->par, R->sum, R->con, R->bad);
+            k_rg_nnz<<<stream_blocks(h->nnz), 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, R->sub, h->nfpb, h->par, R->sum, R->con, R->bad);
             STEP_CK(hipGetLastError());
         }
-        const int lc = std::min(std::max((int)err[1], 1), n);        // the longest contig of the layout scored
+        const int lc = std::min(std::max((int)longest, 1), n);       // the longest contig of the layout scored
         const int n_tiles = (n + 63) / 64;
-        const int Sw = std::min(16, std::max(1, ((lc + 63) / 64 + 7) / 8));
+        const int Sw = mass_stripes(lc);
         k_rg_mass<<<(n_tiles * Sw + 3) / 4, 256, 0, s>>>(n, R->fr, h->nfpb, h->par, reach_bp(h), Sw, R->sum, R->bad);
         STEP_CK(hipGetLastError());
-        k_rg_out<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, R->cnt, R->slot, R->fr, R->sum, R->con, R->bad, R->q, R->c, R->st);
+        k_rg_out<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, L.cnt, L.slot, R->fr, R->sum, R->con, R->bad, R->q, R->c, R->st);
         STEP_CK(hipGetLastError());
         STEP_CK(hipMemcpyAsync(q_out, R->q, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, s));
         STEP_CK(hipMemcpyAsync(contacts_out, R->c, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, s));
         STEP_CK(hipMemcpyAsync(status, R->st, (size_t)n, hipMemcpyDeviceToHost, s));
         STEP_CK(hipStreamSynchronize(s));
     } while (false);
-    return score_exit(h, "graal_ring_scores", rc, nullptr, err[0]);
+    return score_exit(h, "graal_ring_scores", rc, nullptr, err);
 }
 
 int graal_close_rings(graal_ctx* h, int32_t n_rings, const int32_t* frag, int32_t* status)
 {
     if (!h || n_rings < 0 || (n_rings > 0 && (!frag || !status))) return GRAAL_E_ARG;
-    if (!h->have_frags) return fail(h, GRAAL_E_STATE, "graal_close_rings: upload the fragments first");
-    if (h->has_rep) return fail(h, GRAAL_E_UNSUPPORTED, "graal_close_rings: bins with several copies (graal_upload_repeats) are not supported");
-    if (h->x_host || h->nccl_comm) return fail(h, GRAAL_E_STATE, "graal_close_rings: one rank only (an exchange or RCCL is attached)");
+    // (the scorers' refusals, but for what must be uploaded: the commit needs neither contacts nor parameters)
+    if (const int rc = layout_refusal(h, "graal_close_rings", h->have_frags ? nullptr : "upload the fragments first")) return rc;
     for (int i = 0; i < n_rings; i++) status[i] = GRAAL_RINGEDIT_OK;
     if (n_rings == 0) return GRAAL_OK;
     CK(hipSetDevice(h->device));
@@ -421,16 +400,7 @@ int graal_close_rings(graal_ctx* h, int32_t n_rings, const int32_t* frag, int32_
     if (bad_layout) return fail(h, GRAAL_E_STATE, "graal_close_rings: corrupt layout (contig labels, positions or lengths do not agree)");
     for (size_t i = 0; i < hst.size(); i++)
         if (hst[i] != GRAAL_RINGEDIT_OK) return fail(h, GRAAL_E_ARG, "graal_close_rings: a contig cannot be closed (see status)");
-    // ---- the result ends in buffer 0 and the engine in graal_edit_layout's state (the stat_frag table is unchanged)
-    if (h->cur != 0) CK(hipMemcpyAsync(h->soa_mem[0], h->soa_mem[h->cur], sizeof(int) * (size_t)n * GRAAL_N_FIELDS, hipMemcpyDeviceToDevice, s));
-    CK(hipStreamSynchronize(s));
-    h->cur = 0; h->ranks_valid = false; h->pending_commits = 0; h->begin_launched = false; h->stats_from_apply = false;
-    h->order_valid = false;
-    h->carry_q = 0; h->carry_bad = true;
-    int rc = refresh(h);
-    if (rc) return rc;
-    CK(hipStreamSynchronize(s));
-    return sync_args(h);
+    return layout_replaced(h, h->cur);   // (written in place, in the current buffer)
 }
 
 } // extern "C"

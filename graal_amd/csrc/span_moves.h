@@ -1,7 +1,8 @@
 // span_moves.h -- the likelihood each move of a span of fragments would add, for a caller's set of disjoint spans in one pass: in-place
-// reversals (graal_block_flips) and swaps of two adjacent runs (graal_block_swaps).  Included by graal_hip.hip after links.h (it uses
-// LayoutRecs with recs_reserve / recs_build, the records LnFrag / LnCtg, ln_run_sum, ln_block_add, ln_mirror_q, span_check.h and
-// score_common.h's score_entry, score_exit, STEP_CK and free_null).
+// reversals (graal_block_flips) and swaps of two adjacent runs (graal_block_swaps); and the frame of every call that scores spans
+// (span_moves: these two and excise.h's graal_block_excisions).  Included by graal_hip.hip after insert.h (it uses LayoutRecs with
+// recs_reserve / recs_build, slots_read_err, the records LnFrag / LnCtg, ln_run_sum, ln_block_add, ln_mirror_q, span_check.h and
+// score_common.h's score_entry, score_exit, STEP_CK, free_null and stream_blocks).
 //
 // Span k = the fragments of one linear contig at slots first .. last, bp interval [s0, e1).  The breakpoint sm behind slot mid splits it
 // into the runs X = first .. mid and Y = mid + 1 .. last (lx = sm - s0, ly = e1 - sm).  The moved layout puts Y in front of X:
@@ -55,13 +56,15 @@ namespace {
 
 // acc: RF count | the bin's last RF count << 16; meta: fwd | mixed << 1 | reversed by the move << 2 | in Y << 3
 struct SpanSub { float c_old, c_new; int label, span, frag, acc, meta, pad; };
-static_assert(sizeof(SpanSub) == 32, "a sub-fragment's record is two 16-byte loads");
+constexpr size_t SPAN_SUB_BYTES = 32;                                 // of every kind's record: they share SpanBuf's allocation, sized by S
+static_assert(sizeof(SpanSub) == SPAN_SUB_BYTES, "a sub-fragment's record is two 16-byte loads");
 
+// One set per handle for the three calls: each call rebuilds what it reads.
 struct SpanBuf {
     LayoutRecs R;
-    SpanSub* sub = nullptr; int n = 0, S = 0;                         // per sub-fragment
+    void* sub = nullptr; int n = 0, S = 0;                            // per sub-fragment: a SpanSub, or excise.h's ExSub (32 bytes each)
     int *first = nullptr, *mid = nullptr, *last = nullptr; SpanInfo* info = nullptr; SpanRec* rec = nullptr;
-    long long *qb = nullptr, *cb = nullptr, *q = nullptr, *c = nullptr; int *bad = nullptr, *ne = nullptr, *noff = nullptr; int4* nx = nullptr;
+    long long *qb = nullptr, *cb = nullptr, *q = nullptr, *c = nullptr, *ne = nullptr, *noff = nullptr; int* bad = nullptr; int4* nx = nullptr;
     unsigned char* st = nullptr;
     void* tmp = nullptr; size_t tmp_bytes = 0;
     size_t bcap = 0;                                                  // spans the per-span arrays hold
@@ -76,7 +79,7 @@ void sp_free_spans(SpanBuf* b)
 
 void sp_free_subs(SpanBuf* b)
 {
-    free_null({(void**)&b->sub});
+    free_null({&b->sub});
     b->n = 0; b->S = 0;
 }
 
@@ -107,14 +110,16 @@ __global__ void k_sp_gather(int nb, int n, const int* __restrict__ first, const 
     info[k] = r;
 }
 
-// the scored span that holds `slot`, or -1: the last span that starts at or before it, if it reaches that far
-__device__ __forceinline__ int sp_span_of(const SpanRec* __restrict__ rec, int m, int slot)
+// the scored span that holds `slot`, or -1: the last span that starts at or before it, if it reaches that far.  ub: the number of
+// scored spans that start at or before the slot
+__device__ __forceinline__ int sp_span_of(const SpanRec* __restrict__ rec, int m, int slot, int* ub = nullptr)
 {
     int lo = 0, hi = m;                                              // first span with .first > slot
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
         if (rec[mid].first <= slot) lo = mid + 1; else hi = mid;
     }
+    if (ub) *ub = lo;
     return (lo > 0 && slot <= rec[lo - 1].last) ? lo - 1 : -1;
 }
 
@@ -251,7 +256,8 @@ __device__ __forceinline__ int2 sp_run_edges(const LnFrag* __restrict__ fr, int 
 }
 
 // per span: the units of X and of Y (nx = units of X, of them from the left, units of Y, of them from the left); ne = their sum
-__global__ void k_sp_edges(int m, const SpanRec* __restrict__ rec, const LnFrag* __restrict__ fr, int reach_bp, int* __restrict__ ne, int4* __restrict__ nx)
+__global__ void k_sp_edges(int m, const SpanRec* __restrict__ rec, const LnFrag* __restrict__ fr, int reach_bp, long long* __restrict__ ne,
+                           int4* __restrict__ nx)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j > m) return;
@@ -281,8 +287,8 @@ __device__ __forceinline__ long long sp_pair_q(const LnFrag& x, float xo0, float
     return to_q_fast(acc);
 }
 
-// the unit's span: the last j with noff[j] <= W (every span has at least one unit)
-__device__ __forceinline__ int sp_span_of_unit(const int* __restrict__ noff, int m, int W)
+// the unit's span: the last j with noff[j] <= W (every scored span has at least one unit: a fragment of X)
+__device__ __forceinline__ int sp_span_of_unit(const long long* __restrict__ noff, int m, long long W)
 {
     int lo = 0, hi = m - 1;
     while (lo < hi) {
@@ -324,15 +330,16 @@ __device__ __forceinline__ void sp_walk(const LnFrag* __restrict__ fr, int from,
     }
 }
 
-__global__ __launch_bounds__(256) void k_sp_mass(int total, int m, int rev, const SpanRec* __restrict__ rec, const int* __restrict__ noff,
-                                                 const int* __restrict__ ne, const int4* __restrict__ nx, const LnFrag* __restrict__ fr, float nfpb,
-                                                 Par par, int reach_bp, long long* __restrict__ qb, int* __restrict__ badb)
+__global__ __launch_bounds__(256) void k_sp_mass(long long total, int m, int rev, const SpanRec* __restrict__ rec,
+                                                 const long long* __restrict__ noff, const long long* __restrict__ ne,
+                                                 const int4* __restrict__ nx, const LnFrag* __restrict__ fr, float nfpb, Par par, int reach_bp,
+                                                 long long* __restrict__ qb, int* __restrict__ badb)
 {
-    const int W = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const long long W = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (W >= total) return;                                          // (wave-uniform)
     const int j = sp_span_of_unit(noff, m, W);
-    int u = W - noff[j];
-    if (u < 0 || u >= ne[j]) return;
+    if (W - noff[j] < 0 || W - noff[j] >= ne[j]) return;
+    int u = (int)(W - noff[j]);                                      // (< the span's fragments)
     const SpanRec b = rec[j];
     const int4 e = nx[j];
     const bool in_y = u >= e.x;
@@ -404,9 +411,58 @@ __global__ void k_sp_out(int m, const SpanRec* __restrict__ rec, const long long
     c[id] = cb[j];
 }
 
-// The frame of both calls.  mid: null for a kind without one.
+// The units' total behind a kind's edges kernel: the exclusive scan of ne over m + 1 entries, read back (a host wait).
+int sp_unit_total(graal_ctx* h, SpanBuf* B, int m, long long& total)
+{
+    hipStream_t s = h->stream;
+    int rc = GRAAL_OK;
+    do {
+        size_t tb = B->tmp_bytes;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(B->tmp, tb, B->ne, B->noff, m + 1, s));
+        STEP_CK(hipMemcpyAsync(&total, B->noff + m, sizeof(long long), hipMemcpyDeviceToHost, s));
+        STEP_CK(hipStreamSynchronize(s));
+    } while (false);
+    return rc;
+}
+
+// The kernels of a flip or a swap: what span_moves runs between the upload of the m scored spans and k_sp_out.
+int sp_score(graal_ctx* h, const SpanKind& K, SpanBuf* B, const std::vector<SpanRec>& rec, std::string&)
+{
+    const int n = h->n, m = (int)rec.size();
+    const LayoutRecs& R = B->R;
+    SpanSub* const sub = (SpanSub*)B->sub;
+    hipStream_t s = h->stream;
+    const int mirror = (K.rev && (h->mode & GRAAL_MODE_REF_TRANS_ACCU)) ? 1 : 0;
+    int rc = GRAAL_OK;
+    do {
+        k_sp_sub<<<blocks_for(n, 256), 256, 0, s>>>(n, m, K.rev, B->rec, R.L.slot, R.lab, R.fr, h->d_sub_ids, sub);
+        STEP_CK(hipGetLastError());
+        if (h->nnz > 0) {
+            k_sp_nnz<<<stream_blocks(h->nnz), 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, sub, h->nfpb, h->par, mirror, B->qb, B->cb, B->bad);
+            STEP_CK(hipGetLastError());
+        }
+        k_sp_edges<<<blocks_for(m + 1, 256), 256, 0, s>>>(m, B->rec, R.fr, reach_bp(h), B->ne, B->nx);
+        STEP_CK(hipGetLastError());
+        long long total = 0;                                          // (<= n: a fragment belongs to at most one span)
+        if ((rc = sp_unit_total(h, B, m, total))) break;
+        if (total > 0) {
+            k_sp_mass<<<blocks_for(total, 4), 256, 0, s>>>(total, m, K.rev, B->rec, B->noff, B->ne, B->nx, R.fr, h->nfpb, h->par, reach_bp(h), B->qb, B->bad);
+            STEP_CK(hipGetLastError());
+        }
+        if (mirror && h->n_ubins) {
+            k_sp_mirror<<<h->n_ubins, 256, 0, s>>>(n, m, B->rec, h->d_ubins, R.L.slot, R.lab, R.fr, h->nfpb, h->par, B->qb, B->bad);
+            STEP_CK(hipGetLastError());
+        }
+    } while (false);
+    return rc;
+}
+
+// The frame of the three calls.  mid: null for a kind without one.  kernels: the kind's kernels over the scored spans
+// `rec` (at least one; uploaded to B->rec, the sums qb / cb / bad cleared), which leave the sums for k_sp_out; it returns a scorer's rc
+// and may set `unsupported`, the text of a call it cannot serve.  kernels(h, K, B, rec, unsupported).
+template <class Kernels>
 int span_moves(graal_ctx* h, const SpanKind& K, int nb, const int32_t* first, const int32_t* mid, const int32_t* last, int64_t* q,
-               int64_t* contacts, uint8_t* status)
+               int64_t* contacts, uint8_t* status, Kernels kernels)
 {
     if (const int rc = score_entry(h, K.fn)) return rc;
     if (nb == 0) return GRAAL_OK;
@@ -423,16 +479,16 @@ int span_moves(graal_ctx* h, const SpanKind& K, int nb, const int32_t* first, co
     LayoutRecs& R = B->R;
     hipStream_t s = h->stream;
     if (const int rc = recs_reserve(h, R)) return rc;
-    if (B->n != n || B->S != S) {                                     // (B->n stays 0 until the set is allocated)
+    if (B->n != n || B->S != S) {
         sp_free_subs(B);
-        CK(hipMalloc(&B->sub, sizeof(SpanSub) * (size_t)std::max(S, 1)));
+        CK(hipMalloc(&B->sub, SPAN_SUB_BYTES * (size_t)std::max(S, 1)));
         B->n = n; B->S = S;
     }
-    if ((size_t)nb > B->bcap) {                                       // (grows to the largest call; bcap stays 0 until the set is allocated)
+    if ((size_t)nb > B->bcap) {                                       // (grows to the largest call of any kind)
         sp_free_spans(B);
         const size_t cap = (size_t)nb + 1;
-        for (int** p : {&B->first, &B->mid, &B->last, &B->bad, &B->ne, &B->noff}) CK(hipMalloc(p, sizeof(int) * cap));
-        for (long long** p : {&B->qb, &B->cb, &B->q, &B->c}) CK(hipMalloc(p, sizeof(long long) * cap));
+        for (int** p : {&B->first, &B->mid, &B->last, &B->bad}) CK(hipMalloc(p, sizeof(int) * cap));
+        for (long long** p : {&B->qb, &B->cb, &B->q, &B->c, &B->ne, &B->noff}) CK(hipMalloc(p, sizeof(long long) * cap));
         CK(hipMalloc(&B->info, sizeof(SpanInfo) * cap));
         CK(hipMalloc(&B->rec, sizeof(SpanRec) * cap));
         CK(hipMalloc(&B->nx, sizeof(int4) * cap));
@@ -443,22 +499,20 @@ int span_moves(graal_ctx* h, const SpanKind& K, int nb, const int32_t* first, co
         B->tmp_bytes = tb;
         B->bcap = (size_t)nb;
     }
-    const int mirror = (K.rev && (h->mode & GRAAL_MODE_REF_TRANS_ACCU)) ? 1 : 0;
     int rc = GRAAL_OK;
     unsigned err = 0;
     bool refused = false;
+    std::string unsupported;
     std::vector<SpanInfo> info((size_t)nb);
     do {
         if ((rc = recs_build(h, R, 1))) break;
         STEP_CK(hipMemcpyAsync(B->first, first, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
         if (mid) STEP_CK(hipMemcpyAsync(B->mid, mid, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
         STEP_CK(hipMemcpyAsync(B->last, last, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
-        k_sp_gather<<<blocks_for(nb, 256), 256, 0, s>>>(nb, n, B->first, mid ? B->mid : nullptr, B->last, R.slot, R.lab, R.fr, R.ctg, B->info);
+        k_sp_gather<<<blocks_for(nb, 256), 256, 0, s>>>(nb, n, B->first, mid ? B->mid : nullptr, B->last, R.L.slot, R.lab, R.fr, R.ctg, B->info);
         STEP_CK(hipGetLastError());
-        STEP_CK(hipMemcpyAsync(&err, R.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
         STEP_CK(hipMemcpyAsync(info.data(), B->info, sizeof(SpanInfo) * (size_t)nb, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
-        if (err) break;   // (a corrupt layout: the slots are not to be trusted, nothing reads them)
+        if ((rc = slots_read_err(h, R.L, err)) || err) break;
         const SpanChecked C = span_check(info.data(), nb, K);
         if (C.off >= 0) {
             span_reason_text(K, C.why, why, sizeof why);
@@ -476,29 +530,7 @@ int span_moves(graal_ctx* h, const SpanKind& K, int nb, const int32_t* first, co
             STEP_CK(hipMemsetAsync(B->qb, 0, sizeof(long long) * (size_t)m, s));
             STEP_CK(hipMemsetAsync(B->cb, 0, sizeof(long long) * (size_t)m, s));
             STEP_CK(hipMemsetAsync(B->bad, 0, sizeof(int) * (size_t)m, s));
-            k_sp_sub<<<blocks_for(n, 256), 256, 0, s>>>(n, m, K.rev, B->rec, R.slot, R.lab, R.fr, h->d_sub_ids, B->sub);
-            STEP_CK(hipGetLastError());
-            if (h->nnz > 0) {
-                const long long waves = (h->nnz + 63) / 64;
-                const int g = (int)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 2048));
-                k_sp_nnz<<<g, 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, B->sub, h->nfpb, h->par, mirror, B->qb, B->cb, B->bad);
-                STEP_CK(hipGetLastError());
-            }
-            k_sp_edges<<<blocks_for(m + 1, 256), 256, 0, s>>>(m, B->rec, R.fr, reach_bp(h), B->ne, B->nx);
-            STEP_CK(hipGetLastError());
-            size_t tb = B->tmp_bytes;
-            STEP_CK(hipcub::DeviceScan::ExclusiveSum(B->tmp, tb, B->ne, B->noff, m + 1, s));
-            int total = 0;                                            // (<= n: a fragment belongs to at most one span)
-            STEP_CK(hipMemcpyAsync(&total, B->noff + m, sizeof(int), hipMemcpyDeviceToHost, s));
-            STEP_CK(hipStreamSynchronize(s));
-            if (total > 0) {
-                k_sp_mass<<<blocks_for(total, 4), 256, 0, s>>>(total, m, K.rev, B->rec, B->noff, B->ne, B->nx, R.fr, h->nfpb, h->par, reach_bp(h), B->qb, B->bad);
-                STEP_CK(hipGetLastError());
-            }
-            if (mirror && h->n_ubins) {
-                k_sp_mirror<<<h->n_ubins, 256, 0, s>>>(n, m, B->rec, h->d_ubins, R.slot, R.lab, R.fr, h->nfpb, h->par, B->qb, B->bad);
-                STEP_CK(hipGetLastError());
-            }
+            if ((rc = kernels(h, K, B, C.rec, unsupported)) || !unsupported.empty()) break;
             k_sp_out<<<blocks_for(m, 256), 256, 0, s>>>(m, B->rec, B->qb, B->cb, B->bad, K.valid, K.nonfinite, B->q, B->c, B->st);
             STEP_CK(hipGetLastError());
         }
@@ -508,7 +540,7 @@ int span_moves(graal_ctx* h, const SpanKind& K, int nb, const int32_t* first, co
         STEP_CK(hipStreamSynchronize(s));
     } while (false);
     if (refused) return fail(h, GRAAL_E_ARG, msg);
-    return score_exit(h, K.fn, rc, nullptr, err);
+    return score_exit(h, K.fn, rc, unsupported.empty() ? nullptr : unsupported.c_str(), err);
 }
 
 } // namespace
@@ -520,7 +552,7 @@ int graal_block_flips(graal_ctx* h, int32_t n_blocks, const int32_t* first, cons
     if (!h) return GRAAL_E_ARG;
     if (n_blocks < 0 || (n_blocks > 0 && (!first || !last || !q || !contacts || !status)))
         return fail(h, GRAAL_E_ARG, "graal_block_flips: n_blocks < 0 or a null array");
-    return span_moves(h, SPAN_FLIPS, n_blocks, first, nullptr, last, q, contacts, status);
+    return span_moves(h, SPAN_FLIPS, n_blocks, first, nullptr, last, q, contacts, status, sp_score);
 }
 
 int graal_block_swaps(graal_ctx* h, int32_t n_swaps, const int32_t* first, const int32_t* mid, const int32_t* last, int64_t* q, int64_t* contacts,
@@ -529,7 +561,7 @@ int graal_block_swaps(graal_ctx* h, int32_t n_swaps, const int32_t* first, const
     if (!h) return GRAAL_E_ARG;
     if (n_swaps < 0 || (n_swaps > 0 && (!first || !mid || !last || !q || !contacts || !status)))
         return fail(h, GRAAL_E_ARG, "graal_block_swaps: n_swaps < 0 or a null array");
-    return span_moves(h, SPAN_SWAPS, n_swaps, first, mid, last, q, contacts, status);
+    return span_moves(h, SPAN_SWAPS, n_swaps, first, mid, last, q, contacts, status, sp_score);
 }
 
 } // extern "C"

@@ -1,8 +1,11 @@
-"""The whole-layout scorers (graal_junction_scores, graal_end_links, graal_end_links_best, graal_insertions) keep their buffers on the
-handle between calls: the layout records are reallocated when (n, S) changes, the candidate table and the hipCUB scratch grow to the
-largest size a call needed and are then used at a smaller size than their allocation.  Every call on a handle that served other calls
+"""The whole-layout scorers (graal_junction_scores, graal_ring_scores, graal_layout_maps, graal_end_links, graal_end_links_best,
+graal_insertions) keep their buffers on the handle between calls: the slots and the layout records (one set per family, each built on
+layout_slots.h's LayoutSlots) are reallocated when (n, S) changes, the candidate table, the maps' image buffers and the hipCUB scratch
+grow to the largest size a call needed and are then used at a smaller size than their allocation.  Every call on a handle that served other calls
 must return exactly what the same call returns as the FIRST call on a fresh handle with the same uploads.  Nothing here is compared with
-stored numbers: the other GPU tests tie the fresh-handle results to the numpy restatements.
+stored numbers: the other GPU tests tie the fresh-handle results to the numpy restatements; here the restatements only show, before any
+launch, that the ring scores are not all zero (at least 10 contigs with a non-zero score in the cut layouts, all 3 in the uncut ones),
+and the first maps call must see contacts (a non-zero observed image), so that a buffer left all zero cannot pass.
 
 Problem A is window_cases.small_cut("w3") under ref_trans_accu: 160 bins at n_sub 3 with mixed RF counts (the mirror sums, both quirk
 kernels and the insertions' second table are live), pieces of 1-4 and 25-60 bins.  Problem B is small_cut("w1"): 240 fragments at n_sub
@@ -12,6 +15,7 @@ accepted), so the records are reallocated for another (n, S)."""
 import numpy as np
 import pytest
 
+from tests import ring_reference as RR
 from tests import window_cases
 from tests.test_scaffold_gpu import engine_for
 
@@ -26,10 +30,15 @@ CALLS = {
     "ins1": lambda e: e.insertions_q(1),
     "ins4": lambda e: e.insertions_q(4),
     "junctions": lambda e: e.junction_scores_q(),
+    "rings": lambda e: e.ring_scores_q(),
+    "maps64": lambda e: e.layout_maps(64)[:4],        # (the three images and pixel_of_sub)
+    "maps4096": lambda e: e.layout_maps(4096)[:4],
 }
-# links1 after links3: the table grows; links3 after it: the allocation is larger than the `cap` in use
-SEQUENCE = ("links3", "best1", "links1", "links3", "ins4", "ins1", "junctions", "best3")
-UNCUT = ("links1", "best1", "ins4")
+# links1 after links3: the table grows; links3 after it: the allocation is larger than the `cap` in use.  maps4096 after maps64: the image
+# buffers grow; maps64 after it: they are used small.  rings and the maps each follow a call of another family
+SEQUENCE = ("links3", "maps64", "best1", "rings", "links1", "maps4096", "links3", "ins4", "maps64", "ins1", "junctions", "rings", "best3",
+            "maps4096")
+UNCUT = ("links1", "rings", "best1", "maps64", "ins4", "maps4096", "junctions", "rings")
 
 _PROBLEMS, _FRESH = {}, {}
 
@@ -67,9 +76,27 @@ def check(e, name, layout, call, step):
         assert g.dtype == w.dtype and np.array_equal(g, w), (name, layout, call, step, i)
 
 
+def assert_rings_and_maps_score(name, layout):
+    """Rings, on the CPU: enough contigs with a non-zero score.  Maps: the fresh handle's observed images are not empty."""
+    P, uncut = problem(name)
+    state = uncut if layout == "uncut" else P["S_o_A_frags"]
+    R = RR.ring_scores_windowed(P, state=state)[0]
+    idc = np.asarray(state["id_c"])
+    scoring, contigs = len(set(idc[R != 0].tolist())), len(set(idc.tolist()))
+    if layout == "cut":
+        assert scoring >= 10, (name, layout, scoring)
+    else:
+        assert scoring == contigs == 3, (name, layout, scoring, contigs)
+    for call in ("maps64", "maps4096"):
+        assert fresh(name, layout, call)[0].astype(np.float64).sum() != 0, (name, layout, call)
+    assert fresh(name, layout, "maps4096")[0].size > fresh(name, layout, "maps64")[0].size
+
+
 @pytest.mark.parametrize("name", ["w3", "w1"])
 def test_reused_handle_equals_fresh_handle(name):
     P, uncut = problem(name)
+    assert_rings_and_maps_score(name, "cut")
+    assert_rings_and_maps_score(name, "uncut")
     assert len(fresh(name, "cut", "links1")[0]) > len(fresh(name, "cut", "links3")[0]) > len(fresh(name, "uncut", "links1")[0]) > 0
     assert len(fresh(name, "cut", "ins4")[0]) > len(fresh(name, "cut", "ins1")[0]) > 0
     e = engine_for(P, quirk=QUIRK[name])
@@ -87,9 +114,13 @@ def test_another_problem_on_a_used_handle():
     A, _ = problem("w3")
     B, _ = problem("w1")
     assert len(A["S_o_A_frags"]["pos"]) != len(B["S_o_A_frags"]["pos"])
+    first = ("links1", "maps4096", "best1", "rings", "ins4", "junctions")
+    second = ("rings", "links1", "maps64", "best1", "ins4", "maps4096", "junctions", "rings", "links3", "maps64")
+    assert_rings_and_maps_score("w3", "cut")
+    assert_rings_and_maps_score("w1", "cut")
     e = engine_for(A, quirk=True)
     try:
-        for step, call in enumerate(("links1", "best1", "ins4", "junctions")):
+        for step, call in enumerate(first):
             check(e, "w3", "cut", call, step)
         e.upload_subfrags(B["np_sub_frags_id"], B["np_sub_frags_len_bp"], B["np_sub_frags_accu"], B["init_n_sub_frags"],
                           B["mean_squared_frags_per_bin"])
@@ -97,7 +128,7 @@ def test_another_problem_on_a_used_handle():
         e.set_params(B["param_simu"])
         e.upload_frags(B["S_o_A_frags"])
         e.set_mode(ref_trans_accu=False)
-        for step, call in enumerate(("links1", "best1", "ins4", "junctions", "links3")):
-            check(e, "w1", "cut", call, 4 + step)
+        for step, call in enumerate(second):
+            check(e, "w1", "cut", call, len(first) + step)
     finally:
         e.close()

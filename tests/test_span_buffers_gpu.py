@@ -1,20 +1,23 @@
-"""graal_block_flips and graal_block_swaps share one set of buffers on the handle (span_moves.h): the layout records and the
-sub-fragment records are reallocated when (n, S) changes, the per-span arrays and the hipCUB scratch grow to the largest call of either
-and are then used at a smaller size than their allocation, by either call.  Every call on a handle that served other calls must return
+"""graal_block_flips, graal_block_swaps and graal_block_excisions share one set of buffers on the handle (span_moves.h): the layout
+records and the 32-byte sub-fragment records (one allocation, written by each call in its own format) are reallocated when (n, S)
+changes, the per-span arrays and the hipCUB scratch grow to the largest call of any of them and are then used at a smaller size than
+their allocation, by any of them.  Every call on a handle that served other calls must return
 exactly what the same call returns as the FIRST call on a fresh handle with the same uploads.  Nothing here is compared with stored
 numbers: the other GPU tests tie the fresh-handle results to the restatements; here the restatements only show, before any launch, that
 every call used has at least 10 valid spans with a non-zero q, so that a buffer left all zero cannot pass.
 
 The problems are test_score_buffers_gpu's: window_cases.small_cut("w3") under ref_trans_accu (160 bins at n_sub 3 with mixed RF counts:
 the flips' mirror pass is live) and small_cut("w1") (240 fragments at n_sub 1, the quirk off), each also in its uncut layout.  The calls:
-the largest and the smallest set of flips.tilings(s, None, 3) and of swaps.tilings(s, None, 3).  At n_sub 1 a flip of one fragment moves
+the largest and the smallest set of flips.tilings(s, None, 3), of swaps.tilings(s, None, 3) and of excise.tilings(s, None, 3) (every
+span of both excision sets scores).  At n_sub 1 a flip of one fragment moves
 no centre, so problem w1's largest set of flips (every fragment alone) has q = 0 throughout: there "flips_big" is the largest set
 that scores, and "flips_all" adds the largest set itself, which is the call the arrays grow to, held to at least 10 valid spans with
 contacts in the window instead."""
 import numpy as np
 import pytest
 
-from graal_amd import flips, swaps
+from graal_amd import excise, flips, swaps
+from tests import excise_reference as XR
 from tests import flip_reference as FR
 from tests import swap_reference as SR
 from tests.test_scaffold_gpu import engine_for
@@ -22,10 +25,13 @@ from tests.test_score_buffers_gpu import QUIRK, flat, problem
 
 pytestmark = pytest.mark.gpu
 
-# the largest set, the smallest, the largest again, for both moves: the arrays grow with the first call, then serve both calls at
-# smaller and at their full size
-SEQUENCE = ("flips_big", "swaps_big", "flips_small", "swaps_small", "flips_all", "flips_big", "swaps_big")
-UNCUT = ("swaps_small", "flips_big", "swaps_big", "flips_small", "flips_all")
+# the largest set, the smallest, the largest again, for the three calls: the arrays grow with the first calls, then serve every call at
+# smaller and at their full size.  An excision follows a swap and a flip follows an excision at every stage: after the arrays grew, at a
+# smaller size, and (UNCUT, and the second test's lists) in another layout and after a change of (n, S)
+SEQUENCE = ("flips_big", "swaps_big", "excise_big", "flips_small", "swaps_small", "excise_small", "flips_all", "flips_big", "swaps_big",
+            "excise_big", "flips_big")
+UNCUT = ("swaps_small", "excise_big", "flips_big", "swaps_big", "excise_small", "flips_small", "flips_all")
+MOVES = {"flips": (flips, FR, "flips"), "swaps": (swaps, SR, "swaps"), "excise": (excise, XR, "excisions")}
 
 _SETS, _FRESH = {}, {}
 
@@ -38,8 +44,8 @@ def layout(name, which):
 def scoring(name, which, move, frags):
     """On the CPU: how many of the spans are valid with q != 0, and how many valid with contacts != 0."""
     P, _ = problem(name)
-    W = (FR if move == "flips" else SR).window(P, quirk=QUIRK[name])
-    q, c, st, _ = getattr(W, move)(layout(name, which), *frags)
+    W = MOVES[move][1].window(P, quirk=QUIRK[name])
+    q, c, st, _ = getattr(W, MOVES[move][2])(layout(name, which), *frags)
     return int(((st == 0) & (q != 0)).sum()), int(((st == 0) & (c != 0)).sum())
 
 
@@ -48,14 +54,14 @@ def spans(name, which, call):
     move, size = call.split("_")
     key = (name, which, move)
     if key not in _SETS:
-        sets = sorted((flips if move == "flips" else swaps).tilings(layout(name, which), None, 3), key=lambda x: len(x[0]))
+        sets = sorted(MOVES[move][0].tilings(layout(name, which), None, 3), key=lambda x: len(x[0]))
         big = [x for x in sets if scoring(name, which, move, x)[0] >= 10][-1]
         _SETS[key] = {"small": sets[0], "big": big, "all": sets[-1]}
     return _SETS[key][size]
 
 
 def run(e, call, frags):
-    return flat(e.block_flips_q(*frags) if call.startswith("flips") else e.block_swaps_q(*frags))
+    return flat(getattr(e, {"flips": "block_flips_q", "swaps": "block_swaps_q", "excise": "block_excisions_q"}[call.split("_")[0]])(*frags))
 
 
 def fresh(name, which, call):
@@ -80,7 +86,7 @@ def check(e, name, which, call, step):
 
 def assert_calls_score(name, which, calls):
     """On the CPU: every call has at least 10 valid spans whose q is not 0 ("flips_all": whose contacts are not 0)."""
-    assert FR.VALID == SR.VALID == 0
+    assert FR.VALID == SR.VALID == XR.VALID == 0
     for call in set(calls):
         move, size = call.split("_")
         assert scoring(name, which, move, spans(name, which, call))[1 if size == "all" else 0] >= 10, (name, which, call)
@@ -91,8 +97,10 @@ def test_reused_handle_equals_fresh_handle(name):
     P, uncut = problem(name)
     assert_calls_score(name, "cut", SEQUENCE)
     assert_calls_score(name, "uncut", UNCUT)
-    for move in ("flips", "swaps"):
+    for move in MOVES:
         assert len(spans(name, "cut", move + "_big")[0]) > len(spans(name, "cut", move + "_small")[0]) > 0
+    for which in ("cut", "uncut"):                       # the excisions' sets are the largest and the smallest of the tilings
+        assert spans(name, which, "excise_big") is spans(name, which, "excise_all")
     assert len(spans(name, "cut", "flips_all")[0]) >= max(len(spans(name, "cut", move + "_big")[0]) for move in ("flips", "swaps"))
     e = engine_for(P, quirk=QUIRK[name])
     try:
@@ -109,7 +117,8 @@ def test_another_problem_on_a_used_handle():
     A, _ = problem("w3")
     B, _ = problem("w1")
     assert len(A["S_o_A_frags"]["pos"]) != len(B["S_o_A_frags"]["pos"])
-    first, second = ("swaps_big", "flips_big"), ("flips_all", "swaps_small", "swaps_big", "flips_big", "flips_small")
+    first = ("swaps_big", "excise_big", "flips_big")
+    second = ("flips_all", "swaps_small", "excise_small", "flips_small", "swaps_big", "excise_big", "flips_big")
     assert_calls_score("w3", "cut", first)
     assert_calls_score("w1", "cut", second)
     e = engine_for(A, quirk=True)

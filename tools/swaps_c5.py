@@ -1,12 +1,13 @@
-"""graal_block_swaps on C5-size layouts (bench.py's 50,000-fragment / 20 M-contact stand-in), next to graal_block_flips for the same
-spans as blocks and graal_eval_full_q, on the same engine.
+"""graal_block_swaps on C5-size layouts (bench.py's 50,000-fragment / 20 M-contact stand-in), next to graal_block_flips and
+graal_block_excisions for the same spans as blocks, graal_ring_scores and graal_eval_full_q, on the same engine.
 
     python tools/swaps_c5.py [--reps N] [--nnz N]      one JSON line per (layout, tiling set): ms per call (min / median / max)
     rocprofv3 --kernel-trace --stats -d D -o sw -- python tools/swaps_c5.py --reps 3     per-kernel times
 
 Layouts: "late" (the map's 7 original contigs) and "contigs_of_8" (the original order cut into contigs of 8 fragments).  A tiling set
 (span m, split a) is graal_amd.swaps.tilings' set at offset 0: the swaps of a run of a fragments with the m - a behind it that start
-0, m, 2 m, ... fragments into every contig -- one call of a round of swap_rounds.  The flips call gets the same spans as blocks.
+0, m, 2 m, ... fragments into every contig -- one call of a round of swap_rounds.  The flips and the excisions calls get the same
+spans as blocks.
 """
 import argparse
 import json
@@ -60,14 +61,17 @@ def main():
             e.relabel_contigs()
             s = e.download_frags()
             full = timed(e.eval_full_q, args.reps)
+            rings = timed(e.ring_scores_q, args.reps)
             for span, split in sets:
                 first, mid, last = one_set(s, span, split)
                 sw = timed(lambda: e.block_swaps_q(first, mid, last), args.reps)
                 fl = timed(lambda: e.block_flips_q(first, last), args.reps)
+                ex = timed(lambda: e.block_excisions_q(first, last), args.reps)
                 q, c, st = e.block_swaps_q(first, mid, last)
                 print(json.dumps({"layout": name, "span": span, "split": split, "fragments": int(len(s["pos"])), "contacts": int(len(P["coo_row"])),
                                   "longest_contig": int(np.max(s["l_cont"])), "swaps": int(len(first)), "swaps_valid": int((st == 0).sum()),
-                                  "block_swaps_ms": sw, "block_flips_ms": fl, "eval_full_q_ms": full,
+                                  "block_swaps_ms": sw, "block_flips_ms": fl, "block_excisions_ms": ex, "ring_scores_ms": rings,
+                                  "eval_full_q_ms": full,
                                   "swaps_over_flips": round(sw["median"] / fl["median"], 2),
                                   "swaps_over_full": round(sw["median"] / full["median"], 2)}), flush=True)
     finally:
