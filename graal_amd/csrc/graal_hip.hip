@@ -87,7 +87,8 @@ __device__ __forceinline__ float rippe(float s, const Par& p)
     float result = 0.0f;
     if ((s > 0.0f) && (s < p.d_max))
     {
-        // (x / 1.0f is x: a Kuhn length of one -- the fitted models' -- needs no division; wave-uniform, the parameters are kernel arguments)
+        // (x / 1.0f is x: a Kuhn length of one -- the synthetic default's -- needs no division; a fitted one (rippe_fit) is not 1 and
+        // takes the branch; wave-uniform, the parameters are kernel arguments)
         float n = s * p.lm;
         if (p.kuhn != 1.0f) { asm volatile("" : "+v"(n)); n = n / p.kuhn; }   // (the barrier keeps this a branch: as a select, both sides were computed)
         result = (p.c1 * mm_powf_pos(s, p.slope) * mm_expf((p.d - 2) / (sq(n) + p.d))) * p.fact;
@@ -4930,6 +4931,14 @@ int graal_set_params(graal_ctx* h, const float* p)
     if (!h || !p) return GRAAL_E_ARG;
     Par np_;   // (validated before it is compared or committed: h->par never holds rejected values)
     memcpy(&np_, p, sizeof(Par));
+    // (a NaN exponent would be clamped away by mm_powf_pos and price every cis pair at v_inter, silently; a Kuhn length or a persistence
+    // length <= 0 gives powf a negative base, NaN in the reference as well)
+    if (!std::isfinite(np_.kuhn) || !(np_.kuhn > 0.0f)) return fail(h, GRAAL_E_ARG, "kuhn must be finite and > 0");
+    if (!std::isfinite(np_.lm) || !(np_.lm > 0.0f)) return fail(h, GRAAL_E_ARG, "lm must be finite and > 0");
+    if (!std::isfinite(np_.c1)) return fail(h, GRAAL_E_ARG, "c1 must be finite");
+    if (!std::isfinite(np_.slope)) return fail(h, GRAAL_E_ARG, "slope must be finite");
+    if (!std::isfinite(np_.d)) return fail(h, GRAAL_E_ARG, "d must be finite");
+    if (!std::isfinite(np_.fact)) return fail(h, GRAAL_E_ARG, "fact must be finite");
     if (!(np_.v_inter > 0.0f)) return fail(h, GRAAL_E_ARG, "v_inter must be > 0 (the sparse form prices every pixel at >= v_inter)");
     if (!(np_.d_max > 0.0f) || !(np_.d_max < 2.0e6f)) return fail(h, GRAAL_E_ARG, "d_max out of range");
     if (h->have_par && memcmp(&h->par, &np_, sizeof(Par)) == 0) return GRAAL_OK;   // (re-sending the parameters in force)

@@ -77,7 +77,7 @@ __device__ __forceinline__ float mm_powf_pos(float x, float y)
 // powf(x, y), correctly rounded, for x > 0.  x = 0 and x = +inf give powf's limits; a negative base or a NaN gives NaN (powf
 // allows negative bases with integer exponents: the model has none -- distances, the Kuhn length).  Overflow -> +inf, underflow -> 0.
 // One deviation from C's powf: powf(1, NaN) is 1 there and NaN here (y != y wins) -- the model's exponents are parameters that
-// graal_set_params has checked to be finite, so it cannot occur.
+// graal_set_params refuses unless finite (with kuhn > 0 and lm > 0, the two bases), so it cannot occur.
 __device__ __forceinline__ float mm_powf(float x, float y)
 {
     const bool ok = x > 0.0f && x < __builtin_inff();

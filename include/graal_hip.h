@@ -47,7 +47,10 @@ const char* graal_last_error(const graal_ctx* h);
 int graal_abi_version(void);
 
 /* Rippe model parameters: 8 floats kuhn,lm,c1,slope,d,d_max,fact,v_inter (kernels3.cu:26-35);
- * replaces memcpy_htod(gpu_param_simu, ...) cuda_lib_gl.py:1294, 2073 */
+ * replaces memcpy_htod(gpu_param_simu, ...) cuda_lib_gl.py:1294, 2073.
+ * Refused with GRAAL_E_ARG, the message naming the field, and with the parameters in force left as they were: a kuhn, lm, c1,
+ * slope, d or fact that is not finite; kuhn <= 0 or lm <= 0 (powf of a negative base is NaN in the reference as well);
+ * v_inter not > 0; d_max outside (0, 2e6) kb. */
 int graal_set_params(graal_ctx* h, const float* param8);
 
 /* sub-fragment tables of the n_bins unique bins (simulation_loader.py:673-704):

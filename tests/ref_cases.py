@@ -294,6 +294,41 @@ def fixture_arrays(D):
     return mut, lik
 
 
+# -- the same under the parameter sets of tests/param_cases.py: tests/golden/ref_likelihood_params.npz ------------------------------
+# Four layouts (generic and grid coordinates, rings, mixed RF counts, repeated bins) x every set; the layouts, the proposals and the
+# contacts are the ones above, only param_simu differs -- so the candidates' layouts are ref_mutations.npz's.  Totals and deltas only:
+# the per-pixel vectors are left out to keep the file small (the live tests compare them).
+PARAM_LAYOUTS = ("lin_3sub_mixed_generic", "circ_1sub_generic", "circ_3sub_mixed_generic", "rep_3sub_uniform_grid")
+PARAM_LAYOUT_INDEX = tuple([lay["name"] for lay in LAYOUTS].index(n) for n in PARAM_LAYOUTS)
+
+
+def layout_under(li, name):
+    """Layout li under the parameter set `name` (its own fact and v_inter, d_max by bisection as for the layout itself), digest included."""
+    from tests import param_cases
+    lay = LAYOUTS[li]
+    P = param_cases.with_params(lay["P"], name)
+    return dict(lay, P=P, params=name, digest=_digest(P, lay["state"]))
+
+
+def param_key(li, name, what):
+    return "l%d_%s_%s" % (li, name, what)
+
+
+def param_fixture_arrays(D):
+    """The arrays of ref_likelihood_params.npz, computed over kernel class D."""
+    from tests import param_cases
+    out = {}
+    for li in PARAM_LAYOUT_INDEX:
+        for name in param_cases.NAMES:
+            lay = layout_under(li, name)
+            dev = kernels_for(lay, D)
+            per_pix, total = likelihood_record(dev, lay)
+            out[param_key(li, name, "digest")] = np.int64(lay["digest"])
+            out[param_key(li, name, "total")] = np.float64(total)
+            out[param_key(li, name, "deltas")] = np.stack([delta_record(dev, D, lay, per_pix, fA, fBs)[0] for fA, fBs in lay["proposals"]])
+    return out
+
+
 def recorded_candidates(mut, li):
     """Decode ref_mutations.npz for layout li: (out int32[pairs, 13, 14, n] with SENTINEL on unwritten entries,
     written bool[pairs, 13, n], stale int32[pairs, 13]); refuses inputs that drifted from the recorded ones."""

@@ -3,7 +3,9 @@
 engine and returns the candidates' scores, the moves of graal_run_counters and the facts the plan read.  One rank: graal_eval_candidates,
 whose float64 scores are a fixed function of the int64 Q and coarse sums (graal_eval_candidates_x serves only a handle with an exchange of two
 ranks and more attached); they are compared as 64-bit words.  ``python -m tests.step_plan_cases out.npz`` stores the scores of every case (the child runs it with GRAAL_STRICT_DENSE=1 in its environment:
-the O(m^2) validation kernel instead of the windowed reference-arithmetic kernels)."""
+the O(m^2) validation kernel instead of the windowed reference-arithmetic kernels).  A second argument chooses the cases ("strict", or their
+positions in CASES: "0,8"), a third puts parameter sets of tests/param_cases.py behind them ("fitted_a,fitted_b": scores stored as d<i>_<set>;
+tests/test_model_params_gpu.py)."""
 import sys
 
 import numpy as np
@@ -70,12 +72,16 @@ CASES = {
 STRICT = [name for name, c in CASES.items() if c["strict"]]
 
 
-def layout_of(name):
-    """(problem, layout, max_id) of a case; the layout is the same whoever builds it."""
+def layout_of(name, params=None):
+    """(problem, layout, max_id) of a case; the layout is the same whoever builds it.  params: a parameter set of tests/param_cases.py put
+    behind the problem (contacts and layout untouched); None: the case's own parameters."""
     from tests.test_engine_gpu import relabel_ref
     from tests.test_scan_rows_gpu import layout_of_groups
     c = CASES[name]
     P = c["problem"]()
+    if params is not None:
+        from tests import param_cases
+        P = param_cases.with_params(P, params)
     rng = np.random.RandomState(c.get("seed", len(name)))
     if c.get("repeats"):
         from tests.test_repeats_gpu import random_state_with_repeats
@@ -85,11 +91,11 @@ def layout_of(name):
     return P, s, relabel_ref(s)
 
 
-def run_case(name):
+def run_case(name, params=None):
     from tests.test_repeats_gpu import engine_with_repeats, split_observations
     from tests.test_scan_rows_gpu import engine_for
     c = CASES[name]
-    P, s, max_id = layout_of(name)
+    P, s, max_id = layout_of(name, params)
     e = engine_with_repeats(P, s) if c.get("repeats") else engine_for(P, s)
     row = split_observations(P)[0][0] if c.get("repeats") else P["coo_row"]
     e.set_mode(ref_trans_accu=c["strict"], strict=c["strict"])
@@ -110,9 +116,15 @@ def run_case(name):
 
 
 if __name__ == "__main__":
-    names = STRICT if len(sys.argv) > 2 and sys.argv[2] == "strict" else list(CASES)
+    which = sys.argv[2] if len(sys.argv) > 2 else ""
+    if which and all(x.isdigit() for x in which.split(",")):             # (positions in CASES: "0,8")
+        names = [list(CASES)[int(x)] for x in which.split(",")]
+    else:
+        names = STRICT if which == "strict" else list(CASES)
+    params =sys.argv[3].split(",") if len(sys.argv) > 3 else [None]      # (parameter sets of tests/param_cases.py: keys d<i>_<set>)
     out = {}
     for i, name in enumerate(CASES):
         if name in names:
-            out["d%d" % i] = run_case(name)["deltas"]
+            for p in params:
+                out["d%d" % i + ("_" + p if p else "")] = run_case(name, p)["deltas"]
     np.savez(sys.argv[1], **out)

@@ -5,8 +5,9 @@ oracle/Makefile, built by build() wherever the reference's sources are).
 * live differential tests (skipped where the library could not be built): scalar model functions bit for bit, the 13
   candidates of every case of tests/ref_cases.py field by field, the full evaluation pixel by pixel, the candidate
   deltas, whole start_EM runs against tests/golden/traces.json;
-* fixture tests (always run): the oracle and the host build of frag_ops.h reproduce tests/golden/ref_mutations.npz and
-  ref_likelihood.npz, which were recorded from the reference's kernels and are what the GPU tests read.
+* fixture tests (always run): the oracle and the host build of frag_ops.h reproduce tests/golden/ref_mutations.npz,
+  ref_likelihood.npz and ref_likelihood_params.npz (four layouts under the parameter sets of tests/param_cases.py), which were
+  recorded from the reference's kernels and are what the GPU tests read.
 
 Bounds.  Integer results are equal.  float32 model values and per-pixel float64 log-likelihoods are equal as bit
 patterns: both sides make the same libm calls in the same order (the table in oracle/ref_host/curand_kernel.h).  Sums
@@ -22,6 +23,7 @@ import pytest
 from graal_amd import em, synth
 from oracle import oracle as O
 from oracle import ref_kernels as R
+from tests import param_cases
 from tests import ref_cases as C
 from tests import util
 from tests.golden.make_traces import problem as trace_problem
@@ -33,6 +35,7 @@ TRACES = json.load(open(os.path.join(HERE, "golden", "traces.json")))
 APPENDIX_E = json.load(open(os.path.join(HERE, "golden", "appendix_e.json")))
 MUT = np.load(os.path.join(HERE, "golden", "ref_mutations.npz"))
 LIK = np.load(os.path.join(HERE, "golden", "ref_likelihood.npz"))
+LIK_PARAMS = np.load(os.path.join(HERE, "golden", "ref_likelihood_params.npz"))
 
 
 def bits32(x):
@@ -56,6 +59,17 @@ def appendix_e_param():
 
 PARAM_SETS = {"synth_defaults": synth.make_param_simu(), "appendix_e": appendix_e_param(),
               "case_layouts": synth.make_param_simu(fact=300.0, v_inter=0.03)}
+# the sets a fit or a nuisance step gives (tests/param_cases.py), at the case layouts' fact and v_inter: kuhn != 1, other slopes, d <= 2
+PARAM_SETS.update({name: param_cases.param(name, PARAM_SETS["case_layouts"]) for name in param_cases.NAMES})
+# (layout, parameter set) of the live likelihood tests: every layout under its own parameters, four of them under the two fitted sets
+LIVE = [(li, None) for li in range(len(C.LAYOUTS))] + [(li, name) for li in C.PARAM_LAYOUT_INDEX for name in param_cases.FITTED]
+LIVE_IDS = [C.LAYOUTS[li]["name"] + ("-" + name if name else "") for li, name in LIVE]
+RECORDED = [(li, name) for li in C.PARAM_LAYOUT_INDEX for name in param_cases.NAMES]
+RECORDED_IDS = ["%s-%s" % (C.LAYOUTS[li]["name"], name) for li, name in RECORDED]
+
+
+def live_layout(li, name):
+    return C.LAYOUTS[li] if name is None else C.layout_under(li, name)
 
 
 # ---- the case list itself ---------------------------------------------------------------------------------------------------
@@ -196,9 +210,9 @@ def test_single_kernels_equal_the_reference(li):
 
 # ---- likelihood ------------------------------------------------------------------------------------------------------------
 @needs_ref
-@pytest.mark.parametrize("li", range(len(C.LAYOUTS)), ids=[lay["name"] for lay in C.LAYOUTS])
-def test_full_evaluation_per_pixel_bit_equal(li):
-    lay = C.LAYOUTS[li]
+@pytest.mark.parametrize("li,params", LIVE, ids=LIVE_IDS)
+def test_full_evaluation_per_pixel_bit_equal(li, params):
+    lay = live_layout(li, params)
     pix_o, tot_o = C.likelihood_record(C.kernels_for(lay, O.DenseOracle), lay)
     pix_r, tot_r = C.likelihood_record(C.kernels_for(lay, R.RefKernels), lay)
     assert np.array_equal(bits64(pix_o), bits64(pix_r)), np.nonzero(bits64(pix_o) != bits64(pix_r))[0][:10]
@@ -207,9 +221,9 @@ def test_full_evaluation_per_pixel_bit_equal(li):
 
 
 @needs_ref
-@pytest.mark.parametrize("li", range(len(C.LAYOUTS)), ids=[lay["name"] for lay in C.LAYOUTS])
-def test_candidate_deltas_equal_the_reference(li):
-    lay = C.LAYOUTS[li]
+@pytest.mark.parametrize("li,params", LIVE, ids=LIVE_IDS)
+def test_candidate_deltas_equal_the_reference(li, params):
+    lay = live_layout(li, params)
     dev_o, dev_r = C.kernels_for(lay, O.DenseOracle), C.kernels_for(lay, R.RefKernels)
     per_pix, _ = C.likelihood_record(dev_r, lay)
     n_stale = 0
@@ -316,10 +330,43 @@ def test_oracle_reproduces_the_recorded_likelihoods(li):
         assert np.all(np.abs(d_o - deltas_f[i])[ok] <= bound[ok]), (lay["name"], fA, fBs)
 
 
+@pytest.mark.parametrize("li,params", RECORDED, ids=RECORDED_IDS)
+def test_oracle_reproduces_the_recorded_likelihoods_under_parameter_sets(li, params):
+    """ref_likelihood_params.npz holds no pixels: the oracle's own (bit-equal to the reference's where the library is, see
+    test_full_evaluation_per_pixel_bit_equal) give the summation bounds."""
+    lay = C.layout_under(li, params)
+    param_cases.assert_not_default(lay["P"]["param_simu"])
+    assert int(LIK_PARAMS[C.param_key(li, params, "digest")]) == lay["digest"], "the regenerated inputs are not the recorded ones"
+    assert lay["digest"] != C.LAYOUTS[li]["digest"]
+    dev = C.kernels_for(lay, O.DenseOracle)
+    pix_o, tot_o = C.likelihood_record(dev, lay)
+    total_f = float(LIK_PARAMS[C.param_key(li, params, "total")])
+    param_cases.assert_reference_usable(total_f, (lay["name"], params))
+    assert abs(tot_o - total_f) <= sum_bound(pix_o)
+    deltas_f = LIK_PARAMS[C.param_key(li, params, "deltas")]
+    assert deltas_f.shape == (len(lay["proposals"]), C.K, C.N_OPS)
+    param_cases.assert_reference_usable(deltas_f[~np.isnan(deltas_f)], (lay["name"], params))
+    for i, (fA, fBs) in enumerate(lay["proposals"]):
+        d_o, bound = C.delta_record(dev, O.DenseOracle, lay, pix_o, fA, fBs)
+        assert np.array_equal(np.isnan(d_o), np.isnan(deltas_f[i]))
+        ok = ~np.isnan(d_o)
+        assert np.all(np.abs(d_o - deltas_f[i])[ok] <= bound[ok]), (lay["name"], params, fA, fBs)
+
+
+def test_recorded_parameter_sets_differ_from_the_recorded_defaults():
+    """The sets move every recorded number: a kernel that ignored kuhn, lm, slope or d would reproduce ref_likelihood.npz instead."""
+    for li in C.PARAM_LAYOUT_INDEX:
+        totals = [float(LIK["l%d_total" % li])] + [float(LIK_PARAMS[C.param_key(li, n, "total")]) for n in param_cases.NAMES]
+        assert len(set(totals)) == len(totals), totals
+        for a, b in zip(totals, totals[1:]):
+            assert abs(a - b) > 1e-6 * abs(a)
+
+
 @needs_ref
 def test_regenerating_the_fixtures_gives_identical_arrays():
     mut, lik = C.fixture_arrays(R.RefKernels)
-    for name, new, old in (("ref_mutations", mut, MUT), ("ref_likelihood", lik, LIK)):
+    par = C.param_fixture_arrays(R.RefKernels)
+    for name, new, old in (("ref_mutations", mut, MUT), ("ref_likelihood", lik, LIK), ("ref_likelihood_params", par, LIK_PARAMS)):
         assert sorted(new) == sorted(old.files), name
         for k in new:
             a, b = np.asarray(new[k]), old[k]

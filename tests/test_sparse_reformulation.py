@@ -7,6 +7,7 @@ import pytest
 from graal_amd import synth
 from oracle import oracle as O
 from oracle.sparse_numpy import SparseScorer, lf_term
+from tests import param_cases
 from tests import util
 
 
@@ -53,6 +54,28 @@ def test_full_likelihood_sparse_equals_dense(n_sub, seed):
         want = dense.evaluate(s)
         got = sparse.full(s)
         assert got == pytest.approx(want, rel=2e-7), (n_sub, seed)  # numpy float32 pow/exp vs glibc: ulp-level differences per term
+
+
+@pytest.mark.parametrize("params", param_cases.NAMES)
+@pytest.mark.parametrize("n_sub,seed", [(1, 3), (3, 4), (3, 5)])
+def test_full_likelihood_sparse_equals_dense_under_parameter_sets(n_sub, seed, params):
+    """The same problems and the same bound away from the synthetic default parameters (tests/param_cases.py): a Kuhn length that is
+    not 1, other slopes, d - 2 negative and zero."""
+    P = param_cases.with_params(small_problem(n_sub, seed, accu=1 if n_sub == 1 else 9), params)
+    param_cases.assert_not_default(P["param_simu"])
+    dense, sparse = scorers(P)
+    rng = np.random.RandomState(seed)
+    layouts = [{k: np.array(P["S_o_A_frags"][k], np.int32) for k in O.FIELDS}]
+    layouts += [_layout_with_real_lengths(P, rng, n_contigs=None, p_circ=0.5) for _ in range(4)]
+    worst = 0.0
+    for s in layouts:
+        util.check_invariants(s)
+        want = dense.evaluate(s)
+        param_cases.assert_reference_usable(want, (n_sub, seed, params))
+        got = sparse.full(s)
+        worst = max(worst, abs(got - want) / (2e-7 * abs(want)))
+        assert got == pytest.approx(want, rel=2e-7), (n_sub, seed, params)
+    print("\n[params] sparse numpy vs dense oracle, n_sub %d seed %d %s: worst |sparse - dense| / (2e-7 |logL|) = %.3g" % (n_sub, seed, params, worst))
 
 
 @pytest.mark.parametrize("n_sub,seed", [(1, 7), (3, 8)])
