@@ -36,6 +36,7 @@
 #include "scan_rows.h"
 #include "step_plan.h"
 #include "map_shape.h"
+#include "map_window.h"
 
 using namespace graal;
 
@@ -4107,6 +4108,8 @@ struct RgBuf;                  // rings.h: graal_ring_scores' and graal_close_ri
 void rg_free(RgBuf* b);
 struct MpBuf;                  // maps.h: graal_layout_maps' buffers and images
 void mp_free(MpBuf* b);
+struct MwBuf;                  // map_windows.h: graal_map_windows' buffers and images
+void mw_free(MwBuf* b);
 
 struct Ctx {
     int device = 0;
@@ -4314,6 +4317,7 @@ struct Ctx {
                                   // the first call of any of them)
     RgBuf* rg = nullptr;          // graal_ring_scores' and graal_close_rings' buffers (rings.h; allocated by the first call of either)
     MpBuf* mp = nullptr;          // graal_layout_maps' buffers and images (maps.h; allocated by its first call)
+    MwBuf* mw = nullptr;          // graal_map_windows' buffers and images (map_windows.h; allocated by its first call)
 };
 
 #define CK(call)                                                                                     \
@@ -4892,6 +4896,7 @@ void graal_destroy(graal_ctx* h)
         sp_free(h->sp); h->sp = nullptr;
         rg_free(h->rg); h->rg = nullptr;
         mp_free(h->mp); h->mp = nullptr;
+        mw_free(h->mw); h->mw = nullptr;
         if (h->x_host) (void)hipHostUnregister(h->x_host);
         if (h->h_res) (void)hipHostFree(h->h_res);
         if (h->h_stats) (void)hipHostFree(h->h_stats);
@@ -6361,3 +6366,4 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "excise.h"
 #include "edit.h"
 #include "maps.h"
+#include "map_windows.h"

@@ -1,7 +1,7 @@
 // host_check.cpp -- TEST ONLY.  Host build of frag_ops.h / strict_sets.h so that the CPU test-suite can compare the engine's
 // layout algebra (mutations, pieces, per-piece transforms, relation flags; the union set of a step, its classes of equal inputs
 // and its work units) with the oracle and with brute force without a GPU; and of the small pure headers beside them (scan_rows.h,
-// step_plan.h, map_shape.h, span_check.h).
+// step_plan.h, map_shape.h, map_window.h, span_check.h).
 // No likelihood code here and nothing in graal_amd/ loads this library.
 #include <stddef.h>
 #include <stdint.h>
@@ -14,6 +14,7 @@
 #include "scan_rows.h"
 #include "step_plan.h"
 #include "map_shape.h"
+#include "map_window.h"
 #include "span_check.h"
 
 using namespace graal;
@@ -410,6 +411,21 @@ void hc_map_shape(int S, int max_px, const int32_t* ranks, int n_ranks, int32_t*
     const MapShape s = map_shape(S, max_px);
     out[0] = s.bin; out[1] = s.m;
     for (int i = 0; i < n_ranks; i++) out[2 + i] = map_pixel(ranks[i], s.bin);
+}
+
+// ---- a map window's geometry (map_window.h), for n pixels (p[i], q[i]) of the window at (u0, v0): out[6 i ..] = the row ranks lo, hi, the
+// column ranks lo, hi, their overlap lo, hi (clipped to [0, S); lo == hi: none); pix[2 i ..] = the row pixel of ranks[2 i] and the column
+// pixel of ranks[2 i + 1] in a window of px_rows x px_cols pixels (-1: outside)
+void hc_map_window(int S, int u0, int v0, int bin, int px_rows, int px_cols, int n, const int32_t* p, const int32_t* q, const int32_t* ranks,
+                   int32_t* out, int32_t* pix)
+{
+    for (int i = 0; i < n; i++) {
+        const MwRange R = mw_pixel_ranks(u0, p[i], bin, S), C = mw_pixel_ranks(v0, q[i], bin, S), I = mw_overlap(R, C);
+        int32_t* o = out + 6 * (size_t)i;
+        o[0] = R.lo; o[1] = R.hi; o[2] = C.lo; o[3] = C.hi; o[4] = I.lo; o[5] = I.hi;
+        pix[2 * i] = mw_pixel_of(ranks[2 * i], u0, px_rows, bin);
+        pix[2 * i + 1] = mw_pixel_of(ranks[2 * i + 1], v0, px_cols, bin);
+    }
 }
 
 // ---- the spans of a call (span_check.h).  kind: 0 graal_block_flips, 1 graal_block_swaps, 2 graal_block_excisions; info: nb rows of SpanInfo's twelve fields.

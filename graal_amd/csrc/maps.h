@@ -232,6 +232,24 @@ __global__ __launch_bounds__(256) void k_mp_cis(int n, const JnFrag* __restrict_
     }
 }
 
+// One pixel from its sums (k_mp_out, and map_windows.h's k_mw_out: the same float64 operations): observed and expected from the two int64
+// sums -- `twice` is 2 where the sums hold every pair once and the pixel holds it both ways, else 1 -- the background v_over_nfpb * pairs,
+// the residual.  A pixel with a flagged term or a value that is not finite is NaN in expected and residual; returns whether it is.
+__device__ __forceinline__ bool mp_pixel(long long o_sum, long long e_sum, double twice, double pairs, double v_over_nfpb, bool flagged,
+                                         float& obs, float& exp_, float& res)
+{
+    const double o = twice * ((double)o_sum / MP_O_SCALE);
+    double e = v_over_nfpb * pairs + twice * ((double)e_sum / Q_SCALE);
+    const bool bad = flagged || !(fabs(e) < INFINITY);
+    double r = 0.0;
+    if (bad) { e = (double)NAN; r = (double)NAN; }
+    else if (e > 0.0) r = (o - e) / sqrt(e);
+    obs = (float)o;
+    exp_ = (float)e;
+    res = (float)r;
+    return bad;
+}
+
 __global__ __launch_bounds__(256) void k_mp_out(int m, const long long* __restrict__ O, const long long* __restrict__ E, const unsigned* __restrict__ badmap,
                                                 const long long* __restrict__ A, const long long* __restrict__ A2, double v_over_nfpb,
                                                 float* __restrict__ obs, float* __restrict__ exp_, float* __restrict__ res,
@@ -242,19 +260,15 @@ __global__ __launch_bounds__(256) void k_mp_out(int m, const long long* __restri
     const int p = (int)(idx / m), q = (int)(idx - (long long)p * m);
     const int key = min(p, q) * m + max(p, q);
     const double twice = p == q ? 2.0 : 1.0;
-    const double o = twice * ((double)O[key] / MP_O_SCALE);
     const long long ap = A[p], aq = A[q];
     double pairs;   // sum of accu_a accu_b over the pixel's pairs (a diagonal pixel: both ways, as the observed counts)
     if (p != q) pairs = (double)ap * (double)aq;
     else pairs = ap < (1ll << 31) ? (double)(ap * ap - A2[p]) : (double)ap * (double)ap - (double)A2[p];
-    double e = v_over_nfpb * pairs + twice * ((double)E[key] / Q_SCALE);
-    const bool bad = ((badmap[key >> 5] >> (key & 31)) & 1u) != 0 || !(fabs(e) < INFINITY);
-    double r = 0.0;
-    if (bad) { e = (double)NAN; r = (double)NAN; atomicAdd(nbad, 1ull); }
-    else if (e > 0.0) r = (o - e) / sqrt(e);
-    obs[idx] = (float)o;
-    exp_[idx] = (float)e;
-    res[idx] = (float)r;
+    float of, ef, rf;
+    if (mp_pixel(O[key], E[key], twice, pairs, v_over_nfpb, ((badmap[key >> 5] >> (key & 31)) & 1u) != 0, of, ef, rf)) atomicAdd(nbad, 1ull);
+    obs[idx] = of;
+    exp_[idx] = ef;
+    res[idx] = rf;
 }
 
 } // namespace

@@ -54,7 +54,7 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
            "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
            "graal_block_swaps", "graal_block_excisions", "graal_ring_scores", "graal_close_rings",
-           "graal_layout_maps", "graal_layout_maps_fetch",
+           "graal_layout_maps", "graal_layout_maps_fetch", "graal_map_windows", "graal_map_windows_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
 
 STEP_DONE, STEP_PAUSED, STEP_FALLBACK, STEP_SELECT = 0, 1, 2, 3
@@ -154,6 +154,8 @@ def load():
         L.graal_close_rings.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p]
         L.graal_layout_maps.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i32p, _i64p]
         L.graal_layout_maps_fetch.argtypes = [ctypes.c_void_p, _f32p, _f32p, _f32p, _i32p]
+        L.graal_map_windows.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i64p]
+        L.graal_map_windows_fetch.argtypes = [ctypes.c_void_p, _f32p, _f32p, _f32p, _i32p]
         L.graal_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_scan_path.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.graal_set_finisher.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -632,6 +634,43 @@ class Engine:
         self._ck(self._L.graal_layout_maps_fetch(self._h, ptr[0], ptr[1], ptr[2], None if pix is None else pix.ctypes.data_as(_i32p)),
                  "graal_layout_maps_fetch")
         return pix
+
+    def map_windows(self, origins, px_rows, px_cols=None, bin=1):
+        """graal_map_windows + graal_map_windows_fetch: (observed, expected, residual, rank_of_sub, bad_pixels).  `origins` is [n_win, 2]
+        (u0, v0) in ranks of the genome order of layout_maps; the three images are float32 [n_win, px_rows, px_cols] (px_cols defaults to
+        px_rows): pixel (p, q) of a window sums the bin-1 maps over the row ranks [u0 + p bin, u0 + (p + 1) bin) and the column ranks
+        [v0 + q bin, v0 + (q + 1) bin), cut to the genome; a pixel outside it is 0.  rank_of_sub int32[S]: the rank of every sub-fragment
+        id (-1: not ranked).  bad_pixels: pixels whose expected value is not finite (NaN in expected and residual).  Same preconditions
+        and refusals as layout_maps; its own buffers.  Leaves the step state alone."""
+        shape = self.map_windows_compute(origins, px_rows, px_cols, bin)
+        obs, exp, res = (np.zeros(shape, dtype=np.float32) for _ in range(3))
+        rank = self.map_windows_fetch(obs, exp, res)
+        return obs, exp, res, rank, self._windows_bad
+
+    def map_windows_compute(self, origins, px_rows, px_cols=None, bin=1):
+        """graal_map_windows alone: the images stay on the device; their shape (n_win, px_rows, px_cols)."""
+        o = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1, 2))
+        pc = int(px_rows if px_cols is None else px_cols)
+        bad = ctypes.c_int64(0)
+        self._windows_shape = None
+        self._ck(self._L.graal_map_windows(self._h, len(o), o.ctypes.data_as(_i32p), int(px_rows), pc, int(bin), ctypes.byref(bad)),
+                 "graal_map_windows")
+        self._windows_bad = int(bad.value)
+        self._windows_shape = (len(o), int(px_rows), pc)
+        return self._windows_shape
+
+    def map_windows_fetch(self, observed=None, expected=None, residual=None, rank_of_sub=True):
+        """graal_map_windows_fetch into the given float32 [n_win, px_rows, px_cols] arrays (None: not copied); returns rank_of_sub (or
+        None)."""
+        rank = np.full(int(getattr(self, "n_sub_total", 0)), -1, dtype=np.int32) if rank_of_sub else None
+        ptr = []
+        for a in (observed, expected, residual):
+            if a is not None and not (a.dtype == np.float32 and a.flags["C_CONTIGUOUS"] and a.shape == getattr(self, "_windows_shape", None)):
+                raise ValueError("map_windows_fetch takes C-contiguous float32 [n_win, px_rows, px_cols] arrays of the last map_windows_compute")
+            ptr.append(None if a is None else a.ctypes.data_as(_f32p))
+        self._ck(self._L.graal_map_windows_fetch(self._h, ptr[0], ptr[1], ptr[2], None if rank is None else rank.ctypes.data_as(_i32p)),
+                 "graal_map_windows_fetch")
+        return rank
 
     def edit_layout(self, cuts=(), joins=()):
         """graal_edit_layout: cut the junction after every fragment of `cuts`, then apply `joins` (pairs of ends, end = 2 * fragment +

@@ -105,7 +105,15 @@ def main(argv=None):
     ap.add_argument("--maps-max-px", type=int, default=2048, help="with --maps: the images' largest side, 1 .. 4096 (default 2048)")
     ap.add_argument("--maps-every", type=int, default=0, help="with --maps: also write maps/cycle_%%05d_* behind every C-th cycle (default 0: "
                                                               "the final layout's only)")
+    ap.add_argument("--maps-junctions", type=int, default=0, metavar="N",
+                    help="write maps/junction_%%03d_{observed,expected,residual}.tiff and maps/map_junctions.tsv into the output folder: "
+                         "windows of the three maps around the N junctions of the final layout that the data like least, rendered in one "
+                         "call on the GPU (graal_amd.maps)")
+    ap.add_argument("--maps-junction-px", type=int, default=256, help="with --maps-junctions: the windows' side in pixels (default 256)")
+    ap.add_argument("--maps-junction-bin", type=int, default=1, help="with --maps-junctions: sub-fragments per pixel (default 1)")
     args = ap.parse_args(argv)
+    if args.maps_junctions < 0 or (args.maps_junctions and not (1 <= args.maps_junction_px <= 4096 and args.maps_junction_bin >= 1)):
+        raise SystemExit("--maps-junctions must be >= 0, --maps-junction-px in 1 .. 4096 and --maps-junction-bin >= 1")
     if args.maps and not 1 <= args.maps_max_px <= 4096:
         raise SystemExit("--maps-max-px must be in 1 .. 4096")
     if not 0 <= args.level < args.size_pyramid:
@@ -232,6 +240,16 @@ def main(argv=None):
     if args.maps:
         from . import maps
         maps.write_maps(out, "", maps.layout_maps(smp, args.maps_max_px))
+    if args.maps_junctions:
+        from . import junctions, maps, scaffold
+        eng = scaffold._engine(smp)
+        soa = eng.download_frags()
+        score, _ = eng.junction_scores()
+        origins, table = maps.junction_windows(junctions.table_from(soa, score), soa, eng.sub_id, maps.rank_of_sub(soa, eng.sub_id),
+                                               args.maps_junctions, args.maps_junction_px, args.maps_junction_bin)
+        if len(origins):      # (a layout without a scored junction has nothing to show)
+            maps.write_junction_maps(os.path.join(out, "maps"),
+                                     maps.window_maps(eng, origins, args.maps_junction_px, bin=args.maps_junction_bin), table)
     n_steps = len(trace.likelihood)
     print("%d bins (%d fragments, %d sub-fragments), %d MCMC steps in %.1f s (%.0f us/step): %d contigs, logL %.6e, "
           "distance to the initial genome %.4f; traces in %s" % (inp["n_frags"], inp["n_new_frags"], inp["init_n_sub_frags"], n_steps,

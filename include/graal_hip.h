@@ -601,6 +601,33 @@ int graal_close_rings(graal_ctx* h, int32_t n_rings, const int32_t* frag, int32_
 int graal_layout_maps(graal_ctx* h, int32_t max_px, int32_t* m_out, int32_t* bin_out, int64_t* bad_pixels_out);
 int graal_layout_maps_fetch(graal_ctx* h, float* observed, float* expected, float* residual, int32_t* pixel_of_sub);
 
+/* Map windows: chosen windows of the three layout maps at any bin size down to one sub-fragment per pixel, many per call
+ * (graal_amd/csrc/map_windows.h; the geometry in graal_amd/csrc/map_window.h).
+ * Ranks are the layout maps' ranks u in [0, S) (the order above).  M1 is the symmetric S x S matrix of a quantity at bin 1: M1[a][b] =
+ * M1[b][a] the pair's term, M1[a][a] = 0.  Window w has the origin (u0, v0) = origin[2 w], origin[2 w + 1]; all windows of a call share
+ * px_rows, px_cols and bin.  Pixel (p, q) covers the row ranks R = [u0 + p bin, u0 + (p + 1) bin) and the column ranks C = [v0 + q bin,
+ * v0 + (q + 1) bin), both cut to [0, S), and holds the sum of M1[a][b] over a in R, b in C -- the layout maps' own pixel rule, a diagonal
+ * pixel's "both ways" included.  Windows may straddle the diagonal, overlap or repeat; origins may be negative or lie beyond S; a pixel
+ * with no row rank or no column rank is 0 in all three images and never bad.
+ *   observed   count * 2^24, rounded once per contact, added once for every ordered (a, b) in R x C the contact connects; int64;
+ *              (double)sum / 2^24 as float32.
+ *   expected   for every ordered pair a != b in R x C of one contig max(cis price, 0) - max(trans price, 0) rounded to 2^-30 once per
+ *              pair (the layout maps' term; a linear contig's pairs beyond the window are exactly 0 and skipped), summed as int64, plus
+ *              max(v_inter, 0) / n_frags_per_bins * (A(R) A(C) - A2(R n C)): A the sum of the RF counts, A2 of their squares, exact
+ *              integers (int64 while A(R), A(C) < 2^31), converted to double once.
+ *   residual   (observed - expected) / sqrt(expected) where expected > 0, else 0, in float64 from the two sums.
+ * A pixel with a term that is not finite or does not fit, or a value that is not finite, is NaN in expected and residual;
+ * *bad_pixels_out (may be NULL) counts them.  A window with bin 1 (S <= 4096), or with the bin of a layout map and origins that are
+ * multiples of it, is a crop of graal_layout_maps' images: the same integers, the same float64 operations.
+ * GRAAL_E_ARG: n_win < 1, px_rows or px_cols outside 1 .. GRAAL_MAPS_MAX_PX, bin < 1, n_win * px_rows * px_cols > GRAAL_MAPS_MAX_PX^2
+ * (the layout maps' own device budget).  Otherwise the preconditions and refusals of graal_layout_maps.  graal_map_windows_fetch copies
+ * the images of the last call out, [n_win][px_rows][px_cols] float32, and rank_of_sub (one entry per sub-fragment id, -1: not ranked);
+ * any pointer may be NULL; GRAAL_E_STATE before a successful graal_map_windows.  Does not relabel and leaves the step state alone.  The
+ * buffers are the handle's and apart from graal_layout_maps': either fetch returns its own last call's result, whatever ran in between.
+ * Cost: one pass over the contact list per call whatever n_win, and the rank pairs inside the windows. */
+int graal_map_windows(graal_ctx* h, int32_t n_win, const int32_t* origin, int32_t px_rows, int32_t px_cols, int32_t bin, int64_t* bad_pixels_out);
+int graal_map_windows_fetch(graal_ctx* h, float* observed, float* expected, float* residual, int32_t* rank_of_sub);
+
 /* ---- the sampler's per-step HOST logic behind the boundary (graal_amd/csrc/host_step.h) --------------------------------
  * What cuda_lib_gl.sampler.step_max_likelihood does on the host between its launches: return_neighbours
  * (cuda_lib_gl.py:2295-2331: RandomState.choice(xk, n, p=pk, replace=False), expansion to the copies of repeated bins,
