@@ -2147,31 +2147,56 @@ static_assert(X_WHY < X_COARSE && 2 + MAXK * N_OPS <= X_COARSE && X_COARSE + MAX
 // out -- to d_q_out (device; the caller all-reduces them) or to PINNED HOST memory followed by the step's sequence
 // number (the host spins on that word instead of paying for a device->host copy and a stream-synchronise wake-up).
 // sync[0] = k_tm ticket, sync[1] = finished k_scan blocks.
+template <bool TM = false>   // (TM: the call of k_tm's finishing block -- the debug build stamps it)
 __device__ __forceinline__ void hand_out(long long* out, unsigned long long* counters, unsigned long long* sync, int K,
                                          long long* d_q_out, volatile long long* host_res, long long seq)
 {
-    const unsigned long long why = atomicAdd(&counters[6], 0ull);   // 1 / 4 / 8: an in-kernel wait ran out (tables or scan / relabel flag / k_gprep's word); 2: a work list overflowed
-    const bool failed = why != 0ull;
-    if (host_res && threadIdx.x == 0) host_res[X_WHY] = (long long)why;
+    // Everything that is a round trip is requested at once, by different waves, and waited for once: the sums by the first waves (one thread
+    // per sum), and by the LAST wave -- which holds no sum -- the failure word and the step's three counters.
+    static_assert(MAXK * N_OPS <= TM_THREADS - 64, "hand_out: the last wave must be free of sums");
+    __shared__ unsigned long long s_why;
+    if (threadIdx.x >= TM_THREADS - 4) {   // (ONE instruction for the four words: they travel together)
+        const int j = threadIdx.x - (TM_THREADS - 4);
+        // j = 3, counters[6]: 1 / 4 / 8: an in-kernel wait ran out (tables or scan / relabel flag / k_gprep's word); 2: a work list overflowed
+        const unsigned long long v = atomicExch(&counters[j == 3 ? 6 : j], 0ull);
+        if (j < 3) counters[8 + j] = v;
+        else {
+            s_why = v;
+            if (host_res) __hip_atomic_store(const_cast<long long*>(host_res) + X_WHY, (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
     for (int i = threadIdx.x; i < K * N_OPS; i += TM_THREADS) {
         long long v = (long long)atomicExch((unsigned long long*)&out[i], 0ull); // read the final sum, reset for the next step
         const long long c = (long long)atomicExch((unsigned long long*)&out[MAXK * N_OPS + i], 0ull);   // the coarse sum (to_coarse), zero but for a rare candidate
         const bool flagged = ((atomicAdd(&counters[NF_OFF + (i >> 6)], 0ull) >> (i & 63)) & 1ull) != 0ull; // a term was not finite / out of range
-        if (host_res) { host_res[1 + i] = flagged ? Q_NAN : v; host_res[X_COARSE + i] = c; }
+        if (host_res) {   // (system-scope stores, not volatile ones: a volatile store is waited for before the next one is issued)
+            long long* const hr = const_cast<long long*>(host_res);
+            __hip_atomic_store(hr + 1 + i, flagged ? Q_NAN : v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(hr + X_COARSE + i, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
         else { d_q_out[i] = flagged ? 0ll : v; d_q_out[MAXK * N_OPS + i] = c; d_q_out[2 * MAXK * N_OPS + i] = flagged ? 1ll : 0ll; }
     }
+    // Producer form at system scope: every storing wave waits for its stores, the barrier, then ONE lane's system release fence, its wait
+    // (written out: the compiler may drop the fence's own), and the sequence word as a system-scope store.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    const bool failed = s_why != 0ull;
+    STAMP(12, TM && threadIdx.x == 0);
     // a FAILED step (counters[6]: a kernel of the step gave up waiting, a list overflowed) handed out to a device buffer: the failure must
     // survive the ranks' all-reduce, or the partial sums come back as valid scores.  It travels in the first flag word as 2^32 -- a legitimate
     // flag count is at most the number of ranks -- so the summed buffer says "some rank failed" on EVERY rank (Q_STEP_FAILED: k_qout_pub,
     // graal_amd/sampler.py)
     if (!host_res && failed && threadIdx.x == 0) d_q_out[2 * MAXK * N_OPS] += Q_STEP_FAILED;
     if (threadIdx.x >= 4 && threadIdx.x < 7) counters[NF_OFF + threadIdx.x - 4] = 0;
-    if (threadIdx.x < 3) counters[8 + threadIdx.x] = atomicExch(&counters[threadIdx.x], 0ull);
     if (threadIdx.x == 3) { counters[5] = 0; counters[6] = 0; sync[0] = 0; }
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0 && host_res) { host_res[0] = failed ? -seq : seq; __threadfence_system(); }
+    // (the resets above are wave 0's, like the fence: program order; the counters' copies lie in front of the barrier.  Nothing follows the sequence word, and a system-scope store is written
+    // through to the host's memory: no fence behind it)
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        STAMP(13, TM);
+        if (host_res) __hip_atomic_store(const_cast<long long*>(host_res), failed ? -seq : seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 constexpr long long NEED_FIN = 1ll << 62; // published instead of the sums: k_tm left work for k_fin, launch it
@@ -2397,6 +2422,9 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
     }
     __syncthreads();
     if (t < N_OPS && s_acc[t] != 0) atomicAdd((unsigned long long*)&ta.acc[k * N_OPS + t], (unsigned long long)s_acc[t]);
+    // waves 1-3: their table stores are acknowledged before lane 0 releases them (below).  Wave 0 is the releasing wave -- its own stores and the
+    // atomics above are ordered by its fence and the wait behind it, which then overlap the atomics' trip instead of following it.
+    if (t >= 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     STAMP(2, k == 0 && t == 0);
     if (t == 0) {
@@ -2404,7 +2432,14 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
         ta.step_hdr[MAXK + k] = inl ? 1 : 0;
         // release: the tables of neighbour k are complete; the word carries the work-list header for k_fin
         const unsigned long long w = ((unsigned long long)(unsigned)seq << 32) | (inl ? 0x80000000ull : 0ull) | (unsigned long long)(unsigned)ta.step_hdr[k];
-        __hip_atomic_store((unsigned long long*)&ta.tm_done[k], w, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        // Producer form "plain stores -> barrier -> ONE lane's agent release fence -> wait -> relaxed agent-scope signals": the block's
+        // stores lie behind the barrier above, this is the ONE write-back of the XCD's L2, and BOTH signals -- this word (for the kernels
+        // the host may launch later) and the ticket below (for the finishing block) -- come behind the wait for it.  The wait is written
+        // out: the header word has just been loaded and used, so the wave's counter is known to be empty and the compiler may drop the
+        // fence's own wait.  (a release STORE here and __threadfence() in front of the ticket were two write-backs for one publication)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store((unsigned long long*)&ta.tm_done[k], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         STAMP_MAX(3, true);
     }
     if (ta.host_res == nullptr) return;
@@ -2422,11 +2457,13 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
     int* const s_ntl = reinterpret_cast<int*>(s_prl + MAXK * N_PAIRS * PR_WORDS);
     if (t == 0) {
         int mode = 0;
-        __threadfence();
+        // (no fence here: the release fence and its wait above are in front of this ticket too, and nothing has been stored since that
+        // another block reads; the block that comes last acquires below)
         // one atomic: count of finished table blocks in the low 16 bits, neighbours left to k_fin above
         const unsigned long long ticket = atomicAdd(&ta.sync[0], inl ? 1ull : (1ull + (1ull << 16)));
         const unsigned long long after = ticket + (inl ? 1ull : (1ull + (1ull << 16)));
         if ((after & 0xffffull) == (unsigned long long)K) mode = (after >> 16) ? 2 : 1;
+        STAMP(11, mode == 1);
         s_fin = mode;
         s_qlive = 0;
     }
@@ -2448,13 +2485,17 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
         __shared__ int s_seen;
         // the other waves meanwhile copy what the pricing needs of all K tables into LDS (the other blocks released their
         // tables before they took their tickets)
+        // Consumer form "the ticket said 'last' -> ONE agent acquire -> that wave's wait -> the block's barrier -> plain loads": the acquire is
+        // wave 1's, in front of its copy of the keys; its wait stands in front of the barrier below, so every load of a table BEHIND that
+        // barrier finds this CU's L1 invalidated.  A wave that loads tables IN FRONT of the barrier (waves 2 and 3: the staged copy, the exact
+        // arithmetic's lists) is its own acquiring wave -- one fence each, whose own later loads need neither the wait nor the barrier.
+        // Wave 0 loads no table here: its poll reads device-scope words.
+        if (t >= 64 && (t < 128 || !ta.strict || ta.stage_tables)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         if (t >= 64 && t < 64 + K && s_fin == 1) {   // (the other blocks released their tables before they took their tickets)
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             s_qkeys[t - 64] = ta.tabs[t - 64].key;
             if (ta.tabs[t - 64].fB != fA) atomicOr(&s_qlive, 1u << (t - 64));
         }
         if (t >= 64 && s_fin == 1 && ta.strict && ta.stage_tables) {   // reference arithmetic: the transforms and class representatives of all K tables (22 KB at K = 10)
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             const int u = t - 64, nu = 256 - 64;
             Xf* const sx = reinterpret_cast<Xf*>(s_tm_dyn);
             unsigned char* const sc = reinterpret_cast<unsigned char*>(sx + MAXK * N_OPS * NP);
@@ -2462,7 +2503,6 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
             for (int e = u; e < K * N_PAIRS * N_OPS; e += nu) { const int k = e / (N_PAIRS * N_OPS), r = e - k * (N_PAIRS * N_OPS); sc[e] = ta.tabs[k].crep[r / N_OPS][r % N_OPS]; }
         }
         if (t >= 64 && s_fin == 1 && !ta.strict) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             const int u = t - 64, nu = 256 - 64;
             for (int e = u; e < K * N_PAIRS; e += nu) {
                 const int k = e / N_PAIRS, pr = e - k * N_PAIRS;
@@ -2478,6 +2518,7 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
             }
             if (u < K) s_ntl[u] = ta.tabs[u].n_tasks;
         }
+        if (t >= 64 && t < 128) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // wave 1: its invalidate has completed before it joins the barrier
         if (t < 64) {
             bool ok0 = false;
             const unsigned long long t_end = wall_clock64() + (unsigned long long)ta.wait_ticks;
@@ -2494,7 +2535,8 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
         }
         __syncthreads();
         const bool ok = s_seen != 0;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        // (no fence here: the tables are covered by wave 1's acquire, in front of the barrier above; what the scan leaves is read at device
+        // scope -- the queue's tagged words by q_fetch, counters[2] and the completion counters as atomics)
         if (t == 0) {
             s_nq = ok ? __hip_atomic_load(&ta.counters[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
             if (ok && s_nq > (unsigned long long)FIN_INLINE_Q) s_fin = 2;
@@ -2525,7 +2567,7 @@ __global__ __launch_bounds__(256) void k_tm(const DevArgs* __restrict__ A, TmArg
     }
     __syncthreads(); // (waits for this block's atomics: they are complete, at the memory side, before hand_out reads the sums)
     STAMP(5, t == 0);
-    hand_out(ta.acc, ta.counters, ta.sync, K, nullptr, ta.host_res, seq);
+    hand_out<true>(ta.acc, ta.counters, ta.sync, K, nullptr, ta.host_res, seq);
     STAMP(6, t == 0);
 }
 

@@ -4,9 +4,10 @@ import ctypes, os, sys, subprocess
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-so = os.path.join(ROOT, "graal_amd", "libgraal_hip_stamps.so")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                       "-DGRAAL_STAMPS", "-o", so, os.path.join(ROOT, "graal_amd", "csrc", "graal_hip.hip")])
+so = os.environ.get("STAMPS_LIB") or os.path.join(ROOT, "graal_amd", "libgraal_hip_stamps.so")   # STAMPS_LIB: a -DGRAAL_STAMPS library built beforehand
+if not os.environ.get("STAMPS_LIB"):
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
+                           "-DGRAAL_STAMPS", "-o", so, os.path.join(ROOT, "graal_amd", "csrc", "graal_hip.hip")])
 from graal_amd import build
 build.HIP_LIB = so
 from graal_amd import lib, synth
@@ -68,6 +69,10 @@ names = {0: "tm start", 1: "tm tables done", 2: "tm mass done", 3: "tm released"
          24: "tm: A0/B0 loaded", 25: "tm: representatives loaded", 26: "tm: transforms", 27: "tm: relations", 28: "tm: dedupe", 29: "tm: slots", 30: "tm: tasks written",
          11: "fin: unit list built (block 0)", 12: "fin: mass units done (block 0, wave 0)", 13: "fin: contacts priced (block 0, wave 0)", 14: "fin: block 0 past its barrier",
          16: "fin start", 17: "fin tables seen", 18: "fin last-indexed block at ticket", 19: "fin last block past ticket", 20: "fin sums handed out", 21: "fin seq published"}
+if not (C2 or LATE):   # k_tm's last block finishes the step: no k_fin, its numbers are the finishing block's own
+    names.update({11: "tm finisher: ticket returned 'last'", 12: "tm finisher: hand_out, sums read", 13: "tm finisher: hand_out, fenced"})
+    for i in (14, 16, 17, 18, 19, 20, 21):
+        names.pop(i, None)
 for i in sorted(names):
     if abs(a[i]) < 1e6:
         print("%-36s %7.2f us" % (names[i], a[i]))
