@@ -2,7 +2,7 @@
 
 * ``libgraal_hip.so``  -- the product: HIP kernels + C ABI, ``hipcc --offload-arch=gfx950``.
 * ``libgraal_hostcheck.so`` -- TEST ONLY: ``frag_ops.h`` (host/device shared layout algebra) and the other
-  pure headers (``strict_sets.h``, ``scan_rows.h``, ``step_plan.h``, ``map_shape.h``, ``map_window.h``, ``span_check.h``) compiled for the host with g++ so that the CPU test-suite can check it against the oracle without a GPU.
+  pure headers (``strict_sets.h``, ``scan_rows.h``, ``step_plan.h``, ``map_shape.h``, ``map_window.h``, ``span_check.h``, ``dev_buf.h``) compiled for the host with g++ so that the CPU test-suite can check it against the oracle without a GPU.
   It contains no likelihood code and is never loaded by the product path.
 """
 import glob

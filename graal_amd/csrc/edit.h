@@ -1,6 +1,6 @@
 // edit.h -- a batch of cuts and joins applied to the layout in one call (graal_edit_layout).
-// Included by graal_hip.hip after excise.h (it uses Ctx, SoaPtr, the F_* field indices, fail, wait_own and score_common.h's free_null
-// and layout_replaced).
+// Included by graal_hip.hip after excise.h (it uses Ctx, SoaPtr, the F_* field indices, fail, wait_own, dev_buf.h's DevBuf and score_common.h's
+// layout_replaced).
 //
 // The rules are those of include/graal_hip.h (graal_edit_layout); tests/edit_reference.py restates them in numpy.  Kernels, all on the
 // engine's stream:
@@ -24,37 +24,16 @@ struct EdAgg { int np, nf, nbp, minx, minlab, term, nxt, pad; };   // a walk's s
 
 struct EdBuf {
     int n = 0;
-    int *cnt = nullptr, *base = nullptr, *ncut = nullptr, *lastcut = nullptr;   // per label (2n + 5)
-    int *slot = nullptr, *at = nullptr, *cutc = nullptr, *mark = nullptr, *hs = nullptr, *ph = nullptr, *pp = nullptr, *pob = nullptr;
-    int *pcnt = nullptr, *plbp = nullptr, *ptail = nullptr, *plab = nullptr, *fresh = nullptr, *frank = nullptr;   // per fragment
-    int *ejc = nullptr, *ejo = nullptr;                              // per end (2n)
-    EdAgg* agg[2] = {nullptr, nullptr};
-    int* scal = nullptr;                                             // [0] max label, [1] error flags
-    void* tmp = nullptr; size_t tmp_bytes = 0;
-    int *d_cut = nullptr, *d_ea = nullptr, *d_eb = nullptr, *d_st = nullptr; int ccap = 0, jcap = 0;
+    DevBuf<int> cnt, base, ncut, lastcut;                            // per label (2n + 5)
+    DevBuf<int> slot, at, cutc, mark, hs, ph, pp, pob, pcnt, plbp, ptail, plab, fresh, frank;   // per fragment
+    DevBuf<int> ejc, ejo;                                            // per end (2n)
+    DevBuf<EdAgg> agg[2];
+    DevBuf<int> scal;                                                // [0] max label, [1] error flags
+    DevBuf<void> tmp;
+    DevBuf<int> d_cut, d_ea, d_eb, d_st; int ccap = 0, jcap = 0;
 };
 
-void ed_free_fixed(EdBuf* b)
-{
-    free_null({(void**)&b->cnt, (void**)&b->base, (void**)&b->ncut, (void**)&b->lastcut, (void**)&b->slot, (void**)&b->at, (void**)&b->cutc,
-               (void**)&b->mark, (void**)&b->hs, (void**)&b->ph, (void**)&b->pp, (void**)&b->pob, (void**)&b->pcnt, (void**)&b->plbp,
-               (void**)&b->ptail, (void**)&b->plab, (void**)&b->fresh, (void**)&b->frank, (void**)&b->ejc, (void**)&b->ejo,
-               (void**)&b->agg[0], (void**)&b->agg[1], (void**)&b->scal, &b->tmp});
-    b->tmp_bytes = 0; b->n = 0;
-}
-
-void ed_free_args(EdBuf* b)
-{
-    free_null({(void**)&b->d_cut, (void**)&b->d_ea, (void**)&b->d_eb, (void**)&b->d_st});
-    b->ccap = 0; b->jcap = 0;
-}
-
-void ed_free(EdBuf* b)
-{
-    if (!b) return;
-    ed_free_fixed(b); ed_free_args(b);
-    delete b;
-}
+void ed_free(EdBuf* b) { delete b; }
 
 struct EdMax { __device__ __forceinline__ int operator()(int a, int b) const { return a > b ? a : b; } };
 
@@ -306,33 +285,20 @@ int graal_edit_layout(graal_ctx* h, int32_t n_cuts, const int32_t* cut_after, in
     if (!h->ed) h->ed = new EdBuf();
     EdBuf* E = h->ed;
     if (E->n != n) {
-        ed_free_fixed(E);
-        int** per_label[] = {&E->cnt, &E->base, &E->ncut, &E->lastcut};
-        for (int** p : per_label) CK(hipMalloc(p, sizeof(int) * (size_t)NL));
-        int** per_frag[] = {&E->slot, &E->at, &E->cutc, &E->mark, &E->hs, &E->ph, &E->pp, &E->pob, &E->pcnt, &E->plbp, &E->ptail, &E->plab,
-                            &E->fresh, &E->frank};
-        for (int** p : per_frag) CK(hipMalloc(p, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&E->ejc, sizeof(int) * 2 * (size_t)n));
-        CK(hipMalloc(&E->ejo, sizeof(int) * 2 * (size_t)n));
-        CK(hipMalloc(&E->agg[0], sizeof(EdAgg) * 2 * (size_t)n));
-        CK(hipMalloc(&E->agg[1], sizeof(EdAgg) * 2 * (size_t)n));
-        CK(hipMalloc(&E->scal, sizeof(int) * 4));
         size_t b1 = 0, b2 = 0, b3 = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, E->cnt, E->base, NL, s));
-        CK(hipcub::DeviceScan::InclusiveScan(nullptr, b2, E->mark, E->hs, EdMax(), n, s));
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b3, E->fresh, E->frank, n, s));
-        E->tmp_bytes = std::max(b1, std::max(b2, b3));
-        CK(hipMalloc(&E->tmp, E->tmp_bytes));
-        E->n = n;
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, (int*)nullptr, (int*)nullptr, NL, s));
+        CK(hipcub::DeviceScan::InclusiveScan(nullptr, b2, (int*)nullptr, (int*)nullptr, EdMax(), n, s));
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b3, (int*)nullptr, (int*)nullptr, n, s));
+        const size_t n2 = 2 * (size_t)n;
+        CK(group_realloc(E->n, n, E->cnt, NL, E->base, NL, E->ncut, NL, E->lastcut, NL, E->slot, n, E->at, n, E->cutc, n, E->mark, n, E->hs, n,
+                         E->ph, n, E->pp, n, E->pob, n, E->pcnt, n, E->plbp, n, E->ptail, n, E->plab, n, E->fresh, n, E->frank, n, E->ejc, n2,
+                         E->ejo, n2, E->agg[0], n2, E->agg[1], n2, E->scal, 4, E->tmp, std::max(b1, std::max(b2, b3))));
     }
     if (n_cuts > E->ccap || n_joins > E->jcap) {
-        ed_free_args(E);
         const int cc = std::max(n_cuts, 1), jc = std::max(n_joins, 1);
-        CK(hipMalloc(&E->d_cut, sizeof(int) * (size_t)cc));
-        CK(hipMalloc(&E->d_ea, sizeof(int) * (size_t)jc));
-        CK(hipMalloc(&E->d_eb, sizeof(int) * (size_t)jc));
-        CK(hipMalloc(&E->d_st, sizeof(int) * (size_t)(cc + jc)));
-        E->ccap = cc; E->jcap = jc;
+        E->jcap = 0;
+        CK(group_realloc(E->ccap, cc, E->d_cut, cc, E->d_ea, jc, E->d_eb, jc, E->d_st, cc + jc));
+        E->jcap = jc;
     }
     int* st_cut = E->d_st;
     int* st_join = E->d_st + n_cuts;
@@ -357,8 +323,8 @@ int graal_edit_layout(graal_ctx* h, int32_t n_cuts, const int32_t* cut_after, in
     // ---- slots; a corrupt layout stops here, before anything indexes by label or slot
     k_ed_count<<<nb, 256, 0, s>>>(sp, n, E->cnt, E->scal);
     CK(hipGetLastError());
-    size_t tb = E->tmp_bytes;
-    CK(hipcub::DeviceScan::ExclusiveSum(E->tmp, tb, E->cnt, E->base, NL, s));
+    size_t tb = E->tmp.count;
+    CK(hipcub::DeviceScan::ExclusiveSum(E->tmp.p, tb, E->cnt.p, E->base.p, NL, s));
     k_ed_slot<<<nb, 256, 0, s>>>(sp, n, E->cnt, E->base, E->slot, E->at, E->scal);
     CK(hipGetLastError());
     CK(hipMemcpyAsync(scal, E->scal, sizeof scal, hipMemcpyDeviceToHost, s));
@@ -376,13 +342,13 @@ int graal_edit_layout(graal_ctx* h, int32_t n_cuts, const int32_t* cut_after, in
     }
     k_ed_mark<<<nb, 256, 0, s>>>(sp, n, E->at, E->cutc, E->cnt, E->ncut, E->mark);
     CK(hipGetLastError());
-    tb = E->tmp_bytes;
-    CK(hipcub::DeviceScan::InclusiveScan(E->tmp, tb, E->mark, E->hs, EdMax(), n, s));
+    tb = E->tmp.count;
+    CK(hipcub::DeviceScan::InclusiveScan(E->tmp.p, tb, E->mark.p, E->hs.p, EdMax(), n, s));
     k_ed_piece<<<nb, 256, 0, s>>>(sp, n, E->at, E->slot, E->hs, E->base, E->cnt, E->lastcut, E->ph, E->pp, E->pob, E->pcnt, E->plbp);
     k_ed_fresh<<<nb, 256, 0, s>>>(sp, n, E->at, E->base, E->ph, E->fresh);
     CK(hipGetLastError());
-    tb = E->tmp_bytes;
-    CK(hipcub::DeviceScan::ExclusiveSum(E->tmp, tb, E->fresh, E->frank, n, s));
+    tb = E->tmp.count;
+    CK(hipcub::DeviceScan::ExclusiveSum(E->tmp.p, tb, E->fresh.p, E->frank.p, n, s));
     k_ed_piece_lab<<<nb, 256, 0, s>>>(sp, n, E->ph, E->pp, E->pcnt, E->fresh, E->frank, E->scal, E->ptail, E->plab);
     CK(hipGetLastError());
     // ---- joins

@@ -270,7 +270,7 @@ int ex_score(graal_ctx* h, const SpanKind& K, SpanBuf* B, const std::vector<Span
 {
     const int n = h->n, m = (int)rec.size();
     const LayoutRecs& R = B->R;
-    ExSub* const sub = (ExSub*)B->sub;
+    ExSub* const sub = (ExSub*)B->sub.p;
     hipStream_t s = h->stream;
     const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     const int reach = reach_bp(h);

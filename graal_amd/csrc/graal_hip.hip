@@ -4129,6 +4129,15 @@ __global__ __launch_bounds__(256) void k_rep_delta(RepArgs R, const NbTables* __
 }
 
 // ------------------------------------------------------------------ host side
+// dev_buf.h's two functions: every device array and every pinned host word of the engine is allocated and freed here, and nowhere else.
+using devbuf_err = hipError_t;
+inline hipError_t devbuf_alloc(void** p, size_t bytes, bool pinned)
+{
+    return pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+}
+inline void devbuf_free(void* p, bool pinned) { (void)(pinned ? hipHostFree(p) : hipFree(p)); }
+#include "dev_buf.h"
+
 struct HostStep;                 // host_step.h: the sampler's per-step host logic
 void hs_free(HostStep* p);
 
@@ -4153,7 +4162,73 @@ void mp_free(MpBuf* b);
 struct MwBuf;                  // map_windows.h: graal_map_windows' buffers and images
 void mw_free(MwBuf* b);
 
-struct Ctx {
+// Every device array and pinned host word the handle owns (dev_buf.h): Ctx derives from it, so that graal_destroy releases them all at
+// one point of its order -- by assigning an empty CtxMem -- and a new member cannot be forgotten there.
+struct CtxMem {
+    // the commit's own-pixel correction (k_apply, own_pixel_q): observed counts of every bin's own sub-fragment pairs
+    DevBuf<float> d_own_obs;
+    DevBuf<long long> d_own_acc;     // k_own_corr: [0] sum, [1] unknown terms, [2] ticket
+    PinBuf<long long> h_guard;       // 8 words: k_incr's out-of-range record ([0] != 0: tripped)
+    PinBuf<long long> h_own;         // [0] the commit's number, [1] its correction (Q), [2] its unknown terms
+    // the sub-fragment tables (graal_upload_subfrags), one group
+    DevBuf<int> d_sub_ids;           // [n_bins][4], only when some bin has more than one sub-fragment
+    DevBuf<Stat> stat;
+    DevBuf<int> sub2bin;
+    DevBuf<SubRec> sub_rec;          // [n_sub_total] per sub-fragment record of the full evaluation (k_subrec)
+    DevBuf<SubRec8> sub_rec8;        // the compact form, used when every sub-fragment has the same RF count (uniform_accu > 0)
+    DevBuf<unsigned short> sub_lab16; // low 16 bits of every sub-fragment's label (k_full_nnz_l keeps them in LDS)
+    DevBuf<int> d_ubins;             // bins whose sub-fragments carry different RF counts (k_quirk_mass)
+    DevBuf<double> d_ln_tab;         // [LN_TRANS_LUT] ln of the trans value by RF-count product (k_ln_tab; rebuilt by sync_args)
+    // repeated bins (graal_upload_repeats), one group
+    DevBuf<int> d_dup_bins, d_dup_index, d_dispatcher, d_collector, d_sub_ids_all;
+    DevBuf<float> d_rep_obs;
+    // the contact list (graal_upload_contacts), one group
+    DevBuf<int> row, col, cnt;
+    DevBuf<QRaw> queue;
+    DevBuf<long long> rowptr;        // [n_sub_total + 1] first contact of row >= s; null: the list is not sorted by row (no index: every step streams)
+    // the layout (graal_upload_frags), one group under Ctx::n
+    DevBuf<int> soa_mem[2];
+    DevBuf<Geo> geo;
+    DevBuf<unsigned long long> keys, keys_sorted;
+    DevBuf<int> o2n;
+    DevBuf<int> len_of2[2], contig_off2[2]; // per layout buffer (see k_incr)
+    DevBuf<int> perm;
+    DevBuf<int> pstart;              // start_bp in position order (the position index's twin: written wherever it is)
+    DevBuf<int> cbase;
+    DevBuf<Link> link;
+    DevBuf<int> mates;
+    DevBuf<void> cub_tmp;
+    DevBuf<Stat> stat_frag;          // [n] statistics per FRAGMENT (copies of repeated bins: zero sub-fragments)
+    // graal_create's fixed set
+    DevBuf<long long> d_scalars;     // [0..7] stats, [8..9] full q, [10..12] step counters, [13] stale (int), [14] #circ,
+                                     // [15] ticket, [16] error, [18..20] counters of the last finished step
+    DevBuf<long long> d_acc;         // K*13 running sums (self-cleaning: the step's last block zeroes them after reading)
+    DevBuf<long long> tm_done;       // [MAXK] sequence number of the step whose tables are complete
+    DevBuf<unsigned long long> d_wq; // k_fin's work-queue counters (2 x N_WQ, WQ_STRIDE words apart), zero at rest
+    DevBuf<unsigned long long> d_done; // the N_DONE completion counters of k_scan, DONE_STRIDE words apart
+    DevBuf<unsigned long long> d_sync; // [0] k_tm ticket [8] finished blocks of k_scan
+    DevBuf<unsigned> d_flags;        // k_scan's per-block completion flags
+    DevBuf<long long> d_qout;        // K*13
+    DevBuf<NbTables> tabs;
+    DevBuf<int> step_hdr;            // [MAXK] mass work items per neighbour of the current step, [MAXK..] priced by k_tm
+    DevBuf<DevArgs> d_args;          // [2]: one argument block per layout buffer
+    DevBuf<long long> d_part;        // [<= 1024][N_STAT] the commit kernel's per-block statistics (published by the next k_incr)
+    DevBuf<Changed> d_chg;           // [2] commit records: a commit fills one, the relabel that consumes it clears the other
+    PinBuf<long long> h_res;         // [0] sequence number of the published step, [1..] K*13 sums
+    PinBuf<long long> h_stats;       // [0] sequence number, [1..16] the statistics words of k_stats_fin
+    PinBuf<long long> h_full;        // [0] sequence number, [1..4] the sums / flags of the last full evaluation (k_full_pub)
+    PinBuf<long long> h_dist;        // [0] sequence number, [1] half units
+    DevBuf<unsigned long long> d_dist; // [0] sum, [1] ticket
+    // reference arithmetic over the step's union set (strict2.h; launch_strict): the set, the classes per pair of global pieces, and
+    // k_strict2's unit list (k_gprep fills it), slist_cap entries
+    DevBuf<USet> d_uset;
+    DevBuf<GClass> d_cls;
+    DevBuf<int> d_cls_n;
+    DevBuf<unsigned long long> d_slist;
+    DevBuf<int4> d_dref;             // genome-distance reference (graal_upload_distance_ref)
+};
+
+struct Ctx : CtxMem {
     int device = 0;
     HostStep* hs = nullptr;
     std::string err;
@@ -4167,15 +4242,11 @@ struct Ctx {
     hipEvent_t ev_par = nullptr, ev_par2 = nullptr;   // graal_set_params: the parameter update fenced against the auxiliary streams
     // the commit's own-pixel correction (k_apply, own_pixel_q): observed counts of every bin's own sub-fragment pairs; what the statistics'
     // publications have delivered since somebody last took it (graal_take_carry_correction / graal_step with flag 16)
-    float* d_own_obs = nullptr;
     bool apply_had_own = false;      // the last commit computed it
     bool all_uniform = false;        // every bin's sub-fragments carry ONE RF count: the trans-branch indexing (GRAAL_MODE_REF_TRANS_ACCU) changes nothing
     int corr_src = 0;                // the statistics in flight come from: 1 = exactly one commit (k_apply's rows), 2 = no change, 0 = neither (unknown)
     long long carry_q = 0;
     bool carry_bad = false;
-    long long* d_own_acc = nullptr;  // k_own_corr: [0] sum, [1] unknown terms, [2] ticket
-    long long* h_guard = nullptr;    // pinned host, 8 words: k_incr's out-of-range record ([0] != 0: tripped)
-    long long* h_own = nullptr;      // pinned host: [0] the commit's number, [1] its correction (Q), [2] its unknown terms
     long long own_seq = 0;
     bool own_pending = false;        // a correction kernel is out and its result has not been taken from h_own
     int peer_repeats = 0;            // eval_sync: repeats of the step in progress because ANOTHER rank's part of it failed (host exchange)
@@ -4223,7 +4294,6 @@ struct Ctx {
                                   // event pair streams (the pairs are documented as pairs around k_scan), and a sampler run should not stream every
                                   // 8th step for a figure nobody reads
     // the row index of the contact list (k_scan_rows)
-    long long* rowptr = nullptr;  // [n_sub_total + 1] first contact of row >= s; null: the list is not sorted by row (no index: every step streams)
     long long longest_row = 0;    // contacts of the longest row (host side: the bound on what the indexed pass can visit)
     int scan_path = 0;            // graal_set_scan_path; GRAAL_SCAN_PATH (graal_create)
     bool step_indexed = false;    // the evaluation being launched takes its contacts through the row index
@@ -4252,54 +4322,22 @@ struct Ctx {
     bool has_rep = false;
     int n_dup = 0;
     std::vector<int> h_dup_index; // [n_bins] -> index into the repeated bins, -1
-    int *d_dup_bins = nullptr, *d_dup_index = nullptr, *d_dispatcher = nullptr, *d_collector = nullptr, *d_sub_ids_all = nullptr;
-    float* d_rep_obs = nullptr;
-    Stat* stat_frag = nullptr;    // [n] statistics per FRAGMENT (copies of repeated bins: zero sub-fragments)
     // device
-    int* soa_mem[2] = {nullptr, nullptr};
     SoaPtr soa[2];
     int cur = 0;
-    Geo* geo = nullptr;
-    Link* link = nullptr;
-    int* mates = nullptr;
-    Stat* stat = nullptr;
-    SubRec* sub_rec = nullptr;    // [n_sub_total] per sub-fragment record of the full evaluation (k_subrec)
-    SubRec8* sub_rec8 = nullptr;  // the compact form, used when every sub-fragment has the same RF count (uniform_accu > 0)
-    unsigned short* sub_lab16 = nullptr; // low 16 bits of every sub-fragment's label (k_full_nnz_l keeps them in LDS)
     int uniform_accu = 0;
-    int* sub2bin = nullptr;
-    int *row = nullptr, *col = nullptr, *cnt = nullptr;
-    QRaw* queue = nullptr;
     int last_fA = 0, last_K = 0, last_max_id = 0; // proposal of the last evaluation (timing replays of the scan)
     int last_fA_launch = 0;       // fA of the evaluation being launched (k_fin may be launched later, from eval_sync)
     int last_fB[MAXK] = {};
     int max_lcont = 0;            // longest contig at the last graal_begin_step (sizes k_fin's grid)
     int lcont_bound = 0;          // upper bound of the longest contig NOW (graal_step scores before it has the statistics)
-    int* d_sub_ids = nullptr;     // [n_bins][4], only when some bin has more than one sub-fragment
-    unsigned long long *keys = nullptr, *keys_sorted = nullptr;
-    int *o2n = nullptr, *perm = nullptr, *cbase = nullptr;
-    int* pstart = nullptr;         // start_bp in position order (the position index's twin: written wherever it is)
-    int *len_of2[2] = {nullptr, nullptr}, *contig_off2[2] = {nullptr, nullptr}; // per layout buffer (see k_incr)
-    long long* d_part = nullptr;  // [<= 1024][N_STAT] the commit kernel's per-block statistics (published by the next k_incr)
-    Changed* d_chg = nullptr;     // [2] commit records: a commit fills one, the relabel that consumes it clears the other
     int chg_w = 0, chg_last = 0;
     int apply_blocks = 0;         // grid of the last k_apply = rows of d_part
     bool ranks_valid = false;     // labels of buffer `cur` are ranks and its len/offset arrays are current
     int pending_commits = 0;      // commits since the last graal_begin_step
     bool incr_ok = false;         // the single pending commit started from a ranked layout with the right max_id
-    void* cub_tmp = nullptr;
-    size_t cub_tmp_bytes = 0;
-    NbTables* tabs = nullptr;
-    int* step_hdr = nullptr;      // [MAXK] mass work items per neighbour of the current step, [MAXK..] priced by k_tm
-    long long* tm_done = nullptr; // [MAXK] sequence number of the step whose tables are complete
-    long long* d_acc = nullptr;   // K*13 running sums (self-cleaning: the step's last block zeroes them after reading)
-    unsigned long long* d_sync = nullptr; // [0] k_tm ticket [8] finished blocks of k_scan
-    unsigned* d_flags = nullptr;          // k_scan's per-block completion flags
     unsigned long long scan_done_total[N_DONE] = {}; // per completion counter: blocks of all non-dry scans launched so far
-    unsigned long long* d_done = nullptr;    // the N_DONE completion counters of k_scan, DONE_STRIDE words apart
-    unsigned long long* d_wq = nullptr;      // k_fin's work-queue counters (2 x N_WQ, WQ_STRIDE words apart), zero at rest
     int mode = 0;                 // GRAAL_MODE_* flags (graal_set_mode)
-    unsigned long long* d_slist = nullptr;   // k_strict2's unit list (k_gprep fills it), slist_cap entries
     unsigned long long* d_slist_n = nullptr; // its length, a word of d_scalars (zero at rest: k_strict2's last block clears it)
     unsigned long long slist_cap = 0;
     unsigned long long slist_floor = 0;      // entries the list holds at least: raised when a step's list overflowed (eval_sync grows it and repeats the step)
@@ -4307,27 +4345,18 @@ struct Ctx {
     long long rc_list_grown = 0;
     long long rc_carry_repairs = 0;  // graal_step (flag 16): steps whose own-pixel correction was unknown and that evaluated the layout in full instead
     unsigned long long slist_soft_cap = 1ull << 23;   // 8 M entries = 64 MB (C5's 7 contigs list ~1e5); GRAAL_SLIST_SOFT_CAP (graal_create): tests set it small
-    USet* d_uset = nullptr;       // reference arithmetic over the step's union set (strict2.h): the set, the classes per pair of global pieces
-    GClass* d_cls = nullptr;
-    int* d_cls_n = nullptr;
     unsigned scan_token = 0x5ca90000u; // k_scan launches so far (ScanArgs.token)
-    double* d_ln_tab = nullptr;   // [LN_TRANS_LUT] ln of the trans value by RF-count product (k_ln_tab; rebuilt by sync_args)
-    int* d_ubins = nullptr;       // bins whose sub-fragments carry different RF counts (k_quirk_mass)
     int n_ubins = 0;
     bool finisher_ok = true;      // k_tm's last block may finish short-contig steps (switched off when the kernels turn
                                   // out not to run concurrently, e.g. under a profiler that serialises dispatches)
     int gave_up = 0;
     int event_every = 8;          // a HIP event pair around k_scan on every n-th evaluation (they cost a few us of gaps)
     long long eval_calls = 0;
-    DevArgs* d_args = nullptr;    // [2]: one argument block per layout buffer
     // reference arithmetic, one rank: `mid_run` = k_strict_flat goes out behind every scan and k_tm's last block does not try to
     // finish the step (set while most steps need more than k_tm: need_ema, a running mean of "this step did"); flat_tried = this
     // step's flat kernel has been launched (if it also says NEED_FIN, the tiled kernels follow)
     bool mid_run = false, flat_tried = false, step_needed_fin = false, step_needed_geom = false;
     double need_ema = 0.0;
-    long long* h_res = nullptr;   // pinned host: [0] sequence number of the published step, [1..] K*13 sums
-    long long* h_stats = nullptr; // pinned host: [0] sequence number, [1..16] the statistics words of k_stats_fin
-    long long* h_full = nullptr;  // pinned host: [0] sequence number, [1..4] the sums / flags of the last full evaluation (k_full_pub)
     long long full_seq = 0;
     // where the step's last block publishes: h_res, or -- with an exchange attached -- this rank's slot of the step's
     // parity in a host segment shared by the ranks of the node (host and device views of the same memory)
@@ -4340,14 +4369,8 @@ struct Ctx {
     void* nccl_comm = nullptr;    // graal_attach_rccl: the ranks' Q vectors are summed by ONE ncclAllReduce on the engine's stream (eval_sync)
     int n_rank = 0, n_world = 1;
     long long stats_seq = 0;
-    int4* d_dref = nullptr;       // genome-distance reference (graal_upload_distance_ref)
-    unsigned long long* d_dist = nullptr; // [0] sum, [1] ticket
-    long long* h_dist = nullptr;  // pinned host: [0] sequence number, [1] half units
     long long dist_seq = 0;
     long long seq = 0;
-    long long* d_scalars = nullptr; // [0..7] stats, [8..9] full q, [10..12] step counters, [13] stale (int), [14] #circ,
-                                    // [15] ticket, [16] error, [18..20] counters of the last finished step
-    long long* d_qout = nullptr;    // K*13
     long long counters[4] = {0, 0, 0, 0};
     float timing[4] = {0, 0, 0, 0};
     SimBuf* sim = nullptr;        // graal_simulate_contacts' buffers (simulate.h; allocated by its first call)
@@ -4492,7 +4515,7 @@ int sync_args(Ctx* h)
     CK(hipMemcpy(h->d_args, a, sizeof a, hipMemcpyHostToDevice));
     h->args_synced = h->have_par && h->have_sub && h->d_args != nullptr;
     if (h->have_par && h->have_sub && h->ln_lut_n > 0) {
-        if (!h->d_ln_tab) CK(hipMalloc(&h->d_ln_tab, sizeof(double) * LN_TRANS_LUT));
+        if (!h->d_ln_tab) CK(h->d_ln_tab.alloc(LN_TRANS_LUT));
         k_ln_tab<<<blocks_for(h->ln_lut_n, 256), 256, 0, h->stream>>>(h->d_ln_tab, h->ln_lut_n, h->nfpb, h->par);
         CK(hipGetLastError());
         CK(hipStreamSynchronize(h->stream));
@@ -4564,8 +4587,8 @@ int launch_scan(Ctx* h, const ProducerPlan& pp, int fA, const Neigh& nb, int K, 
     ScanArgs sa;
     sa.geo = h->geo; sa.link = h->link; sa.mates = h->mates; sa.cnt = h->cnt;
     sa.cbase = h->cbase; sa.perm = h->perm; sa.sub_ids = h->d_sub_ids;
-    sa.row4 = reinterpret_cast<const int4*>(h->row); sa.nnz = h->nnz; sa.bitmap_words = (int)(shm / 4); sa.bm_wmask = wmask;
-    sa.col4 = reinterpret_cast<const int4*>(h->col); sa.geo2 = reinterpret_cast<const int2*>(h->geo); sa.sub2bin = h->sub2bin;
+    sa.row4 = reinterpret_cast<const int4*>(h->row.p); sa.nnz = h->nnz; sa.bitmap_words = (int)(shm / 4); sa.bm_wmask = wmask;
+    sa.col4 = reinterpret_cast<const int4*>(h->col.p); sa.geo2 = reinterpret_cast<const int2*>(h->geo.p); sa.sub2bin = h->sub2bin;
     sa.queue = h->queue; sa.counters = (unsigned long long*)(h->d_scalars + 10);
     sa.flags = h->d_flags; sa.seq32 = (unsigned)h->seq;
     sa.strict = (h->mode & GRAAL_MODE_STRICT) ? 1 : 0;
@@ -4654,10 +4677,9 @@ int launch_strict(Ctx* h, const StrictPlan& sp, int fA, int K, int rank, int wor
     }
     // the union set's kernels (strict2.h): k_gprep (classes per pair of global pieces + the unit list) on the auxiliary stream behind
     // k_tm, under the scan; k_strict2 waits for both
-    if (!h->d_uset) {
-        CK(hipMalloc(&h->d_uset, sizeof(USet)));
-        CK(hipMalloc(&h->d_cls, sizeof(GClass) * (size_t)US_MAXPAIRS * US_NCAND));
-        CK(hipMalloc(&h->d_cls_n, sizeof(int) * US_MAXPAIRS + 1024));   // (+ the units' draw counter, k_gprep's ticket and completion word: a line of its own each)
+    if (!h->d_cls_n) {   // (the last of the three: a set that failed half-way is started again)
+        // (d_cls_n: + the units' draw counter, k_gprep's ticket and completion word: a line of its own each)
+        CK(group_alloc(h->d_uset, 1, h->d_cls, (size_t)US_MAXPAIRS * US_NCAND, h->d_cls_n, US_MAXPAIRS + 1024 / sizeof(int)));
         CK(hipMemset(h->d_cls_n, 0, sizeof(int) * US_MAXPAIRS + 1024));
         CK(hipDeviceSynchronize());
     }
@@ -4666,11 +4688,7 @@ int launch_strict(Ctx* h, const StrictPlan& sp, int fA, int K, int rank, int wor
     h->slist_worst = sp.worst;
     if (sp.alloc) {
         CK(hipDeviceSynchronize());   // (rare: the first tiled step of a layout size, or a list that has just overflowed)
-        if (h->d_slist) CK(hipFree(h->d_slist));
-        h->d_slist = nullptr;
-        h->slist_cap = 0;
-        CK(hipMalloc(&h->d_slist, sp.alloc * sizeof(unsigned long long)));
-        h->slist_cap = sp.alloc;
+        CK(group_realloc(h->slist_cap, sp.alloc, h->d_slist, sp.alloc));
     }
     h->d_slist_n = (unsigned long long*)(h->d_scalars + SLIST_N);
     sx.list_cap = h->slist_cap;
@@ -4865,45 +4883,39 @@ int graal_create(int device, graal_ctx** out)
     for (auto& ev : h->ring) CK(hipEventCreate(&ev));
     h->sring.resize(2 * 256, nullptr);
     for (auto& ev : h->sring) CK(hipEventCreate(&ev));
-    CK(hipMalloc(&h->d_scalars, 32 * sizeof(long long)));
+    CK(h->d_scalars.alloc(32));
     CK(hipMemset(h->d_scalars, 0, 32 * sizeof(long long)));
-    CK(hipMalloc(&h->d_acc, 2 * MAXK * N_OPS * sizeof(long long)));   // (fine sums, coarse sums: to_coarse)
+    CK(h->d_acc.alloc(2 * MAXK * N_OPS));   // (fine sums, coarse sums: to_coarse)
     CK(hipMemset(h->d_acc, 0, 2 * MAXK * N_OPS * sizeof(long long)));
-    CK(hipMalloc(&h->tm_done, MAXK * sizeof(long long)));
+    CK(h->tm_done.alloc(MAXK));
     CK(hipMemset(h->tm_done, 0, MAXK * sizeof(long long)));
-    CK(hipMalloc(&h->d_wq, 2 * N_WQ * WQ_STRIDE * sizeof(unsigned long long)));
+    CK(h->d_wq.alloc(2 * N_WQ * WQ_STRIDE));
     CK(hipMemset(h->d_wq, 0, 2 * N_WQ * WQ_STRIDE * sizeof(unsigned long long)));
-    CK(hipMalloc(&h->d_done, N_DONE * DONE_STRIDE * sizeof(unsigned long long)));
+    CK(h->d_done.alloc(N_DONE * DONE_STRIDE));
     CK(hipMemset(h->d_done, 0, N_DONE * DONE_STRIDE * sizeof(unsigned long long)));
-    CK(hipMalloc(&h->d_sync, 32 * sizeof(unsigned long long)));
+    CK(h->d_sync.alloc(32));
     CK(hipMemset(h->d_sync, 0, 32 * sizeof(unsigned long long)));
-    CK(hipMalloc(&h->d_flags, (size_t)MAX_SCAN_BLOCKS * FLAG_STRIDE * sizeof(unsigned)));
+    CK(h->d_flags.alloc((size_t)MAX_SCAN_BLOCKS * FLAG_STRIDE));
     CK(hipMemset(h->d_flags, 0, (size_t)MAX_SCAN_BLOCKS * FLAG_STRIDE * sizeof(unsigned)));
-    CK(hipMalloc(&h->d_qout, 3 * MAXK * N_OPS * sizeof(long long)));   // (fine sums, coarse sums, not-finite flags: hand_out)
-    CK(hipMalloc(&h->tabs, MAXK * sizeof(NbTables)));
-    CK(hipMalloc(&h->step_hdr, 2 * MAXK * sizeof(int)));
+    CK(h->d_qout.alloc(3 * MAXK * N_OPS));   // (fine sums, coarse sums, not-finite flags: hand_out)
+    CK(h->tabs.alloc(MAXK));
+    CK(h->step_hdr.alloc(2 * MAXK));
     CK(hipMemset(h->step_hdr, 0, 2 * MAXK * sizeof(int)));
-    CK(hipMalloc(&h->d_args, 2 * sizeof(DevArgs)));
-    CK(hipMalloc(&h->d_part, 1024 * N_STAT * sizeof(long long)));
+    CK(h->d_args.alloc(2));
+    CK(h->d_part.alloc(1024 * N_STAT));
     CK(hipMemset(h->d_part, 0, 1024 * N_STAT * sizeof(long long)));
-    CK(hipMalloc(&h->d_chg, 2 * sizeof(Changed)));
+    CK(h->d_chg.alloc(2));
     CK(hipMemset(h->d_chg, 0, 2 * sizeof(Changed)));
-    CK(hipHostMalloc((void**)&h->h_res, X_SLOT_WORDS * sizeof(long long), hipHostMallocDefault));
-    memset(h->h_res, 0, X_SLOT_WORDS * sizeof(long long));
+    CK(h->h_res.alloc(X_SLOT_WORDS));
     h->res_host = h->res_dev = h->h_res;
-    CK(hipHostMalloc((void**)&h->h_dist, 2 * sizeof(long long), hipHostMallocDefault));
-    memset(h->h_dist, 0, 2 * sizeof(long long));
-    CK(hipMalloc(&h->d_dist, 2 * sizeof(unsigned long long)));
+    CK(h->h_dist.alloc(2));
+    CK(h->d_dist.alloc(2));
     CK(hipMemset(h->d_dist, 0, 2 * sizeof(unsigned long long)));
-    CK(hipHostMalloc((void**)&h->h_full, 8 * sizeof(long long), hipHostMallocDefault));
-    memset(h->h_full, 0, 8 * sizeof(long long));
-    CK(hipHostMalloc((void**)&h->h_stats, 17 * sizeof(long long), hipHostMallocDefault));
-    memset(h->h_stats, 0, 17 * sizeof(long long));
-    CK(hipHostMalloc((void**)&h->h_guard, 8 * sizeof(long long), hipHostMallocDefault));
-    memset(h->h_guard, 0, 8 * sizeof(long long));
-    CK(hipHostMalloc((void**)&h->h_own, 4 * sizeof(long long), hipHostMallocDefault));
-    memset(h->h_own, 0, 4 * sizeof(long long));
-    CK(hipMalloc(&h->d_own_acc, 4 * sizeof(long long)));
+    CK(h->h_full.alloc(8));
+    CK(h->h_stats.alloc(17));
+    CK(h->h_guard.alloc(8));
+    CK(h->h_own.alloc(4));
+    CK(h->d_own_acc.alloc(4));
     CK(hipMemset(h->d_own_acc, 0, 4 * sizeof(long long)));
     {
         const long long init[8] = {0, 0, 0, 0, 0, 0x7fffffff, 0, -1}; // k_stats accumulators (re-armed by k_stats_fin)
@@ -4923,13 +4935,9 @@ void graal_destroy(graal_ctx* h)
         // ... and whatever this handle's kernels were launched on besides its own streams (graal_eval_candidates_q takes the CALLER'S stream: the
         // torch path of exchange="rccl"): nothing of this process may still touch the buffers, pinned words and the registered segment freed below
         (void)hipDeviceSynchronize();
-        void* ptrs[] = {h->soa_mem[0], h->soa_mem[1], h->geo, h->stat, h->sub_rec, h->sub_rec8, h->sub_lab16, h->d_ubins, h->d_ln_tab, h->sub2bin, h->row, h->col, h->cnt, h->queue, h->rowptr, h->d_sub_ids, h->d_acc, h->tm_done, h->d_sync, h->d_done, h->d_wq, h->d_flags, h->d_slist, h->d_uset, h->d_cls, h->d_cls_n, h->stat_frag, h->d_dup_bins, h->d_dup_index,
-                        h->d_dispatcher, h->d_collector, h->d_sub_ids_all, h->d_rep_obs,
-                        h->keys, h->keys_sorted, h->o2n, h->len_of2[0], h->len_of2[1], h->contig_off2[0], h->contig_off2[1], h->perm, h->pstart, h->cbase, h->link, h->mates, h->cub_tmp, h->tabs, h->step_hdr, h->d_args, h->d_chg, h->d_part,
-                        h->d_scalars, h->d_qout, h->d_dref, h->d_dist};
-        for (void* p : ptrs) if (p) (void)hipFree(p);
         if (h->nccl_comm) { Rccl* R = rccl_load(nullptr); if (R) (void)R->CommDestroy(h->nccl_comm); h->nccl_comm = nullptr; }
-        if (h->d_own_obs) (void)hipFree(h->d_own_obs);
+        if (h->x_host) (void)hipHostUnregister(h->x_host);
+        // every buffer, while the handle's device is current: the scorers' sets, then all of CtxMem at once
         sim_free(h->sim); h->sim = nullptr;
         jn_free(h->jn); h->jn = nullptr;
         ln_free(h->ln); h->ln = nullptr;
@@ -4939,14 +4947,7 @@ void graal_destroy(graal_ctx* h)
         rg_free(h->rg); h->rg = nullptr;
         mp_free(h->mp); h->mp = nullptr;
         mw_free(h->mw); h->mw = nullptr;
-        if (h->x_host) (void)hipHostUnregister(h->x_host);
-        if (h->h_res) (void)hipHostFree(h->h_res);
-        if (h->h_stats) (void)hipHostFree(h->h_stats);
-        if (h->h_own) (void)hipHostFree(h->h_own);
-        if (h->h_guard) (void)hipHostFree(h->h_guard);
-        if (h->d_own_acc) (void)hipFree(h->d_own_acc);
-        if (h->h_full) (void)hipHostFree(h->h_full);
-        if (h->h_dist) (void)hipHostFree(h->h_dist);
+        static_cast<CtxMem&>(*h) = CtxMem();
         for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
         for (auto& ev : h->ring) if (ev) (void)hipEventDestroy(ev);
         for (auto& ev : h->sring) if (ev) (void)hipEventDestroy(ev);
@@ -5060,19 +5061,13 @@ int graal_upload_subfrags(graal_ctx* h, const int32_t* sub_id, const float* sub_
     h->has_rep = false; h->n_dup = 0; h->h_dup_index.assign((size_t)n_bins, -1); // (graal_upload_repeats comes after)
     // single_sub additionally needs sub id == bin id so that the scan can skip the sub2bin gather
     for (int b = 0; single && b < n_bins; b++) single = (sub_id[4 * b] == b);
-    if (h->stat) { (void)hipFree(h->stat); (void)hipFree(h->sub2bin); (void)hipFree(h->d_sub_ids); (void)hipFree(h->sub_rec); (void)hipFree(h->sub_rec8); (void)hipFree(h->sub_lab16); h->d_sub_ids = nullptr; h->sub_rec = nullptr; h->sub_rec8 = nullptr; h->sub_lab16 = nullptr; }
-    if (!single) {
-        CK(hipMalloc(&h->d_sub_ids, sizeof(int) * 4 * (size_t)n_bins));
-        CK(hipMemcpy(h->d_sub_ids, sub_id, sizeof(int) * 4 * (size_t)n_bins, hipMemcpyHostToDevice));
-    }
-    CK(hipMalloc(&h->stat, sizeof(Stat) * (size_t)n_bins));
-    CK(hipMalloc(&h->sub2bin, sizeof(int) * (size_t)n_sub_total));
-    CK(hipMalloc(&h->sub_rec, sizeof(SubRec) * (size_t)n_sub_total));
-    CK(hipMemset(h->sub_rec, 0, sizeof(SubRec) * (size_t)n_sub_total));
-    CK(hipMalloc(&h->sub_rec8, sizeof(SubRec8) * (size_t)n_sub_total));
-    CK(hipMemset(h->sub_rec8, 0, sizeof(SubRec8) * (size_t)n_sub_total));
-    CK(hipMalloc(&h->sub_lab16, 2 * (size_t)(((size_t)n_sub_total + 7) & ~(size_t)7)));
-    CK(hipMemset(h->sub_lab16, 0, 2 * (size_t)(((size_t)n_sub_total + 7) & ~(size_t)7)));
+    const size_t S = (size_t)n_sub_total;
+    CK(group_alloc(h->d_sub_ids, single ? 0 : 4 * (size_t)n_bins, h->stat, n_bins, h->sub2bin, S, h->sub_rec, S, h->sub_rec8, S,
+                   h->sub_lab16, (S + 7) & ~(size_t)7));
+    if (!single) CK(hipMemcpy(h->d_sub_ids, sub_id, sizeof(int) * 4 * (size_t)n_bins, hipMemcpyHostToDevice));
+    CK(hipMemset(h->sub_rec, 0, sizeof(SubRec) * S));
+    CK(hipMemset(h->sub_rec8, 0, sizeof(SubRec8) * S));
+    CK(hipMemset(h->sub_lab16, 0, 2 * ((S + 7) & ~(size_t)7)));
     {
         h->uniform_accu = sub_accu[0];
         for (int b = 0; b < n_bins && h->uniform_accu; b++)
@@ -5087,10 +5082,10 @@ int graal_upload_subfrags(graal_ctx* h, const int32_t* sub_id, const float* sub_
             for (int k = 1; k < ns; k++) uni = uni && sub_accu[3 * b + k] == sub_accu[3 * b];
             if (!uni) ub.push_back(b);
         }
-        if (h->d_ubins) { (void)hipFree(h->d_ubins); h->d_ubins = nullptr; }
+        h->d_ubins.release();
         h->n_ubins = (int)ub.size();
         if (h->n_ubins) {
-            CK(hipMalloc(&h->d_ubins, sizeof(int) * ub.size()));
+            CK(h->d_ubins.alloc(ub.size()));
             CK(hipMemcpy(h->d_ubins, ub.data(), sizeof(int) * ub.size(), hipMemcpyHostToDevice));
         }
     }
@@ -5126,9 +5121,12 @@ int graal_upload_repeats(graal_ctx* h, const int32_t* dup_bins, int32_t n_dup, c
     if (!h || n_dup < 0 || (n_dup > 0 && (!dup_bins || !dispatcher || !collector || !obs_rows))) return GRAAL_E_ARG;
     if (!h->have_sub) return fail(h, GRAAL_E_STATE, "upload_subfrags first");
     CK(hipSetDevice(h->device));
-    void* old[] = {h->d_dup_bins, h->d_dup_index, h->d_dispatcher, h->d_collector, h->d_sub_ids_all, h->d_rep_obs};
-    for (void* p : old) if (p) (void)hipFree(p);
-    h->d_dup_bins = h->d_dup_index = h->d_dispatcher = h->d_collector = h->d_sub_ids_all = nullptr; h->d_rep_obs = nullptr;
+    auto reserve = [&](size_t nd) {   // (nd 0: the release alone)
+        const size_t nb = nd ? (size_t)h->n_bins : 0;
+        return group_alloc(h->d_dup_bins, nd, h->d_dup_index, nb, h->d_dispatcher, 2 * nb, h->d_collector, nd ? (size_t)n_collector : 0,
+                           h->d_sub_ids_all, 4 * nb, h->d_rep_obs, 3 * nd * (size_t)h->n_sub_total);
+    };
+    CK(reserve(0));
     h->h_dup_index.assign((size_t)h->n_bins, -1);
     h->has_rep = n_dup > 0; h->n_dup = n_dup;
     h->have_frags = false; h->have_contacts = false; h->order_valid = false; // both depend on which bins are repeated
@@ -5142,12 +5140,7 @@ int graal_upload_repeats(graal_ctx* h, const int32_t* dup_bins, int32_t n_dup, c
         if (lo < 0 || hi > n_collector || hi <= lo) return fail(h, GRAAL_E_ARG, "dispatcher ranges must be non-empty and inside the collector");
         if (h->h_dup_index[b] < 0 && (hi - lo != 1 || collector[lo] != b)) return fail(h, GRAAL_E_ARG, "a non-repeated bin has exactly one copy: itself");
     }
-    CK(hipMalloc(&h->d_dup_bins, sizeof(int) * (size_t)n_dup));
-    CK(hipMalloc(&h->d_dup_index, sizeof(int) * (size_t)h->n_bins));
-    CK(hipMalloc(&h->d_dispatcher, sizeof(int) * 2 * (size_t)h->n_bins));
-    CK(hipMalloc(&h->d_collector, sizeof(int) * (size_t)n_collector));
-    CK(hipMalloc(&h->d_sub_ids_all, sizeof(int) * 4 * (size_t)h->n_bins));
-    CK(hipMalloc(&h->d_rep_obs, sizeof(float) * 3 * (size_t)n_dup * (size_t)h->n_sub_total));
+    CK(reserve((size_t)n_dup));
     CK(hipMemcpy(h->d_dup_bins, dup_bins, sizeof(int) * (size_t)n_dup, hipMemcpyHostToDevice));
     CK(hipMemcpy(h->d_dup_index, h->h_dup_index.data(), sizeof(int) * (size_t)h->n_bins, hipMemcpyHostToDevice));
     CK(hipMemcpy(h->d_dispatcher, dispatcher, sizeof(int) * 2 * (size_t)h->n_bins, hipMemcpyHostToDevice));
@@ -5180,15 +5173,14 @@ static int upload_contacts_impl(graal_ctx* h, const int32_t* row, const int32_t*
         const int ci = (int)c;
         c_lf_q += (c < 16.0f && (float)ci == c) ? lf_small[ci] : llrint(lf_term((double)c) * Q_SCALE);
     }
-    if (h->row) { (void)hipFree(h->row); (void)hipFree(h->col); (void)hipFree(h->cnt); (void)hipFree(h->queue); h->row = h->col = h->cnt = nullptr; h->queue = nullptr; }
-    if (h->rowptr) { (void)hipFree(h->rowptr); h->rowptr = nullptr; }
     h->longest_row = 0;
-    const size_t bytes = sizeof(int) * (size_t)(nnz + 8); // +8: int4 tail reads stay in bounds
-    CK(hipMalloc(&h->row, bytes)); CK(hipMalloc(&h->col, bytes)); CK(hipMalloc(&h->cnt, bytes));
+    const size_t len = (size_t)(nnz + 8);   // +8: int4 tail reads stay in bounds; the queue: every contact may have both ends affected in the worst case
+    const size_t bytes = sizeof(int) * len;
+    // (the row index: (ids + 1) 64-bit offsets, only for a list sorted by row)
+    CK(group_alloc(h->row, len, h->col, len, h->cnt, len, h->queue, len, h->rowptr, runs.sorted ? (size_t)h->n_sub_total + 1 : 0));
     CK(hipMemset(h->row, 0, bytes)); CK(hipMemset(h->col, 0, bytes));
-    CK(hipMalloc(&h->queue, sizeof(QRaw) * (size_t)(nnz + 8))); // every contact may have both ends affected in the worst case
     // (recycled device memory may hold another engine's entries, tags and all: a consumer that validates tags must never meet them)
-    CK(hipMemset(h->queue, 0, sizeof(QRaw) * (size_t)(nnz + 8)));
+    CK(hipMemset(h->queue, 0, sizeof(QRaw) * len));
     if (nnz) {
         CK(hipMemcpy(h->row, row, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
         CK(hipMemcpy(h->col, col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
@@ -5196,8 +5188,7 @@ static int upload_contacts_impl(graal_ctx* h, const int32_t* row, const int32_t*
     }
     // (an EMPTY list -- a rank whose shard holds nothing -- is a sorted list: its offsets are all zero and every row's slice is empty; the
     // switch never takes it, 0 contacts are never R times a bound, but a forced indexed pass finds what the streaming pass finds: nothing)
-    if (runs.sorted) {   // the row index: (ids + 1) 64-bit offsets, one binary search per id over the uploaded list
-        CK(hipMalloc(&h->rowptr, sizeof(long long) * ((size_t)h->n_sub_total + 1)));
+    if (runs.sorted) {   // the row index: one binary search per id over the uploaded list
         k_rowptr<<<blocks_for((long long)h->n_sub_total + 1, 256), 256, 0, h->stream>>>(h->n_sub_total, h->row, nnz, h->rowptr);
         CK(hipGetLastError());
         CK(hipStreamSynchronize(h->stream));
@@ -5205,7 +5196,7 @@ static int upload_contacts_impl(graal_ctx* h, const int32_t* row, const int32_t*
     }
     h->nnz = nnz; h->c_lf_q = c_lf_q; h->have_contacts = true;
     // the observed counts of every bin's OWN sub-fragment pairs (own_pixel_q): contacts whose two sub-fragments belong to one bin
-    if (h->d_own_obs) { (void)hipFree(h->d_own_obs); h->d_own_obs = nullptr; }
+    h->d_own_obs.release();
     if (!h->single_sub && !h->has_rep) {
         std::vector<float> own(3 * (size_t)h->n_bins, 0.0f);
         for (int64_t i = 0; i < nnz; i++) {
@@ -5215,7 +5206,7 @@ static int upload_contacts_impl(graal_ctx* h, const int32_t* row, const int32_t*
             if (sa == sb) continue;
             own[3 * (size_t)(ra >> 2) + (sa == 0 ? sb - 1 : 2)] = count[i];
         }
-        CK(hipMalloc(&h->d_own_obs, sizeof(float) * own.size()));
+        CK(h->d_own_obs.alloc(own.size()));
         CK(hipMemcpy(h->d_own_obs, own.data(), sizeof(float) * own.size(), hipMemcpyHostToDevice));
     }
     h->own_complete = false;
@@ -5262,31 +5253,16 @@ int graal_upload_frags(graal_ctx* h, const int32_t* const soa[GRAAL_N_FIELDS], i
             return fail(h, GRAAL_E_ARG, "rep and activ must be 0 or 1");
     }
     if (h->n != n) {
-        void* old[] = {h->soa_mem[0], h->soa_mem[1], h->geo, h->keys, h->keys_sorted, h->o2n, h->len_of2[0], h->len_of2[1], h->contig_off2[0], h->contig_off2[1], h->perm, h->pstart, h->cbase, h->link, h->mates, h->cub_tmp};
-        for (void* p : old) if (p) (void)hipFree(p);
-        for (int b = 0; b < 2; b++) {
-            CK(hipMalloc(&h->soa_mem[b], sizeof(int) * (size_t)n * GRAAL_N_FIELDS));
-            for (int k = 0; k < GRAAL_N_FIELDS; k++) h->soa[b].p[k] = h->soa_mem[b] + (size_t)k * n;
-        }
-        CK(hipMalloc(&h->geo, sizeof(Geo) * (size_t)n));
-        CK(hipMalloc(&h->keys, sizeof(unsigned long long) * (size_t)n));
-        CK(hipMalloc(&h->keys_sorted, sizeof(unsigned long long) * (size_t)n));
-        CK(hipMalloc(&h->o2n, sizeof(int) * (size_t)(2 * n + 8)));
-        for (int b = 0; b < 2; b++) {
-            CK(hipMalloc(&h->len_of2[b], sizeof(int) * (size_t)(n + 2)));
-            CK(hipMalloc(&h->contig_off2[b], sizeof(int) * (size_t)(n + 2)));
-        }
-        CK(hipMalloc(&h->perm, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&h->pstart, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&h->cbase, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&h->link, sizeof(Link) * (size_t)n));
-        CK(hipMalloc(&h->mates, sizeof(int) * N_MATES * (size_t)n));
         size_t b1 = 0, b2 = 0;
-        (void)hipcub::DeviceRadixSort::SortKeys(nullptr, b1, h->keys, h->keys_sorted, n, 0, 2 * LABEL_BITS, h->stream);
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b2, h->len_of2[0], h->contig_off2[0], n + 1, h->stream);
-        h->cub_tmp_bytes = b1 > b2 ? b1 : b2;
-        CK(hipMalloc(&h->cub_tmp, h->cub_tmp_bytes));
-        h->n = n;
+        (void)hipcub::DeviceRadixSort::SortKeys(nullptr, b1, (unsigned long long*)nullptr, (unsigned long long*)nullptr, n, 0, 2 * LABEL_BITS, h->stream);
+        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (int*)nullptr, (int*)nullptr, n + 1, h->stream);
+        h->have_frags = false;   // (until this upload has gone through: h->n reads 0 while the set is being replaced)
+        const size_t N = (size_t)n;
+        CK(group_realloc(h->n, N, h->soa_mem[0], N * GRAAL_N_FIELDS, h->soa_mem[1], N * GRAAL_N_FIELDS, h->geo, N, h->keys, N, h->keys_sorted, N,
+                         h->o2n, 2 * N + 8, h->len_of2[0], N + 2, h->contig_off2[0], N + 2, h->len_of2[1], N + 2, h->contig_off2[1], N + 2, h->perm, N,
+                         h->pstart, N, h->cbase, N, h->link, N, h->mates, N_MATES * N, h->cub_tmp, std::max(b1, b2)));
+        for (int b = 0; b < 2; b++)
+            for (int k = 0; k < GRAAL_N_FIELDS; k++) h->soa[b].p[k] = h->soa_mem[b] + (size_t)k * n;
     }
     h->cur = 0; h->ranks_valid = false; h->pending_commits = 0; h->begin_launched = false; h->stats_from_apply = false;
     for (int k = 0; k < GRAAL_N_FIELDS; k++)
@@ -5299,8 +5275,7 @@ int graal_upload_frags(graal_ctx* h, const int32_t* const soa[GRAAL_N_FIELDS], i
             sf[(size_t)i] = h->h_stat[(size_t)b];
             if (h->has_rep && h->h_dup_index[b] >= 0) sf[(size_t)i].n = 0;
         }
-        if (h->stat_frag) (void)hipFree(h->stat_frag);
-        CK(hipMalloc(&h->stat_frag, sizeof(Stat) * (size_t)n));
+        CK(h->stat_frag.alloc(n));
         CK(hipMemcpy(h->stat_frag, sf.data(), sizeof(Stat) * (size_t)n, hipMemcpyHostToDevice));
     }
     h->have_frags = true; h->order_valid = false;
@@ -5388,18 +5363,18 @@ static int begin_step_launch(graal_ctx* h, bool defer = false)
     } else {
         k_relabel_keys<<<nb, bs, 0, h->stream>>>(s, n, h->keys);
         CK(hipGetLastError());
-        size_t tb = h->cub_tmp_bytes;
-        CK(hipcub::DeviceRadixSort::SortKeys(h->cub_tmp, tb, h->keys, h->keys_sorted, n, 0, 2 * LABEL_BITS, h->stream));
+        size_t tb = h->cub_tmp.count;
+        CK(hipcub::DeviceRadixSort::SortKeys(h->cub_tmp.p, tb, h->keys.p, h->keys_sorted.p, n, 0, 2 * LABEL_BITS, h->stream));
         k_relabel_o2n<<<nb, bs, 0, h->stream>>>(h->keys_sorted, n, h->d_scalars, h->o2n, h->len_of2[cur]);
         k_relabel_apply<<<nb, bs, 0, h->stream>>>(s, n, h->o2n);
         CK(hipGetLastError());
-        tb = h->cub_tmp_bytes;
-        CK(hipcub::DeviceScan::ExclusiveSum(h->cub_tmp, tb, h->len_of2[cur], h->contig_off2[cur], n + 1, h->stream));
+        tb = h->cub_tmp.count;
+        CK(hipcub::DeviceScan::ExclusiveSum(h->cub_tmp.p, tb, h->len_of2[cur].p, h->contig_off2[cur].p, n + 1, h->stream));
         k_build_perm<<<nb, bs, 0, h->stream>>>(s, n, h->contig_off2[cur], h->perm, h->cbase, h->pstart);
         CK(hipGetLastError());
         int rc = refresh(h);
         if (rc) return rc;
-        k_mates<<<nb, bs, 0, h->stream>>>(n, h->perm, h->cbase, h->link, h->mates, (int*)h->d_chg, (int)(2 * sizeof(Changed) / sizeof(int)));
+        k_mates<<<nb, bs, 0, h->stream>>>(n, h->perm, h->cbase, h->link, h->mates, (int*)h->d_chg.p, (int)(2 * sizeof(Changed) / sizeof(int)));
         CK(hipGetLastError());
         full_relabel = true;
     }
@@ -5523,7 +5498,7 @@ static int full_launch(graal_ctx* h, hipStream_t fs)
         // the compact records serve that mode too)
         k_subrec<<<blocks_for(h->n, 256), 256, 0, fs>>>(h->n, h->geo, h->stat_frag, h->d_sub_ids, h->sub_rec, fp.compact ? h->sub_rec8 : nullptr, h->sub_lab16);
         constexpr int FG = PLAN_FULL_G;
-#define FULL_NNZ_ARGS reinterpret_cast<const int4*>(h->row), reinterpret_cast<const int4*>(h->col), reinterpret_cast<const int4*>(h->cnt), \
+#define FULL_NNZ_ARGS reinterpret_cast<const int4*>(h->row.p), reinterpret_cast<const int4*>(h->col.p), reinterpret_cast<const int4*>(h->cnt.p), \
                       h->nnz, h->sub_rec, s.p[F_LCONTBP], h->nfpb, h->par, h->ln_lut_n, quirk ? 1 : 0, h->d_scalars + 8, h->d_scalars + FULL_BAD
         if (fp.nnz_kernel == FULL_NNZ_L) {   // labels in LDS
             static bool attr_set = false;
@@ -5531,14 +5506,14 @@ static int full_launch(graal_ctx* h, hipStream_t fs)
                 CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_full_nnz_l<FG>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
                 attr_set = true;
             }
-#define FULL_NNZ_L_ARGS reinterpret_cast<const int4*>(h->row), reinterpret_cast<const int4*>(h->col), reinterpret_cast<const int4*>(h->cnt), \
+#define FULL_NNZ_L_ARGS reinterpret_cast<const int4*>(h->row.p), reinterpret_cast<const int4*>(h->col.p), reinterpret_cast<const int4*>(h->cnt.p), \
                         h->nnz, h->sub_lab16, h->n_sub_total, h->sub_rec8, h->sub_rec, s.p[F_LCONTBP], h->nfpb, h->par, h->uniform_accu,        \
                         h->d_scalars + 8, h->d_scalars + FULL_BAD
             k_full_nnz_l<FG><<<fp.nnz_grid, 1024, fp.lab_bytes, fs>>>(FULL_NNZ_L_ARGS);
 #undef FULL_NNZ_L_ARGS
         }
         else if (fp.nnz_kernel == FULL_NNZ_U) {
-#define FULL_NNZ_U_ARGS reinterpret_cast<const int4*>(h->row), reinterpret_cast<const int4*>(h->col), reinterpret_cast<const int4*>(h->cnt), \
+#define FULL_NNZ_U_ARGS reinterpret_cast<const int4*>(h->row.p), reinterpret_cast<const int4*>(h->col.p), reinterpret_cast<const int4*>(h->cnt.p), \
                         h->nnz, h->sub_rec8, h->sub_rec, s.p[F_LCONTBP], h->nfpb, h->par, h->uniform_accu, h->d_scalars + 8, h->d_scalars + FULL_BAD
             k_full_nnz_u<FG><<<fp.nnz_grid, 256, 0, fs>>>(FULL_NNZ_U_ARGS);
 #undef FULL_NNZ_U_ARGS
@@ -5787,7 +5762,7 @@ static int eval_sync(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int
         if (!R) return GRAAL_E_STATE;
         h->res_host = h->res_dev = h->h_res;
         h->publish = false;
-        int rc = graal_eval_candidates_q(h, fA, fB, K, max_id, rank, world, (int64_t*)h->d_qout, nullptr);
+        int rc = graal_eval_candidates_q(h, fA, fB, K, max_id, rank, world, (int64_t*)h->d_qout.p, nullptr);
         if (rc) return rc;
         const int nrc = R->AllReduce(h->d_qout, h->d_qout, (size_t)3 * MAXK * N_OPS, NCCL_INT64, NCCL_SUM, h->nccl_comm, h->stream);
         if (nrc != 0) { h->err = std::string("ncclAllReduce failed: ") + (R->GetErrorString ? R->GetErrorString(nrc) : "?"); return GRAAL_E_HIP; }
@@ -5823,7 +5798,7 @@ static int eval_sync(graal_ctx* h, int32_t fA, const int32_t* fB, int32_t K, int
     h->step_needed_fin = false;
     h->step_needed_geom = false;
     h->rc_evals += 1;
-    int rc = graal_eval_candidates_q(h, fA, fB, K, max_id, rank, world, (int64_t*)h->d_qout, nullptr);
+    int rc = graal_eval_candidates_q(h, fA, fB, K, max_id, rank, world, (int64_t*)h->d_qout.p, nullptr);
     h->publish = false;
     if (rc) return rc;
     const bool launched_mid = h->flat_tried;   // (k_strict_flat went out with the step: it reports whether it was needed)
@@ -6098,8 +6073,7 @@ int graal_upload_distance_ref(graal_ctx* h, const int32_t* init_prev, const int3
     CK(hipSetDevice(h->device));
     std::vector<int4> ref((size_t)n);
     for (int i = 0; i < n; i++) ref[(size_t)i] = make_int4(init_prev[i], init_next[i], init_ori[i], (orientable[i] != 0 ? 1 : 0) | (counted[i] ? 2 : 0));
-    if (h->d_dref) { CK(hipFree(h->d_dref)); h->d_dref = nullptr; }
-    CK(hipMalloc(&h->d_dref, (size_t)n * sizeof(int4)));
+    CK(h->d_dref.alloc(n));
     CK(hipMemcpy(h->d_dref, ref.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice));
     return GRAAL_OK;
 }
@@ -6360,7 +6334,7 @@ int graal_upload_own_obs(graal_ctx* h, const float* own, int32_t n_bins)
     if (h->single_sub || h->has_rep) return GRAAL_OK;      // (no own pixels to correct / not carried with repeats)
     CK(hipSetDevice(h->device));
     if (h->fstream) CK(hipStreamSynchronize(h->fstream));   // (a correction kernel may be reading the old table)
-    if (!h->d_own_obs) CK(hipMalloc(&h->d_own_obs, sizeof(float) * 3 * (size_t)n_bins));
+    if (!h->d_own_obs) CK(h->d_own_obs.alloc(3 * (size_t)n_bins));
     CK(hipMemcpy(h->d_own_obs, own, sizeof(float) * 3 * (size_t)n_bins, hipMemcpyHostToDevice));
     h->own_complete = true;
     h->carry_q = 0; h->carry_bad = true;

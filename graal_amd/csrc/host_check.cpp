@@ -1,11 +1,17 @@
 // host_check.cpp -- TEST ONLY.  Host build of frag_ops.h / strict_sets.h so that the CPU test-suite can compare the engine's
 // layout algebra (mutations, pieces, per-piece transforms, relation flags; the union set of a step, its classes of equal inputs
 // and its work units) with the oracle and with brute force without a GPU; and of the small pure headers beside them (scan_rows.h,
-// step_plan.h, map_shape.h, map_window.h, span_check.h).
+// step_plan.h, map_shape.h, map_window.h, span_check.h); and of dev_buf.h over a counting host allocator (hc_devbuf_*).
 // No likelihood code here and nothing in graal_amd/ loads this library.
 #include <stddef.h>
 #include <stdint.h>
 
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <set>
+#include <utility>
 #include <vector>
 #include <map>
 
@@ -16,6 +22,33 @@
 #include "map_shape.h"
 #include "map_window.h"
 #include "span_check.h"
+
+// dev_buf.h's allocator here: malloc behind a set of the live blocks.  It counts its calls, fails on the fail_at-th allocation (0: never),
+// reports a free of a block that is not live, and hands out memory filled with 0xAB (pinned words must come back zeroed).
+namespace {
+struct HcAlloc {
+    std::set<void*> live;
+    long long allocs = 0, frees = 0, bad_frees = 0, fail_at = 0;
+    size_t peak = 0;
+} g_alloc;
+}
+using devbuf_err = int;
+inline int devbuf_alloc(void** p, size_t bytes, bool)
+{
+    if (++g_alloc.allocs == g_alloc.fail_at) return 2;   // (hipErrorOutOfMemory's value; any non-zero does)
+    *p = malloc(bytes);
+    memset(*p, 0xAB, bytes);
+    g_alloc.live.insert(*p);
+    g_alloc.peak = std::max(g_alloc.peak, g_alloc.live.size());
+    return 0;
+}
+inline void devbuf_free(void* p, bool)
+{
+    g_alloc.frees++;
+    if (!g_alloc.live.erase(p)) { g_alloc.bad_frees++; return; }
+    free(p);
+}
+#include "dev_buf.h"
 
 using namespace graal;
 
@@ -37,9 +70,68 @@ void st(int32_t* const* s, int f, const Rec& r)
     s[F_ID][f] = f; s[F_PREV][f] = r.prev; s[F_NEXT][f] = r.next; s[F_LCONT][f] = r.l_cont; s[F_LCONTBP][f] = r.l_cont_bp;
     s[F_ORI][f] = r.ori; s[F_REP][f] = r.rep; s[F_ACTIV][f] = r.activ; s[F_IDD][f] = r.id_d;
 }
+
+struct HcGroup { long long size = 0; DevBuf<int> a; DevBuf<long long> b; DevBuf<unsigned char> c; DevBuf<void> d; DevBuf<double> e; };
+struct HcRig { DevBuf<int> one; HcGroup g; };
+HcRig* g_rig = new HcRig();
+int hc_state(const void* p) { return !p ? 0 : g_alloc.live.count(const_cast<void*>(p)) ? 1 : 2; }   // null, live, dangling
 } // namespace
 
 extern "C" {
+
+// ---- dev_buf.h (tests/test_dev_buf_cpu.py).  The counters restart (peak at the blocks live now); the fail_at-th allocation from here fails.
+void hc_devbuf_arm(long long fail_at)
+{
+    g_alloc.allocs = g_alloc.frees = g_alloc.bad_frees = 0;
+    g_alloc.fail_at = fail_at;
+    g_alloc.peak = g_alloc.live.size();
+}
+
+// out[5]: allocator calls, frees, frees of a block that was not live, live blocks, peak of live blocks since hc_devbuf_arm
+void hc_devbuf_stats(long long* out)
+{
+    out[0] = g_alloc.allocs; out[1] = g_alloc.frees; out[2] = g_alloc.bad_frees; out[3] = (long long)g_alloc.live.size(); out[4] = (long long)g_alloc.peak;
+}
+
+// One buffer.  what 0: reserve_exact(n), 1: reserve_grow(n), 2: moved into a local that dies here.  Returns the error; out[2]: the count
+// held and the pointer's state (0 null, 1 live, 2 dangling).
+int hc_devbuf_one(int what, long long n, long long* out)
+{
+    DevBuf<int>& b = g_rig->one;
+    int e = 0;
+    if (what == 0) e = b.reserve_exact((size_t)n);
+    else if (what == 1) e = b.reserve_grow((size_t)n);
+    else { DevBuf<int> taken(std::move(b)); }
+    out[0] = (long long)b.count; out[1] = hc_state(b.p);
+    return e;
+}
+
+// The group of five.  what 0: group_exact, 1: group_grow, 2: group_realloc, each to size `want` with counts[5] elements per member.
+// Returns the error; out[6]: the size field and the five pointers' states.
+int hc_devbuf_group(int what, long long want, const long long* counts, long long* out)
+{
+    HcGroup& g = g_rig->g;
+    const size_t c0 = (size_t)counts[0], c1 = (size_t)counts[1], c2 = (size_t)counts[2], c3 = (size_t)counts[3], c4 = (size_t)counts[4];
+    int e;
+    if (what == 0) e = group_exact(g.size, (size_t)want, g.a, c0, g.b, c1, g.c, c2, g.d, c3, g.e, c4);
+    else if (what == 1) e = group_grow(g.size, (size_t)want, g.a, c0, g.b, c1, g.c, c2, g.d, c3, g.e, c4);
+    else e = group_realloc(g.size, (size_t)want, g.a, c0, g.b, c1, g.c, c2, g.d, c3, g.e, c4);
+    out[0] = g.size;
+    out[1] = hc_state(g.a.p); out[2] = hc_state(g.b.p); out[3] = hc_state(g.c.p); out[4] = hc_state(g.d.p); out[5] = hc_state(g.e.p);
+    return e;
+}
+
+// n pinned words: 1 when they come back zeroed (the allocator fills its blocks with 0xAB), and the block is freed again
+int hc_devbuf_pinned_zeroed(int n)
+{
+    PinBuf<long long> w;
+    if (w.alloc((size_t)n)) return -1;
+    for (int i = 0; i < n; i++) if (w[i] != 0) return 0;
+    return 1;
+}
+
+// destroys every owner (the buffer and the group) and starts with fresh ones
+void hc_devbuf_destroy() { delete g_rig; g_rig = new HcRig(); }
 
 // out = apply_move(in) for every fragment; returns the number of stale (unwritten paste) fragments
 int hc_apply_move(int op, int fA, int fB, int max_id, int32_t* const* in, int32_t* const* out, int n)

@@ -1,7 +1,7 @@
 // insert.h -- the likelihood every insertion of a small contig into a junction would add, for every (piece, junction, orientation) the
 // contacts support (graal_insertions).  Included by graal_hip.hip after links.h (it uses LayoutRecs with recs_reserve / recs_build, the
 // records LnSub / LnFrag / LnCtg, ln_slot, ln_run_sum, ln_pair_mass, ln_quirk_pair, ln_mirror_q, k_ln_mirror, k_ln_flag and k_ln_keys, and
-// score_common.h's score_entry, score_exit, STEP_CK, free_null, stream_blocks and CandTable).
+// score_common.h's score_entry, score_exit, STEP_CK, stream_blocks and CandTable).
 //
 // A PIECE is a linear contig P of 1 .. max_piece_frags fragments; a TARGET junction is a fragment f with next[f] = g != -1 of a linear
 // contig T != P.  The inserted layout cuts T between f and g into T1 (.. f) and T2 (g ..) and writes T1, P, T2 as one contig: T1 and T2
@@ -43,49 +43,19 @@ namespace {
 struct InBuf {
     LayoutRecs R;                                                    // (its own instance: nothing shared with graal_end_links' calls)
     CandTable T;
-    long long* rowptr = nullptr; size_t rcap = 0;                    // row offsets (S + 1) when the engine has none for this list
-    unsigned* uns = nullptr;                                         // the contact list is not sorted by row
-    int *srow = nullptr, *pin = nullptr, *perm = nullptr; void* ptmp = nullptr; size_t pcap = 0, ptmp_bytes = 0;   // its sort by row
+    DevBuf<long long> rowptr; size_t rcap = 0;                       // row offsets (S + 1) when the engine has none for this list
+    DevBuf<unsigned> uns;                                            // the contact list is not sorted by row
+    DevBuf<int> srow, pin, perm; DevBuf<void> ptmp; size_t pcap = 0; // its sort by row
     // the candidate table (T), the (P, T) table and the per-candidate arrays grow to the largest size a call needed (within GRAAL_LINKS_MAX_BYTES)
-    unsigned long long* keys2 = nullptr; long long *pf = nullptr, *pm = nullptr; int* pb = nullptr; size_t cap2 = 0;
-    unsigned long long *ko = nullptr, *ks = nullptr; int *vo = nullptr, *vs = nullptr;
-    long long *q = nullptr, *c = nullptr, *sh = nullptr; int *bad = nullptr, *shbad = nullptr, *lead = nullptr, *piece = nullptr, *after = nullptr;
-    unsigned char *rev = nullptr, *st = nullptr;
+    DevBuf<unsigned long long> keys2; DevBuf<long long> pf, pm; DevBuf<int> pb; size_t cap2 = 0;
+    DevBuf<unsigned long long> ko, ks; DevBuf<int> vo, vs;
+    DevBuf<long long> q, c, sh; DevBuf<int> bad, shbad, lead, piece, after;
+    DevBuf<unsigned char> rev, st;
     size_t lcap = 0;
     long long n_out = -1;                                            // -1: no result to fetch
 };
 
-void in_free_rows(InBuf* b)
-{
-    free_null({(void**)&b->rowptr, (void**)&b->uns});
-    b->rcap = 0;
-}
-
-void in_free_pairs(InBuf* b)
-{
-    free_null({(void**)&b->keys2, (void**)&b->pf, (void**)&b->pm, (void**)&b->pb});
-    b->cap2 = 0;
-}
-
-void in_free_cands(InBuf* b)
-{
-    free_null({(void**)&b->ko, (void**)&b->ks, (void**)&b->vo, (void**)&b->vs, (void**)&b->q, (void**)&b->c, (void**)&b->sh, (void**)&b->bad,
-               (void**)&b->shbad, (void**)&b->lead, (void**)&b->piece, (void**)&b->after, (void**)&b->rev, (void**)&b->st});
-    b->lcap = 0;
-}
-
-void in_free_sort(InBuf* b)
-{
-    free_null({(void**)&b->srow, (void**)&b->pin, (void**)&b->perm, &b->ptmp});
-    b->pcap = 0; b->ptmp_bytes = 0;
-}
-
-void in_free(InBuf* b)
-{
-    if (!b) return;
-    recs_free(b->R); table_free(b->T); in_free_rows(b); in_free_pairs(b); in_free_cands(b); in_free_sort(b);
-    delete b;
-}
+void in_free(InBuf* b) { delete b; }
 
 // after k_ln_prep (min_frags 1: a record's elig = linear): a contig record's elig marks a PIECE (linear, 1 .. max_piece_frags fragments)
 __global__ void k_in_piece(int nl, int max_piece, LnCtg* __restrict__ ctg)
@@ -557,12 +527,7 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
     if (n < 1) { B->n_out = 0; return GRAAL_OK; }
     hipStream_t s = h->stream;
     if (const int rc = recs_reserve(h, R)) return rc;
-    if ((size_t)S + 1 != B->rcap) {                                  // (B->rcap stays 0 until both are allocated)
-        in_free_rows(B);
-        CK(hipMalloc(&B->rowptr, sizeof(long long) * (size_t)(S + 1)));
-        CK(hipMalloc(&B->uns, sizeof(unsigned)));
-        B->rcap = (size_t)S + 1;
-    }
+    CK(group_exact(B->rcap, (size_t)S + 1, B->rowptr, (size_t)S + 1, B->uns, 1));
     const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     const int mq = quirk && h->n_ubins > 0;
     const int reach = reach_bp(h);
@@ -602,16 +567,12 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
             STEP_CK(hipcub::DeviceRadixSort::SortPairs(nullptr, pb, (const int*)nullptr, (int*)nullptr, (const int*)nullptr, (int*)nullptr, nz, 0,
                                                      32, s));
             sort_bytes = 3 * sizeof(int) * (size_t)nz + pb;
-            if ((size_t)nz > B->pcap || pb > B->ptmp_bytes) {
-                in_free_sort(B);
-                STEP_CK(hipMalloc(&B->srow, sizeof(int) * (size_t)nz)); STEP_CK(hipMalloc(&B->pin, sizeof(int) * (size_t)nz));
-                STEP_CK(hipMalloc(&B->perm, sizeof(int) * (size_t)nz)); STEP_CK(hipMalloc(&B->ptmp, std::max<size_t>(pb, 1)));
-                B->pcap = (size_t)nz; B->ptmp_bytes = std::max<size_t>(pb, 1);
-            }
+            if ((size_t)nz > B->pcap || pb > B->ptmp.count)
+                STEP_CK(group_realloc(B->pcap, nz, B->srow, nz, B->pin, nz, B->perm, nz, B->ptmp, std::max<size_t>(pb, 1)));
             k_in_iota<<<blocks_for(nz, 256), 256, 0, s>>>(nz, B->pin);
             STEP_CK(hipGetLastError());
-            pb = B->ptmp_bytes;
-            STEP_CK(hipcub::DeviceRadixSort::SortPairs(B->ptmp, pb, h->row, B->srow, B->pin, B->perm, nz, 0, 32, s));
+            pb = B->ptmp.count;
+            STEP_CK(hipcub::DeviceRadixSort::SortPairs(B->ptmp.p, pb, h->row.p, B->srow.p, B->pin.p, B->perm.p, nz, 0, 32, s));
             rows = B->srow;
             perm = B->perm;
         }
@@ -658,25 +619,9 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
             break;
         }
         STEP_CK(table_reserve(T, cap));
-        if (cap2 > B->cap2) {
-            in_free_pairs(B);
-            STEP_CK(hipMalloc(&B->keys2, sizeof(unsigned long long) * cap2));
-            STEP_CK(hipMalloc(&B->pf, sizeof(long long) * cap2));
-            STEP_CK(hipMalloc(&B->pm, sizeof(long long) * cap2));
-            STEP_CK(hipMalloc(&B->pb, sizeof(int) * cap2));
-            B->cap2 = cap2;
-        }
-        if (L > B->lcap) {
-            in_free_cands(B);
-            STEP_CK(hipMalloc(&B->ko, sizeof(unsigned long long) * L)); STEP_CK(hipMalloc(&B->ks, sizeof(unsigned long long) * L));
-            STEP_CK(hipMalloc(&B->vo, sizeof(int) * L)); STEP_CK(hipMalloc(&B->vs, sizeof(int) * L));
-            STEP_CK(hipMalloc(&B->q, sizeof(long long) * L)); STEP_CK(hipMalloc(&B->c, sizeof(long long) * L));
-            STEP_CK(hipMalloc(&B->sh, sizeof(long long) * L));
-            STEP_CK(hipMalloc(&B->bad, sizeof(int) * L)); STEP_CK(hipMalloc(&B->shbad, sizeof(int) * L)); STEP_CK(hipMalloc(&B->lead, sizeof(int) * L));
-            STEP_CK(hipMalloc(&B->piece, sizeof(int) * L)); STEP_CK(hipMalloc(&B->after, sizeof(int) * L));
-            STEP_CK(hipMalloc(&B->rev, L)); STEP_CK(hipMalloc(&B->st, L));
-            B->lcap = L;
-        }
+        STEP_CK(group_grow(B->cap2, cap2, B->keys2, cap2, B->pf, cap2, B->pm, cap2, B->pb, cap2));
+        STEP_CK(group_grow(B->lcap, L, B->ko, L, B->ks, L, B->vo, L, B->vs, L, B->q, L, B->c, L, B->sh, L, B->bad, L, B->shbad, L, B->lead, L,
+                           B->piece, L, B->after, L, B->rev, L, B->st, L));
         STEP_CK(scratch_reserve(T, tneed));
         // (the tables are used at sizes `cap` / `cap2`, whatever their allocations: the probe sequences depend on them)
         STEP_CK(table_clear(T, cap, s));
@@ -695,8 +640,8 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
         }
         k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(T.keys, T.tf, (long long)cap, T.tsel);
         STEP_CK(hipGetLastError());
-        size_t tb = T.stmp_bytes;
-        STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)T.tsel, B->vo, &R.ctr[1],
+        size_t tb = T.stmp.count;
+        STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)T.tsel, B->vo.p, &R.ctr[1],
                                             (int)cap, s));
         STEP_CK(hipMemcpyAsync(ctr, R.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
         STEP_CK(hipMemcpyAsync(&err, R.L.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -711,8 +656,8 @@ int graal_insertions(graal_ctx* h, int32_t max_piece_frags, int64_t* n_out)
         }
         k_ln_keys<<<blocks_for(m, 256), 256, 0, s>>>(m, T.keys, B->vo, B->ko);
         STEP_CK(hipGetLastError());
-        tb = T.stmp_bytes;
-        STEP_CK(hipcub::DeviceRadixSort::SortPairs(T.stmp, tb, B->ko, B->ks, B->vo, B->vs, (int)m, 0, 64, s));
+        tb = T.stmp.count;
+        STEP_CK(hipcub::DeviceRadixSort::SortPairs(T.stmp.p, tb, B->ko.p, B->ks.p, B->vo.p, B->vs.p, (int)m, 0, 64, s));
         k_in_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, B->ks, B->vs, T.tq, T.tc, T.tf, B->q, B->c, B->bad, B->sh, B->shbad, B->piece,
                                                        B->after, B->rev);
         STEP_CK(hipGetLastError());

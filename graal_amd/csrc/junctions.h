@@ -1,6 +1,6 @@
 // junctions.h -- the likelihood each join of the current layout carries, for every junction in one pass (graal_junction_scores).
 // Included by graal_hip.hip after layout_slots.h (it uses Ctx, Stat, centre_kb, rippe, to_q, WAVE_LDS_SYNC, model_math.h,
-// score_common.h's score_entry, score_exit, STEP_CK, free_null, stream_blocks and mass_stripes, and layout_slots.h's LayoutSlots and
+// score_common.h's score_entry, score_exit, STEP_CK, stream_blocks and mass_stripes, and layout_slots.h's LayoutSlots and
 // slot_claim).
 //
 // J[f] = logL(layout) - logL(layout cut between f and next[f]), for f in a LINEAR contig with next[f] != -1, in the engine's exact
@@ -38,26 +38,14 @@ struct JnFrag { int frag, start_bp, len_bp, flags; int n, a0, a1, a2; float c0, 
 struct JnBuf {
     int n = 0, S = 0;
     LayoutSlots L;                                         // (its tmp also serves the two inclusive scans)
-    JnFrag* fr = nullptr;
-    JnSub* sub = nullptr;
-    long long *D = nullptr, *P = nullptr;
-    int *B = nullptr, *PB = nullptr;
-    long long* q = nullptr; unsigned char* st = nullptr;   // the results, fragment-indexed
+    DevBuf<JnFrag> fr;
+    DevBuf<JnSub> sub;
+    DevBuf<long long> D, P;
+    DevBuf<int> B, PB;
+    DevBuf<long long> q; DevBuf<unsigned char> st;         // the results, fragment-indexed
 };
 
-void jn_free_all(JnBuf* b)
-{
-    slots_free(b->L);
-    free_null({(void**)&b->fr, (void**)&b->sub, (void**)&b->D, (void**)&b->P, (void**)&b->B, (void**)&b->PB, (void**)&b->q, (void**)&b->st});
-    b->n = 0; b->S = 0;
-}
-
-void jn_free(JnBuf* b)
-{
-    if (!b) return;
-    jn_free_all(b);
-    delete b;
-}
+void jn_free(JnBuf* b) { delete b; }
 
 // What k_jn_prep and k_rg_prep read of fragment f: its bp interval, orientation and topology, its Stat, and the centres of its (up to
 // three) sub-fragments as the pricing has them.
@@ -298,20 +286,12 @@ int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status)
     JnBuf* J = h->jn;
     hipStream_t s = h->stream;
     if (J->n != n || J->S != S) {
-        jn_free_all(J);
         size_t b2 = 0, b3 = 0;
-        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b2, J->D, J->P, n, s));
-        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b3, J->B, J->PB, n, s));
+        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b2, J->D.p, J->P.p, n, s));
+        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b3, J->B.p, J->PB.p, n, s));
         if (const int rc = slots_reserve(h, J->L, std::max(b2, b3))) return rc;
-        CK(hipMalloc(&J->fr, sizeof(JnFrag) * (size_t)n));
-        CK(hipMalloc(&J->sub, sizeof(JnSub) * (size_t)std::max(S, 1)));
-        CK(hipMalloc(&J->D, sizeof(long long) * (size_t)n));
-        CK(hipMalloc(&J->P, sizeof(long long) * (size_t)n));
-        CK(hipMalloc(&J->B, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&J->PB, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&J->q, sizeof(long long) * (size_t)n));
-        CK(hipMalloc(&J->st, (size_t)n));
-        J->n = n; J->S = S;
+        CK(group_realloc(J->n, n, J->fr, n, J->sub, std::max(S, 1), J->D, n, J->P, n, J->B, n, J->PB, n, J->q, n, J->st, n));
+        J->S = S;
     }
     LayoutSlots& L = J->L;
     const SoaPtr sp = h->soa[h->cur];
@@ -339,10 +319,10 @@ int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status)
             k_jn_quirk<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, L.slot, J->fr, h->nfpb, h->par, reach_bp(h), J->D, J->B);
             STEP_CK(hipGetLastError());
         }
-        size_t tb = L.tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::InclusiveSum(L.tmp, tb, J->D, J->P, n, s));
-        tb = L.tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::InclusiveSum(L.tmp, tb, J->B, J->PB, n, s));
+        size_t tb = L.tmp.count;
+        STEP_CK(hipcub::DeviceScan::InclusiveSum(L.tmp.p, tb, J->D.p, J->P.p, n, s));
+        tb = L.tmp.count;
+        STEP_CK(hipcub::DeviceScan::InclusiveSum(L.tmp.p, tb, J->B.p, J->PB.p, n, s));
         k_jn_out<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, L.slot, J->P, J->PB, J->q, J->st);
         STEP_CK(hipGetLastError());
         STEP_CK(hipMemcpyAsync(q_out, J->q, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, s));

@@ -1,6 +1,6 @@
 // layout_slots.h -- the slot numbering of a layout, built once for every whole-layout scorer: junctions.h, rings.h and maps.h hold a
 // LayoutSlots in their buffers, links.h's LayoutRecs holds one for links, insertions, span moves and excisions.  Included by
-// graal_hip.hip after score_common.h (it uses Ctx, SoaPtr, CK, blocks_for and score_common.h's STEP_CK and free_null).
+// graal_hip.hip after score_common.h (it uses Ctx, SoaPtr, CK, blocks_for and score_common.h's STEP_CK, and dev_buf.h's DevBuf).
 //
 // Number the fragments of the layout by slots: contigs by ascending label, a contig's fragments consecutive, in position order (contig
 // label -> member count -> exclusive scan -> offset + position).  The numbering is built from the layout fields, not taken from the
@@ -13,37 +13,22 @@ namespace {
 // cnt: members per contig label; base: a label's first slot (the exclusive scan of cnt over the n + 3 labels); slot: per fragment, -1 for
 // one without; err[0]: the flags of a corrupt layout (bit 0 a label, bit 1 a position or slot out of range; the callers OR their own bits),
 // err[1]: rings.h's longest contig; tmp: hipCUB's scratch for the scan, and for the owner's own scans when it asked for more.
-// The owners' rule, here and for every set of buffers built on this one: a size field (n) stays 0 until the whole set is allocated.  With
-// free_null, a failed hipMalloc then leaves every pointer valid or null, and the next call frees the valid ones once and starts again.
+// The owners' rule (dev_buf.h) holds for this set and for every set built on it: n stays 0 until the whole set is allocated.
 struct LayoutSlots {
     int n = 0;
-    int *cnt = nullptr, *base = nullptr, *slot = nullptr;
-    unsigned* err = nullptr;
-    void* tmp = nullptr; size_t tmp_bytes = 0;
+    DevBuf<int> cnt, base, slot;
+    DevBuf<unsigned> err;
+    DevBuf<void> tmp;
 };
-
-void slots_free(LayoutSlots& L)
-{
-    free_null({(void**)&L.cnt, (void**)&L.base, (void**)&L.slot, (void**)&L.err, &L.tmp});
-    L.tmp_bytes = 0; L.n = 0;
-}
 
 // Sized to the engine's n, reallocated when it changes or when the owner needs more scratch than there is.
 int slots_reserve(Ctx* h, LayoutSlots& L, size_t own_tmp_bytes = 0)
 {
     const int n = h->n;
-    if (L.n == n && L.tmp_bytes >= own_tmp_bytes) return GRAAL_OK;
-    slots_free(L);
-    CK(hipMalloc(&L.cnt, sizeof(int) * (size_t)(n + 3)));
-    CK(hipMalloc(&L.base, sizeof(int) * (size_t)(n + 3)));
-    CK(hipMalloc(&L.slot, sizeof(int) * (size_t)n));
-    CK(hipMalloc(&L.err, sizeof(unsigned) * 2));
+    if (L.n == n && L.tmp.count >= own_tmp_bytes) return GRAAL_OK;
     size_t tb = 0;
-    CK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, L.cnt, L.base, n + 3, h->stream));
-    tb = std::max(tb, own_tmp_bytes);
-    CK(hipMalloc(&L.tmp, tb));
-    L.tmp_bytes = tb;
-    L.n = n;
+    CK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (int*)nullptr, (int*)nullptr, n + 3, h->stream));
+    CK(group_realloc(L.n, n, L.cnt, n + 3, L.base, n + 3, L.slot, n, L.err, 2, L.tmp, std::max(tb, own_tmp_bytes)));
     return GRAAL_OK;
 }
 
@@ -81,8 +66,8 @@ int slots_count(Ctx* h, LayoutSlots& L)
         STEP_CK(hipMemsetAsync(L.cnt, 0, sizeof(int) * (size_t)(n + 3), s));
         k_jn_count<<<blocks_for(n, 256), 256, 0, s>>>(h->soa[h->cur], n, L.cnt, L.err);
         STEP_CK(hipGetLastError());
-        size_t tb = L.tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp, tb, L.cnt, L.base, n + 3, s));
+        size_t tb = L.tmp.count;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp.p, tb, L.cnt.p, L.base.p, n + 3, s));
     } while (false);
     return rc;
 }

@@ -1,6 +1,6 @@
 // links.h -- the likelihood every join between two contig ends would add, for every pair of ends the contacts support (graal_end_links).
 // Included by graal_hip.hip after rings.h (it uses Ctx, Stat, centre_kb, rippe, to_q, jn_trans, model_math.h, score_common.h's
-// score_entry, score_exit, STEP_CK, free_null, stream_blocks and CandTable, and layout_slots.h's LayoutSlots and slot_claim).
+// score_entry, score_exit, STEP_CK, stream_blocks and CandTable, and layout_slots.h's LayoutSlots and slot_claim).
 // LayoutRecs, below, is shared with insert.h, span_moves.h and excise.h.
 //
 // Ends.  end = 2 * f + side of a LINEAR contig: side 0 its head (position 0), side 1 its tail (position l_cont - 1), f the fragment there.
@@ -87,36 +87,22 @@ __global__ __launch_bounds__(256) void k_ln_prep(SoaPtr s, int n, int min_frags,
 struct LayoutRecs {
     int n = 0, S = 0;
     LayoutSlots L;
-    int* lab = nullptr;
-    LnFrag* fr = nullptr;
-    LnSub* sub = nullptr;
-    LnCtg* ctg = nullptr;
-    long long* mir = nullptr; int* mirbad = nullptr;
-    unsigned long long* ctr = nullptr;   // [0] records counted, [1] listed keys, [2] eligible contigs, [3] insert.h's pair records
+    DevBuf<int> lab;
+    DevBuf<LnFrag> fr;
+    DevBuf<LnSub> sub;
+    DevBuf<LnCtg> ctg;
+    DevBuf<long long> mir; DevBuf<int> mirbad;
+    DevBuf<unsigned long long> ctr;      // [0] records counted, [1] listed keys, [2] eligible contigs, [3] insert.h's pair records
 };
-
-void recs_free(LayoutRecs& R)
-{
-    slots_free(R.L);
-    free_null({(void**)&R.lab, (void**)&R.fr, (void**)&R.sub, (void**)&R.ctg, (void**)&R.mir, (void**)&R.mirbad, (void**)&R.ctr});
-    R.n = 0; R.S = 0;
-}
 
 // Sized to the engine's (n, S), reallocated when they change.
 int recs_reserve(Ctx* h, LayoutRecs& R)
 {
     const int n = h->n, S = h->n_sub_total;
     if (R.n == n && R.S == S) return GRAAL_OK;
-    recs_free(R);
     if (const int rc = slots_reserve(h, R.L)) return rc;
-    CK(hipMalloc(&R.lab, sizeof(int) * (size_t)n));
-    CK(hipMalloc(&R.fr, sizeof(LnFrag) * (size_t)n));
-    CK(hipMalloc(&R.sub, sizeof(LnSub) * (size_t)std::max(S, 1)));
-    CK(hipMalloc(&R.ctg, sizeof(LnCtg) * (size_t)(n + 3)));
-    CK(hipMalloc(&R.mir, sizeof(long long) * (size_t)(n + 3)));
-    CK(hipMalloc(&R.mirbad, sizeof(int) * (size_t)(n + 3)));
-    CK(hipMalloc(&R.ctr, sizeof(unsigned long long) * 4));
-    R.n = n; R.S = S;
+    CK(group_realloc(R.n, n, R.lab, n, R.fr, n, R.sub, std::max(S, 1), R.ctg, n + 3, R.mir, n + 3, R.mirbad, n + 3, R.ctr, 4));
+    R.S = S;
     return GRAAL_OK;
 }
 
@@ -145,36 +131,18 @@ struct LnBuf {
     LayoutRecs R;
     CandTable T;
     // the table (T) and the per-link arrays grow to the largest size a call needed (within GRAAL_LINKS_MAX_BYTES)
-    unsigned long long *ko = nullptr, *ks = nullptr; int *vo = nullptr, *vs = nullptr;
-    long long *q = nullptr, *c = nullptr, *ch = nullptr, *choff = nullptr; int* bad = nullptr; unsigned char* st = nullptr;
-    int *ea = nullptr, *eb = nullptr;
+    DevBuf<unsigned long long> ko, ks; DevBuf<int> vo, vs;
+    DevBuf<long long> q, c, ch, choff; DevBuf<int> bad; DevBuf<unsigned char> st;
+    DevBuf<int> ea, eb;
     size_t lcap = 0;
     long long n_links = -1;                                          // -1: no result to fetch
     // graal_end_links_best: per end (2n) the best Q and partner, the mutual flag, and the mutual links compacted
-    long long* bq = nullptr; int* be = nullptr; unsigned char* bflag = nullptr; int *bsel = nullptr, *mea = nullptr, *meb = nullptr;
-    long long* mq = nullptr; size_t bcap = 0;
+    DevBuf<long long> bq; DevBuf<int> be; DevBuf<unsigned char> bflag; DevBuf<int> bsel, mea, meb;
+    DevBuf<long long> mq; size_t bcap = 0;
     long long n_mutual = -1;                                         // -1: no result to fetch
 };
 
-void ln_free_links(LnBuf* b)
-{
-    free_null({(void**)&b->ko, (void**)&b->ks, (void**)&b->vo, (void**)&b->vs, (void**)&b->q, (void**)&b->c, (void**)&b->bad, (void**)&b->ch,
-               (void**)&b->choff, (void**)&b->st, (void**)&b->ea, (void**)&b->eb});
-    b->lcap = 0;
-}
-
-void ln_free_best(LnBuf* b)
-{
-    free_null({(void**)&b->bq, (void**)&b->be, (void**)&b->bflag, (void**)&b->bsel, (void**)&b->mea, (void**)&b->meb, (void**)&b->mq});
-    b->bcap = 0;
-}
-
-void ln_free(LnBuf* b)
-{
-    if (!b) return;
-    recs_free(b->R); table_free(b->T); ln_free_links(b); ln_free_best(b);
-    delete b;
-}
+void ln_free(LnBuf* b) { delete b; }
 
 __device__ __forceinline__ int ln_k(int meta) { return meta & 3; }
 __device__ __forceinline__ bool ln_fwd(int meta) { return (meta >> 4) & 1; }
@@ -797,16 +765,8 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
         }
         STEP_CK(table_reserve(T, cap));
         STEP_CK(table_clear(T, cap, s));
-        if (L > Lb->lcap) {
-            ln_free_links(Lb);
-            STEP_CK(hipMalloc(&Lb->ko, sizeof(unsigned long long) * L)); STEP_CK(hipMalloc(&Lb->ks, sizeof(unsigned long long) * L));
-            STEP_CK(hipMalloc(&Lb->vo, sizeof(int) * L)); STEP_CK(hipMalloc(&Lb->vs, sizeof(int) * L));
-            STEP_CK(hipMalloc(&Lb->q, sizeof(long long) * L)); STEP_CK(hipMalloc(&Lb->c, sizeof(long long) * L));
-            STEP_CK(hipMalloc(&Lb->ch, sizeof(long long) * L)); STEP_CK(hipMalloc(&Lb->choff, sizeof(long long) * L));
-            STEP_CK(hipMalloc(&Lb->bad, sizeof(int) * L));
-            STEP_CK(hipMalloc(&Lb->ea, sizeof(int) * L)); STEP_CK(hipMalloc(&Lb->eb, sizeof(int) * L)); STEP_CK(hipMalloc(&Lb->st, L));
-            Lb->lcap = L;
-        }
+        STEP_CK(group_grow(Lb->lcap, L, Lb->ko, L, Lb->ks, L, Lb->vo, L, Lb->vs, L, Lb->q, L, Lb->c, L, Lb->ch, L, Lb->choff, L, Lb->bad, L, Lb->ea, L,
+                           Lb->eb, L, Lb->st, L));
         STEP_CK(scratch_reserve(T, tneed));
         // ---- insert pass, selection of the listed slots, sort by key
         if (h->nnz > 0) {
@@ -816,8 +776,8 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
         }
         k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(T.keys, T.tf, (long long)cap, T.tsel);
         STEP_CK(hipGetLastError());
-        size_t tb = T.stmp_bytes;
-        STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)T.tsel, Lb->vo, &R.ctr[1],
+        size_t tb = T.stmp.count;
+        STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)T.tsel, Lb->vo.p, &R.ctr[1],
                                               (int)cap, s));
         STEP_CK(hipMemcpyAsync(C.ctr, R.ctr, sizeof C.ctr, hipMemcpyDeviceToHost, s));
         if ((rc = slots_read_err(h, R.L, C.err)) || C.err) break;
@@ -825,13 +785,13 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
         if (m == 0) break;
         k_ln_keys<<<blocks_for(m, 256), 256, 0, s>>>(m, T.keys, Lb->vo, Lb->ko);
         STEP_CK(hipGetLastError());
-        tb = T.stmp_bytes;
-        STEP_CK(hipcub::DeviceRadixSort::SortPairs(T.stmp, tb, Lb->ko, Lb->ks, Lb->vo, Lb->vs, (int)m, 0, 64, s));
+        tb = T.stmp.count;
+        STEP_CK(hipcub::DeviceRadixSort::SortPairs(T.stmp.p, tb, Lb->ko.p, Lb->ks.p, Lb->vo.p, Lb->vs.p, (int)m, 0, 64, s));
         k_ln_gather<<<blocks_for(m, 256), 256, 0, s>>>(m, Lb->ks, Lb->vs, T.tq, T.tc, T.tf, R.lab, R.ctg, Lb->q, Lb->c, Lb->bad, Lb->ch, Lb->ea,
                                                        Lb->eb);
         STEP_CK(hipGetLastError());
-        tb = T.stmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(T.stmp, tb, Lb->ch, Lb->choff, (int)m, s));
+        tb = T.stmp.count;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(T.stmp, tb, Lb->ch.p, Lb->choff.p, (int)m, s));
         long long last[2] = {0, 0};
         STEP_CK(hipMemcpyAsync(&last[0], Lb->choff + (m - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
         STEP_CK(hipMemcpyAsync(&last[1], Lb->ch + (m - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
@@ -925,14 +885,7 @@ int graal_end_links_best(graal_ctx* h, int32_t min_frags, int32_t* best_end, int
             break;
         }
         STEP_CK(table_reserve(T, cap));
-        if ((size_t)n2 > Lb->bcap) {
-            ln_free_best(Lb);
-            STEP_CK(hipMalloc(&Lb->bq, sizeof(long long) * (size_t)n2)); STEP_CK(hipMalloc(&Lb->be, sizeof(int) * (size_t)n2));
-            STEP_CK(hipMalloc(&Lb->bflag, (size_t)n2)); STEP_CK(hipMalloc(&Lb->bsel, sizeof(int) * (size_t)n2));
-            STEP_CK(hipMalloc(&Lb->mea, sizeof(int) * (size_t)n2)); STEP_CK(hipMalloc(&Lb->meb, sizeof(int) * (size_t)n2));
-            STEP_CK(hipMalloc(&Lb->mq, sizeof(long long) * (size_t)n2));
-            Lb->bcap = (size_t)n2;
-        }
+        STEP_CK(group_grow(Lb->bcap, n2, Lb->bq, n2, Lb->be, n2, Lb->bflag, n2, Lb->bsel, n2, Lb->mea, n2, Lb->meb, n2, Lb->mq, n2));
         STEP_CK(scratch_reserve(T, b_sel));
         STEP_CK(table_clear(T, cap, s));
         // ---- insert pass, then the scores in place: mass, the quirk's passes, mirrors and status
@@ -957,8 +910,8 @@ int graal_end_links_best(graal_ctx* h, int32_t min_frags, int32_t* best_end, int
         k_lb_norm<<<blocks_for(n2, 256), 256, 0, s>>>(n2, Lb->bq, Lb->be);
         k_lb_flag<<<blocks_for(n2, 256), 256, 0, s>>>(n2, Lb->bq, Lb->be, Lb->bflag);
         STEP_CK(hipGetLastError());
-        size_t tb = T.stmp_bytes;
-        STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)Lb->bflag, Lb->bsel,
+        size_t tb = T.stmp.count;
+        STEP_CK(hipcub::DeviceSelect::Flagged(T.stmp, tb, hipcub::CountingInputIterator<int>(0), (const unsigned char*)Lb->bflag, Lb->bsel.p,
                                               &R.ctr[1], (int)n2, s));
         STEP_CK(hipMemcpyAsync(C.ctr, R.ctr, sizeof C.ctr, hipMemcpyDeviceToHost, s));
         if ((rc = slots_read_err(h, R.L, C.err)) || C.err) break;

@@ -41,46 +41,24 @@ struct MwRec { float centre; int accu; int key; int slot; int start_bp; int end_
 struct MwBuf {
     int n = 0, S = 0;                         // the layout buffers' sizes
     LayoutSlots L;                            // (its tmp also serves the scans of nsub and of the RF counts)
-    int *nsub = nullptr, *rank0 = nullptr, *lbp = nullptr, *rank_of = nullptr;
-    JnFrag* fr = nullptr;
-    JnSub* sub = nullptr;
-    MwRec* rec = nullptr;
-    long long *A = nullptr, *A2 = nullptr;    // per rank: the RF count and its square (S + 1 entries, the last 0)
-    long long *PA = nullptr, *PA2 = nullptr;  // their exclusive prefix sums (S + 1 entries)
-    unsigned* cover = nullptr;                // the bitmap over ranks
-    unsigned long long* nbad = nullptr;
-    int win_cap = 0;                          // windows the origin buffer holds
-    int* win = nullptr;                       // [5][win_cap]: u0, v0 in the caller's order; u0, v0, image index sorted by u0
+    DevBuf<int> nsub, rank0, lbp, rank_of;
+    DevBuf<JnFrag> fr;
+    DevBuf<JnSub> sub;
+    DevBuf<MwRec> rec;
+    DevBuf<long long> A, A2;                  // per rank: the RF count and its square (S + 1 entries, the last 0)
+    DevBuf<long long> PA, PA2;                // their exclusive prefix sums (S + 1 entries)
+    DevBuf<unsigned> cover;                   // the bitmap over ranks
+    DevBuf<unsigned long long> nbad;
+    DevBuf<int> win;                          // [5][n_win]: u0, v0 in the caller's order; u0, v0, image index sorted by u0 (it only grows)
     size_t px_cap = 0;                        // pixels the image buffers hold (they only grow)
-    long long *O = nullptr, *E = nullptr;
-    unsigned char* badf = nullptr;
-    float *obs = nullptr, *exp = nullptr, *res = nullptr;
+    DevBuf<long long> O, E;
+    DevBuf<unsigned char> badf;
+    DevBuf<float> obs, exp, res;
     int n_win = 0, pr = 0, pc = 0;
     bool valid = false;                       // the images are those of a finished call
 };
 
-void mw_free_layout(MwBuf* b)
-{
-    slots_free(b->L);
-    free_null({(void**)&b->nsub, (void**)&b->rank0, (void**)&b->lbp, (void**)&b->rank_of, (void**)&b->fr, (void**)&b->sub, (void**)&b->rec,
-               (void**)&b->A, (void**)&b->A2, (void**)&b->PA, (void**)&b->PA2, (void**)&b->cover, (void**)&b->nbad});
-    b->n = 0; b->S = 0;
-}
-
-void mw_free_images(MwBuf* b)
-{
-    free_null({(void**)&b->O, (void**)&b->E, (void**)&b->badf, (void**)&b->obs, (void**)&b->exp, (void**)&b->res});
-    b->px_cap = 0;
-}
-
-void mw_free(MwBuf* b)
-{
-    if (!b) return;
-    mw_free_layout(b);
-    mw_free_images(b);
-    free_null({(void**)&b->win});
-    delete b;
-}
+void mw_free(MwBuf* b) { delete b; }
 
 // per slot: the record of each of its ranks (k_mp_rank has checked that the ranks add up)
 __global__ void k_mw_rec(int n, int S, const JnFrag* __restrict__ fr, const int* __restrict__ rank0, const int* __restrict__ lbp_of,
@@ -332,18 +310,8 @@ int graal_map_windows(graal_ctx* h, int32_t n_win, const int32_t* origin, int32_
     if (bad_pixels_out) *bad_pixels_out = 0;
     hipStream_t s = h->stream;
     const size_t px = (size_t)n_win * (size_t)px_rows * (size_t)px_cols;
-    if (px > M->px_cap) {
-        mw_free_images(M);
-        CK(hipMalloc(&M->O, sizeof(long long) * px));
-        CK(hipMalloc(&M->E, sizeof(long long) * px));
-        CK(hipMalloc(&M->badf, px));
-        CK(hipMalloc(&M->obs, sizeof(float) * px));
-        CK(hipMalloc(&M->exp, sizeof(float) * px));
-        CK(hipMalloc(&M->res, sizeof(float) * px));
-        M->px_cap = px;
-    }
+    CK(group_grow(M->px_cap, px, M->O, px, M->E, px, M->badf, px, M->obs, px, M->exp, px, M->res, px));
     if (n < 1 || S < 1) {                     // no genome: every pixel lies outside it
-        mw_free_layout(M);
         CK(hipMemsetAsync(M->obs, 0, sizeof(float) * px, s));
         CK(hipMemsetAsync(M->exp, 0, sizeof(float) * px, s));
         CK(hipMemsetAsync(M->res, 0, sizeof(float) * px, s));
@@ -353,32 +321,16 @@ int graal_map_windows(graal_ctx* h, int32_t n_win, const int32_t* origin, int32_
     }
     const int words = (S + 31) / 32;
     if (M->n != n || M->S != S) {
-        mw_free_layout(M);
         size_t b2 = 0, b3 = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, M->nsub, M->rank0, n, s));
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b3, M->A, M->PA, S + 1, s));
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (int*)nullptr, (int*)nullptr, n, s));
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b3, (long long*)nullptr, (long long*)nullptr, S + 1, s));
         if (const int rc = slots_reserve(h, M->L, std::max(b2, b3))) return rc;
-        CK(hipMalloc(&M->nsub, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&M->rank0, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&M->lbp, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&M->rank_of, sizeof(int) * (size_t)S));
-        CK(hipMalloc(&M->fr, sizeof(JnFrag) * (size_t)n));
-        CK(hipMalloc(&M->sub, sizeof(JnSub) * (size_t)S));
-        CK(hipMalloc(&M->rec, sizeof(MwRec) * (size_t)S));
-        CK(hipMalloc(&M->A, sizeof(long long) * ((size_t)S + 1)));
-        CK(hipMalloc(&M->A2, sizeof(long long) * ((size_t)S + 1)));
-        CK(hipMalloc(&M->PA, sizeof(long long) * ((size_t)S + 1)));
-        CK(hipMalloc(&M->PA2, sizeof(long long) * ((size_t)S + 1)));
-        CK(hipMalloc(&M->cover, sizeof(unsigned) * (size_t)words));
-        CK(hipMalloc(&M->nbad, sizeof(unsigned long long)));
-        M->n = n; M->S = S;
+        const size_t S1 = (size_t)S + 1;
+        CK(group_realloc(M->n, n, M->nsub, n, M->rank0, n, M->lbp, n, M->rank_of, S, M->fr, n, M->sub, S, M->rec, S, M->A, S1, M->A2, S1, M->PA, S1,
+                         M->PA2, S1, M->cover, words, M->nbad, 1));
+        M->S = S;
     }
-    if (n_win > M->win_cap) {
-        free_null({(void**)&M->win});
-        M->win_cap = 0;
-        CK(hipMalloc(&M->win, sizeof(int) * 5 * (size_t)n_win));
-        M->win_cap = n_win;
-    }
+    CK(M->win.reserve_grow(5 * (size_t)n_win));
     // the origins in the caller's order, and sorted by row origin for the contacts' search
     std::vector<int> hw(5 * (size_t)n_win), order((size_t)n_win);
     for (int w = 0; w < n_win; w++) { hw[(size_t)w] = origin[2 * w]; hw[(size_t)n_win + w] = origin[2 * w + 1]; order[(size_t)w] = w; }
@@ -416,16 +368,16 @@ int graal_map_windows(graal_ctx* h, int32_t n_win, const int32_t* origin, int32_
         k_mp_slots<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, L.slot, h->stat_frag, M->nsub, M->lbp, L.err);
         STEP_CK(hipGetLastError());
         if ((rc = slots_read_err(h, L, err)) || err) break;   // (a corrupt layout or an inactive fragment)
-        size_t tb = L.tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp, tb, M->nsub, M->rank0, n, s));
+        size_t tb = L.tmp.count;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp.p, tb, M->nsub.p, M->rank0.p, n, s));
         // (at bin 1 a pixel is a rank: pix is rank_of_sub, A and A2 are the RF count and its square per rank)
         k_mp_rank<<<blocks_for(n, 256), 256, 0, s>>>(n, S, 1, M->fr, M->nsub, M->rank0, h->d_sub_ids, M->rank_of, M->A, M->A2, L.err);
         STEP_CK(hipGetLastError());
         if ((rc = slots_read_err(h, L, err)) || err) break;   // (the ranks do not cover the sub-fragments: no pixel is to be trusted)
-        tb = L.tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp, tb, M->A, M->PA, S + 1, s));
-        tb = L.tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp, tb, M->A2, M->PA2, S + 1, s));
+        tb = L.tmp.count;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp.p, tb, M->A.p, M->PA.p, S + 1, s));
+        tb = L.tmp.count;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp.p, tb, M->A2.p, M->PA2.p, S + 1, s));
         k_mw_rec<<<blocks_for(n, 256), 256, 0, s>>>(n, S, M->fr, M->rank0, M->lbp, M->rec);
         STEP_CK(hipGetLastError());
         if (h->nnz > 0) {

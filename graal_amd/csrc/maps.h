@@ -32,40 +32,20 @@ struct MpTile { int start_bp, n, r0, fwd; float c0, c1, c2; int a0, a1, a2, pad0
 struct MpBuf {
     int n = 0, S = 0;                         // the layout buffers' sizes
     LayoutSlots L;                            // (its tmp also serves the scan of nsub)
-    int *nsub = nullptr, *rank0 = nullptr, *lbp = nullptr, *pix = nullptr;
-    JnFrag* fr = nullptr;
-    JnSub* sub = nullptr;
-    long long *A = nullptr, *A2 = nullptr;    // per pixel: sum of RF counts, sum of their squares
-    unsigned long long* nbad = nullptr;
+    DevBuf<int> nsub, rank0, lbp, pix;
+    DevBuf<JnFrag> fr;
+    DevBuf<JnSub> sub;
+    DevBuf<long long> A, A2;                  // per pixel: sum of RF counts, sum of their squares
+    DevBuf<unsigned long long> nbad;
     size_t px_cap = 0;                        // pixels the image buffers hold (they only grow)
-    long long *O = nullptr, *E = nullptr;
-    unsigned* badmap = nullptr;
-    float *obs = nullptr, *exp = nullptr, *res = nullptr;
+    DevBuf<long long> O, E;
+    DevBuf<unsigned> badmap;
+    DevBuf<float> obs, exp, res;
     int m = 0, bin = 1;
     bool valid = false;                       // the images are those of a finished call
 };
 
-void mp_free_layout(MpBuf* b)
-{
-    slots_free(b->L);
-    free_null({(void**)&b->nsub, (void**)&b->rank0, (void**)&b->lbp, (void**)&b->pix, (void**)&b->fr, (void**)&b->sub, (void**)&b->A,
-               (void**)&b->A2, (void**)&b->nbad});
-    b->n = 0; b->S = 0;
-}
-
-void mp_free_images(MpBuf* b)
-{
-    free_null({(void**)&b->O, (void**)&b->E, (void**)&b->badmap, (void**)&b->obs, (void**)&b->exp, (void**)&b->res});
-    b->px_cap = 0;
-}
-
-void mp_free(MpBuf* b)
-{
-    if (!b) return;
-    mp_free_layout(b);
-    mp_free_images(b);
-    delete b;
-}
+void mp_free(MpBuf* b) { delete b; }
 
 // per fragment: its slot's sub-fragment count and contig length; an inactive fragment is flagged (err bit 4)
 __global__ void k_mp_slots(SoaPtr s, int n, const int* __restrict__ slot_of, const Stat* __restrict__ stat, int* __restrict__ nsub,
@@ -292,32 +272,14 @@ int graal_layout_maps(graal_ctx* h, int32_t max_px, int32_t* m_out, int32_t* bin
     if (n < 1 || S < 1) { M->m = 0; M->bin = 1; M->valid = true; if (m_out) *m_out = 0; return GRAAL_OK; }
     hipStream_t s = h->stream;
     if (M->n != n || M->S != S) {
-        mp_free_layout(M);
         size_t b2 = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, M->nsub, M->rank0, n, s));
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (int*)nullptr, (int*)nullptr, n, s));
         if (const int rc = slots_reserve(h, M->L, b2)) return rc;
-        CK(hipMalloc(&M->nsub, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&M->rank0, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&M->lbp, sizeof(int) * (size_t)n));
-        CK(hipMalloc(&M->pix, sizeof(int) * (size_t)S));
-        CK(hipMalloc(&M->fr, sizeof(JnFrag) * (size_t)n));
-        CK(hipMalloc(&M->sub, sizeof(JnSub) * (size_t)S));
-        CK(hipMalloc(&M->A, sizeof(long long) * (size_t)S));      // (m <= S)
-        CK(hipMalloc(&M->A2, sizeof(long long) * (size_t)S));
-        CK(hipMalloc(&M->nbad, sizeof(unsigned long long)));
-        M->n = n; M->S = S;
+        CK(group_realloc(M->n, n, M->nsub, n, M->rank0, n, M->lbp, n, M->pix, S, M->fr, n, M->sub, S, M->A, S /* m <= S */, M->A2, S, M->nbad, 1));
+        M->S = S;
     }
     const size_t px = (size_t)m * (size_t)m, bad_words = (px + 31) / 32;
-    if (px > M->px_cap) {
-        mp_free_images(M);
-        CK(hipMalloc(&M->O, sizeof(long long) * px));
-        CK(hipMalloc(&M->E, sizeof(long long) * px));
-        CK(hipMalloc(&M->badmap, sizeof(unsigned) * bad_words));
-        CK(hipMalloc(&M->obs, sizeof(float) * px));
-        CK(hipMalloc(&M->exp, sizeof(float) * px));
-        CK(hipMalloc(&M->res, sizeof(float) * px));
-        M->px_cap = px;
-    }
+    CK(group_grow(M->px_cap, px, M->O, px, M->E, px, M->badmap, bad_words, M->obs, px, M->exp, px, M->res, px));
     LayoutSlots& L = M->L;
     const SoaPtr sp = h->soa[h->cur];
     int rc = GRAAL_OK;
@@ -340,8 +302,8 @@ int graal_layout_maps(graal_ctx* h, int32_t max_px, int32_t* m_out, int32_t* bin
         k_mp_slots<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, L.slot, h->stat_frag, M->nsub, M->lbp, L.err);
         STEP_CK(hipGetLastError());
         if ((rc = slots_read_err(h, L, err)) || err) break;   // (a corrupt layout or an inactive fragment)
-        size_t tb = L.tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp, tb, M->nsub, M->rank0, n, s));
+        size_t tb = L.tmp.count;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(L.tmp.p, tb, M->nsub.p, M->rank0.p, n, s));
         k_mp_rank<<<blocks_for(n, 256), 256, 0, s>>>(n, S, bin, M->fr, M->nsub, M->rank0, h->d_sub_ids, M->pix, M->A, M->A2, L.err);
         STEP_CK(hipGetLastError());
         if ((rc = slots_read_err(h, L, err)) || err) break;   // (the ranks do not cover the sub-fragments: no pixel is to be trusted)

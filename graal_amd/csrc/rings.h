@@ -1,7 +1,7 @@
 // rings.h -- the likelihood closing each linear contig into a ring, or opening each ring at its wrap, would add, for every contig in one
 // pass (graal_ring_scores); and the commit that closes contigs (graal_close_rings).
 // Included by graal_hip.hip after junctions.h (it uses Ctx, Stat, rippe, to_q, WAVE_LDS_SYNC, model_math.h, score_common.h's score_entry,
-// layout_refusal, score_exit, STEP_CK, free_null, stream_blocks, mass_stripes and layout_replaced, layout_slots.h's LayoutSlots and
+// layout_refusal, score_exit, STEP_CK, stream_blocks, mass_stripes and layout_replaced, layout_slots.h's LayoutSlots and
 // slot_claim, and junctions.h's jn_load and jn_run_sum).
 //
 // R[c] = logL(layout with contig c in the OTHER topology, every coordinate kept) - logL(layout), in the engine's exact arithmetic.  Nothing
@@ -46,33 +46,14 @@ struct RgPre { float K, k3, norm_circ; };
 struct RgBuf {
     int n = 0, S = 0;
     LayoutSlots L;                                              // (err[1]: the longest contig)
-    RgFrag* fr = nullptr;
-    RgSub* sub = nullptr;
-    long long *sum = nullptr, *con = nullptr, *bad = nullptr;   // per slot, used at a contig's last slot (one allocation of 3n)
-    long long *q = nullptr, *c = nullptr; unsigned char* st = nullptr;   // the results, fragment-indexed
-    int *mark = nullptr, *head = nullptr, *tail = nullptr, *d_frag = nullptr, *d_st = nullptr; int n_lab = 0, fcap = 0;   // graal_close_rings
+    DevBuf<RgFrag> fr;
+    DevBuf<RgSub> sub;
+    DevBuf<long long> sum; long long *con = nullptr, *bad = nullptr;   // per slot, used at a contig's last slot (one allocation of 3n)
+    DevBuf<long long> q, c; DevBuf<unsigned char> st;           // the results, fragment-indexed
+    DevBuf<int> mark, head, tail, d_frag, d_st; int n_lab = 0, fcap = 0;   // graal_close_rings
 };
 
-void rg_free_score(RgBuf* b)
-{
-    slots_free(b->L);
-    free_null({(void**)&b->fr, (void**)&b->sub, (void**)&b->sum, (void**)&b->q, (void**)&b->c, (void**)&b->st});
-    b->con = b->bad = nullptr;
-    b->n = 0; b->S = 0;
-}
-
-void rg_free_close(RgBuf* b)
-{
-    free_null({(void**)&b->mark, (void**)&b->head, (void**)&b->tail, (void**)&b->d_frag, (void**)&b->d_st});
-    b->n_lab = 0; b->fcap = 0;
-}
-
-void rg_free(RgBuf* b)
-{
-    if (!b) return;
-    rg_free_score(b); rg_free_close(b);
-    delete b;
-}
+void rg_free(RgBuf* b) { delete b; }
 
 // the parameter-only factors of rippe_circ, by its own operations
 __device__ __forceinline__ RgPre rg_pre(const Par& p)
@@ -318,15 +299,9 @@ int graal_ring_scores(graal_ctx* h, int64_t* q_out, int64_t* contacts_out, uint8
     RgBuf* R = h->rg;
     hipStream_t s = h->stream;
     if (R->n != n || R->S != S) {
-        rg_free_score(R);
         if (const int rc = slots_reserve(h, R->L)) return rc;
-        CK(hipMalloc(&R->fr, sizeof(RgFrag) * (size_t)n));
-        CK(hipMalloc(&R->sub, sizeof(RgSub) * (size_t)std::max(S, 1)));
-        CK(hipMalloc(&R->sum, sizeof(long long) * 3 * (size_t)n));
-        CK(hipMalloc(&R->q, sizeof(long long) * (size_t)n));
-        CK(hipMalloc(&R->c, sizeof(long long) * (size_t)n));
-        CK(hipMalloc(&R->st, (size_t)n));
-        R->n = n; R->S = S;
+        CK(group_realloc(R->n, n, R->fr, n, R->sub, std::max(S, 1), R->sum, 3 * (size_t)n, R->q, n, R->c, n, R->st, n));
+        R->S = S;
     }
     R->con = R->sum + n; R->bad = R->sum + 2 * (size_t)n;
     LayoutSlots& L = R->L;
@@ -376,13 +351,8 @@ int graal_close_rings(graal_ctx* h, int32_t n_rings, const int32_t* frag, int32_
     if (!h->rg) h->rg = new RgBuf();
     RgBuf* R = h->rg;
     if (R->n_lab != NL || n_rings > R->fcap) {
-        rg_free_close(R);
-        CK(hipMalloc(&R->mark, sizeof(int) * (size_t)(NL + 1)));     // (+ 1: the error word)
-        CK(hipMalloc(&R->head, sizeof(int) * (size_t)NL));
-        CK(hipMalloc(&R->tail, sizeof(int) * (size_t)NL));
-        CK(hipMalloc(&R->d_frag, sizeof(int) * (size_t)n_rings));
-        CK(hipMalloc(&R->d_st, sizeof(int) * (size_t)n_rings));
-        R->n_lab = NL; R->fcap = n_rings;
+        CK(group_realloc(R->n_lab, NL, R->mark, NL + 1 /* the error word */, R->head, NL, R->tail, NL, R->d_frag, n_rings, R->d_st, n_rings));
+        R->fcap = n_rings;
     }
     CK(hipMemcpyAsync(R->d_frag, frag, sizeof(int) * (size_t)n_rings, hipMemcpyHostToDevice, s));
     CK(hipMemsetAsync(R->d_st, 0, sizeof(int) * (size_t)n_rings, s));

@@ -1,6 +1,6 @@
 // score_common.h -- what the whole-layout scorers and commits (junctions.h, rings.h, links.h, insert.h, span_moves.h, excise.h, edit.h,
 // maps.h) share on the host side: the entry refusals and the common exits, the step check of their do { ... } while (false) frames, the
-// free-and-null of a pointer list, the two launch sizes they all compute, the tail of a commit that rewrote the layout, and the
+// two launch sizes they all compute, the tail of a commit that rewrote the layout, and the
 // open-addressing candidate table.
 // Included by graal_hip.hip before layout_slots.h and junctions.h (it uses Ctx, fail, CK, refresh and sync_args).
 #pragma once
@@ -10,13 +10,6 @@ namespace {
 // One step of a scorer's `do { ... } while (false)` frame: a HIP error is recorded in h->err, `rc` becomes GRAAL_E_HIP and the frame is left
 // (the caller drains the stream and returns rc).  Needs `h` and an `int rc` in scope.
 #define STEP_CK(call) { const hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = hipGetErrorString(e_); rc = GRAAL_E_HIP; break; } }
-
-// Every pointer is freed AND nulled: under the owners' rule (stated on LayoutSlots, layout_slots.h) a failed hipMalloc leaves nothing to
-// free twice.
-void free_null(std::initializer_list<void**> ptrs)
-{
-    for (void** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
-}
 
 // What every whole-layout call `fn` refuses before it touches the device.  missing: what the call needs uploaded and does not find (null:
 // nothing is missing); the scorers and graal_close_rings differ in that alone.
@@ -81,43 +74,20 @@ int layout_replaced(Ctx* h, int from_buffer)
 // The candidate table: open addressing keyed by a 64-bit key (ln_slot), per slot a Q sum, a contact count, flags and the selection byte of
 // DeviceSelect::Flagged; and the hipCUB scratch of the passes behind it.  Both grow to the largest size a call needed.
 struct CandTable {
-    unsigned long long* keys = nullptr; long long *tq = nullptr, *tc = nullptr; int* tf = nullptr; unsigned char* tsel = nullptr; size_t cap = 0;
-    void* stmp = nullptr; size_t stmp_bytes = 0;
+    DevBuf<unsigned long long> keys; DevBuf<long long> tq, tc; DevBuf<int> tf; DevBuf<unsigned char> tsel; size_t cap = 0;
+    DevBuf<void> stmp;
 };
 constexpr unsigned long long TABLE_SLOT_BYTES = 8 + 8 + 8 + 4 + 1;   // key, q, contacts, flags, selection byte
 
 // slots for an upper bound of the distinct keys (load factor <= 2/3)
 inline unsigned long long table_cap(unsigned long long bound) { return bound + bound / 2 + 64; }
 
-void table_free(CandTable& T)
-{
-    free_null({(void**)&T.keys, (void**)&T.tq, (void**)&T.tc, (void**)&T.tf, (void**)&T.tsel, &T.stmp});
-    T.cap = 0; T.stmp_bytes = 0;
-}
-
 hipError_t table_reserve(CandTable& T, unsigned long long cap)
 {
-    if (cap <= T.cap) return hipSuccess;
-    free_null({(void**)&T.keys, (void**)&T.tq, (void**)&T.tc, (void**)&T.tf, (void**)&T.tsel});
-    T.cap = 0;
-    hipError_t e = hipMalloc(&T.keys, sizeof(unsigned long long) * cap);
-    if (e == hipSuccess) e = hipMalloc(&T.tq, sizeof(long long) * cap);
-    if (e == hipSuccess) e = hipMalloc(&T.tc, sizeof(long long) * cap);
-    if (e == hipSuccess) e = hipMalloc(&T.tf, sizeof(int) * cap);
-    if (e == hipSuccess) e = hipMalloc(&T.tsel, cap);
-    if (e == hipSuccess) T.cap = cap;
-    return e;
+    return group_grow(T.cap, cap, T.keys, cap, T.tq, cap, T.tc, cap, T.tf, cap, T.tsel, cap);
 }
 
-hipError_t scratch_reserve(CandTable& T, size_t bytes)
-{
-    if (bytes <= T.stmp_bytes) return hipSuccess;
-    free_null({&T.stmp});
-    T.stmp_bytes = 0;
-    const hipError_t e = hipMalloc(&T.stmp, bytes);
-    if (e == hipSuccess) T.stmp_bytes = bytes;
-    return e;
-}
+hipError_t scratch_reserve(CandTable& T, size_t bytes) { return T.stmp.reserve_grow(bytes); }
 
 // (the table is used at size `cap`, whatever its allocation: the probe sequence depends on it)
 hipError_t table_clear(CandTable& T, unsigned long long cap, hipStream_t s)

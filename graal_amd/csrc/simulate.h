@@ -36,25 +36,19 @@ struct SimRec { float centre; int label; int accu; int lbp; };   // label -1: in
 
 struct SimBuf {
     int S = 0;
-    SimRec* rec = nullptr;
-    unsigned long long *key = nullptr, *key_s = nullptr;
-    int *val = nullptr, *order = nullptr, *inv = nullptr, *cnt = nullptr;
-    float* sc = nullptr; int* sl = nullptr;
-    long long* off = nullptr;
-    void* tmp = nullptr; size_t tmp_bytes = 0;
-    int2* ent = nullptr; long long ent_cap = 0;
-    int *orow = nullptr, *ocol = nullptr, *ocnt = nullptr; long long out_cap = 0;
-    unsigned* err = nullptr;
+    DevBuf<SimRec> rec;
+    DevBuf<unsigned long long> key, key_s;
+    DevBuf<int> val, order, inv, cnt;
+    DevBuf<float> sc; DevBuf<int> sl;
+    DevBuf<long long> off;
+    DevBuf<void> tmp;
+    DevBuf<int2> ent;                                   // grows (at least 1024 entries)
+    DevBuf<int> orow, ocol, ocnt; long long out_cap = 0;
+    DevBuf<unsigned> err;
     long long nnz = -1;
 };
 
-void sim_free(SimBuf* b)
-{
-    if (!b) return;
-    void* p[] = {b->rec, b->key, b->key_s, b->val, b->order, b->inv, b->cnt, b->sc, b->sl, b->off, b->tmp, b->ent, b->orow, b->ocol, b->ocnt, b->err};
-    for (void* q : p) if (q) (void)hipFree(q);
-    delete b;
-}
+void sim_free(SimBuf* b) { delete b; }
 
 // ---- Philox4x32-10 and the uniform stream
 __device__ __forceinline__ uint4 philox4x32(uint4 c, unsigned k0, unsigned k1)
@@ -369,30 +363,12 @@ int graal_simulate_contacts(graal_ctx* h, uint64_t seed, int64_t* nnz_out)
     B->nnz = -1;
     hipStream_t s = h->stream;
     if (B->S != S) {
-        // (every pointer is freed AND nulled, and B->S stays 0 until the whole set is allocated: a failed hipMalloc leaves nothing that a
-        // later call or sim_free would free twice)
-        B->S = 0;
-        void** p[] = {(void**)&B->rec, (void**)&B->key, (void**)&B->key_s, (void**)&B->val, (void**)&B->order, (void**)&B->inv, (void**)&B->cnt,
-                      (void**)&B->sc, (void**)&B->sl, (void**)&B->off, &B->tmp, (void**)&B->err};
-        for (void** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
-        B->tmp_bytes = 0;
-        CK(hipMalloc(&B->rec, sizeof(SimRec) * (size_t)S));
-        CK(hipMalloc(&B->key, sizeof(unsigned long long) * (size_t)S));
-        CK(hipMalloc(&B->key_s, sizeof(unsigned long long) * (size_t)S));
-        CK(hipMalloc(&B->val, sizeof(int) * (size_t)S));
-        CK(hipMalloc(&B->order, sizeof(int) * (size_t)S));
-        CK(hipMalloc(&B->inv, sizeof(int) * (size_t)S));
-        CK(hipMalloc(&B->cnt, sizeof(int) * (size_t)S));
-        CK(hipMalloc(&B->sc, sizeof(float) * (size_t)S));
-        CK(hipMalloc(&B->sl, sizeof(int) * (size_t)S));
-        CK(hipMalloc(&B->off, sizeof(long long) * (size_t)(S + 1)));
-        CK(hipMalloc(&B->err, sizeof(unsigned)));
         size_t b1 = 0, b2 = 0;
-        CK(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, B->key, B->key_s, B->val, B->order, S, 0, 64, s));
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, B->cnt, B->off, S, s));
-        CK(hipMalloc(&B->tmp, std::max(b1, b2)));
-        B->tmp_bytes = std::max(b1, b2);
-        B->S = S;
+        CK(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int*)nullptr, (int*)nullptr,
+                                              S, 0, 64, s));
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (int*)nullptr, (long long*)nullptr, S, s));
+        CK(group_realloc(B->S, S, B->rec, S, B->key, S, B->key_s, S, B->val, S, B->order, S, B->inv, S, B->cnt, S, B->sc, S, B->sl, S, B->off, S + 1,
+                         B->err, 1, B->tmp, std::max(b1, b2)));
     }
     int amax = 1;
     for (int b = 0; b < h->n_bins; b++)
@@ -400,37 +376,24 @@ int graal_simulate_contacts(graal_ctx* h, uint64_t seed, int64_t* nnz_out)
     // (rows without a sub-fragment record -- none: every sub-fragment id belongs to one bin slot, graal_upload_subfrags checks it)
     k_sim_prep<<<blocks_for(n, 256), 256, 0, s>>>(n, h->geo, h->stat_frag, h->d_sub_ids, h->soa[h->cur].p[F_LCONTBP], B->rec, B->key, B->val);
     CK(hipGetLastError());
-    size_t tb = B->tmp_bytes;
-    CK(hipcub::DeviceRadixSort::SortPairs(B->tmp, tb, B->key, B->key_s, B->val, B->order, S, 0, 64, s));
+    size_t tb = B->tmp.count;
+    CK(hipcub::DeviceRadixSort::SortPairs(B->tmp.p, tb, B->key.p, B->key_s.p, B->val.p, B->order.p, S, 0, 64, s));
     k_sim_sorted<<<blocks_for(S, 256), 256, 0, s>>>(S, B->order, B->rec, B->inv, B->sc, B->sl);
     CK(hipGetLastError());
     CK(hipMemsetAsync(B->err, 0, sizeof(unsigned), s));
     k_sim_rows<false><<<S, SIM_BLOCK, 0, s>>>(S, B->rec, B->order, B->inv, B->sc, B->sl, h->par, h->nfpb, amax, (unsigned long long)seed, B->cnt,
                                                nullptr, nullptr, B->err);
     CK(hipGetLastError());
-    tb = B->tmp_bytes;
-    CK(hipcub::DeviceScan::ExclusiveSum(B->tmp, tb, B->cnt, B->off, S, s));
+    tb = B->tmp.count;
+    CK(hipcub::DeviceScan::ExclusiveSum(B->tmp.p, tb, B->cnt.p, B->off.p, S, s));
     k_sim_off_tail<<<1, 1, 0, s>>>(S, B->cnt, B->off);
     CK(hipGetLastError());
     long long nnz = 0;
     CK(hipMemcpyAsync(&nnz, B->off + S, sizeof(long long), hipMemcpyDeviceToHost, s));
     CK(hipStreamSynchronize(s));
-    if (nnz > B->ent_cap) {
-        if (B->ent) (void)hipFree(B->ent);
-        B->ent = nullptr; B->ent_cap = 0;
-        const long long c = std::max<long long>(nnz, 1024);
-        CK(hipMalloc(&B->ent, sizeof(int2) * (size_t)c));
-        B->ent_cap = c;
-    }
-    if (nnz > B->out_cap) {
-        for (int** p : {&B->orow, &B->ocol, &B->ocnt}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        B->out_cap = 0;
-        const long long c = std::max<long long>(nnz, 1024);
-        CK(hipMalloc(&B->orow, sizeof(int) * (size_t)c));
-        CK(hipMalloc(&B->ocol, sizeof(int) * (size_t)c));
-        CK(hipMalloc(&B->ocnt, sizeof(int) * (size_t)c));
-        B->out_cap = c;
-    }
+    const size_t out = (size_t)std::max<long long>(nnz, 1024);
+    if ((size_t)nnz > B->ent.count) CK(B->ent.alloc(out));
+    if (nnz > B->out_cap) CK(group_realloc(B->out_cap, out, B->orow, out, B->ocol, out, B->ocnt, out));
     if (nnz > 0) {
         k_sim_rows<true><<<S, SIM_BLOCK, 0, s>>>(S, B->rec, B->order, B->inv, B->sc, B->sl, h->par, h->nfpb, amax, (unsigned long long)seed,
                                                   B->cnt, B->off, B->ent, B->err);

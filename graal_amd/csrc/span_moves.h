@@ -2,7 +2,7 @@
 // reversals (graal_block_flips) and swaps of two adjacent runs (graal_block_swaps); and the frame of every call that scores spans
 // (span_moves: these two and excise.h's graal_block_excisions).  Included by graal_hip.hip after insert.h (it uses LayoutRecs with
 // recs_reserve / recs_build, slots_read_err, the records LnFrag / LnCtg, ln_run_sum, ln_block_add, ln_mirror_q, span_check.h and
-// score_common.h's score_entry, score_exit, STEP_CK, free_null and stream_blocks).
+// score_common.h's score_entry, score_exit, STEP_CK and stream_blocks).
 //
 // Span k = the fragments of one linear contig at slots first .. last, bp interval [s0, e1).  The breakpoint sm behind slot mid splits it
 // into the runs X = first .. mid and Y = mid + 1 .. last (lx = sm - s0, ly = e1 - sm).  The moved layout puts Y in front of X:
@@ -62,33 +62,15 @@ static_assert(sizeof(SpanSub) == SPAN_SUB_BYTES, "a sub-fragment's record is two
 // One set per handle for the three calls: each call rebuilds what it reads.
 struct SpanBuf {
     LayoutRecs R;
-    void* sub = nullptr; int n = 0, S = 0;                            // per sub-fragment: a SpanSub, or excise.h's ExSub (32 bytes each)
-    int *first = nullptr, *mid = nullptr, *last = nullptr; SpanInfo* info = nullptr; SpanRec* rec = nullptr;
-    long long *qb = nullptr, *cb = nullptr, *q = nullptr, *c = nullptr, *ne = nullptr, *noff = nullptr; int* bad = nullptr; int4* nx = nullptr;
-    unsigned char* st = nullptr;
-    void* tmp = nullptr; size_t tmp_bytes = 0;
+    DevBuf<SpanSub> sub; int n = 0, S = 0;                            // per sub-fragment: a SpanSub, or excise.h's ExSub (32 bytes each)
+    DevBuf<int> first, mid, last; DevBuf<SpanInfo> info; DevBuf<SpanRec> rec;
+    DevBuf<long long> qb, cb, q, c, ne, noff; DevBuf<int> bad; DevBuf<int4> nx;
+    DevBuf<unsigned char> st;
+    DevBuf<void> tmp;
     size_t bcap = 0;                                                  // spans the per-span arrays hold
 };
 
-void sp_free_spans(SpanBuf* b)
-{
-    free_null({(void**)&b->first, (void**)&b->mid, (void**)&b->last, (void**)&b->info, (void**)&b->rec, (void**)&b->qb, (void**)&b->cb,
-               (void**)&b->q, (void**)&b->c, (void**)&b->bad, (void**)&b->ne, (void**)&b->noff, (void**)&b->nx, (void**)&b->st, &b->tmp});
-    b->bcap = 0; b->tmp_bytes = 0;
-}
-
-void sp_free_subs(SpanBuf* b)
-{
-    free_null({&b->sub});
-    b->n = 0; b->S = 0;
-}
-
-void sp_free(SpanBuf* b)
-{
-    if (!b) return;
-    recs_free(b->R); sp_free_subs(b); sp_free_spans(b);
-    delete b;
-}
+void sp_free(SpanBuf* b) { delete b; }
 
 // mid: null for a call without a breakpoint (mid = last)
 __global__ void k_sp_gather(int nb, int n, const int* __restrict__ first, const int* __restrict__ mid, const int* __restrict__ last,
@@ -417,8 +399,8 @@ int sp_unit_total(graal_ctx* h, SpanBuf* B, int m, long long& total)
     hipStream_t s = h->stream;
     int rc = GRAAL_OK;
     do {
-        size_t tb = B->tmp_bytes;
-        STEP_CK(hipcub::DeviceScan::ExclusiveSum(B->tmp, tb, B->ne, B->noff, m + 1, s));
+        size_t tb = B->tmp.count;
+        STEP_CK(hipcub::DeviceScan::ExclusiveSum(B->tmp.p, tb, B->ne.p, B->noff.p, m + 1, s));
         STEP_CK(hipMemcpyAsync(&total, B->noff + m, sizeof(long long), hipMemcpyDeviceToHost, s));
         STEP_CK(hipStreamSynchronize(s));
     } while (false);
@@ -480,24 +462,15 @@ int span_moves(graal_ctx* h, const SpanKind& K, int nb, const int32_t* first, co
     hipStream_t s = h->stream;
     if (const int rc = recs_reserve(h, R)) return rc;
     if (B->n != n || B->S != S) {
-        sp_free_subs(B);
-        CK(hipMalloc(&B->sub, SPAN_SUB_BYTES * (size_t)std::max(S, 1)));
-        B->n = n; B->S = S;
+        CK(group_realloc(B->n, n, B->sub, std::max(S, 1)));
+        B->S = S;
     }
     if ((size_t)nb > B->bcap) {                                       // (grows to the largest call of any kind)
-        sp_free_spans(B);
         const size_t cap = (size_t)nb + 1;
-        for (int** p : {&B->first, &B->mid, &B->last, &B->bad}) CK(hipMalloc(p, sizeof(int) * cap));
-        for (long long** p : {&B->qb, &B->cb, &B->q, &B->c, &B->ne, &B->noff}) CK(hipMalloc(p, sizeof(long long) * cap));
-        CK(hipMalloc(&B->info, sizeof(SpanInfo) * cap));
-        CK(hipMalloc(&B->rec, sizeof(SpanRec) * cap));
-        CK(hipMalloc(&B->nx, sizeof(int4) * cap));
-        CK(hipMalloc(&B->st, cap));
         size_t tb = 0;
-        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, B->ne, B->noff, (int)cap, s));
-        CK(hipMalloc(&B->tmp, tb));
-        B->tmp_bytes = tb;
-        B->bcap = (size_t)nb;
+        CK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (long long*)nullptr, (long long*)nullptr, (int)cap, s));
+        CK(group_realloc(B->bcap, nb, B->first, cap, B->mid, cap, B->last, cap, B->bad, cap, B->qb, cap, B->cb, cap, B->q, cap, B->c, cap, B->ne, cap,
+                         B->noff, cap, B->info, cap, B->rec, cap, B->nx, cap, B->st, cap, B->tmp, tb));
     }
     int rc = GRAAL_OK;
     unsigned err = 0;
@@ -509,7 +482,7 @@ int span_moves(graal_ctx* h, const SpanKind& K, int nb, const int32_t* first, co
         STEP_CK(hipMemcpyAsync(B->first, first, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
         if (mid) STEP_CK(hipMemcpyAsync(B->mid, mid, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
         STEP_CK(hipMemcpyAsync(B->last, last, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
-        k_sp_gather<<<blocks_for(nb, 256), 256, 0, s>>>(nb, n, B->first, mid ? B->mid : nullptr, B->last, R.L.slot, R.lab, R.fr, R.ctg, B->info);
+        k_sp_gather<<<blocks_for(nb, 256), 256, 0, s>>>(nb, n, B->first, mid ? B->mid.p : nullptr, B->last, R.L.slot, R.lab, R.fr, R.ctg, B->info);
         STEP_CK(hipGetLastError());
         STEP_CK(hipMemcpyAsync(info.data(), B->info, sizeof(SpanInfo) * (size_t)nb, hipMemcpyDeviceToHost, s));
         if ((rc = slots_read_err(h, R.L, err)) || err) break;
