@@ -3327,8 +3327,9 @@ __global__ __launch_bounds__(256) void k_fin(const DevArgs* __restrict__ A, FinA
                     const Geo gy = geo[fy];
                     const End Y = end_xf(gy, same ? tk.xp : tk.xq);
                     YTile y;
-                    y.start_bp = Y.start_bp; y.len_bp = gy.len_bp; y.flags = (Y.fwd ? 1 : 0) | (Y.circ << 1); y.label = Y.label;
+                    y.start_bp = Y.start_bp; y.len_bp = gy.len_bp; y.label = Y.label;
                     y.lbp = Y.lbp; y.st = stat[fy];
+                    y.flags = (Y.fwd ? 1 : 0) | (Y.circ << 1) | (y.st.n == 0 ? 4 : 0);   // (bit 2: a copy of a repeated bin, no sub-fragments here)
                     const Ctr cy = centres_of(Y.start_bp, Y.fwd, y.st);
                     y.c0 = cy.c0; y.c1 = cy.c1; y.c2 = cy.c2;
                     tile[lane] = y;
@@ -3345,7 +3346,9 @@ __global__ __launch_bounds__(256) void k_fin(const DevArgs* __restrict__ A, FinA
                                          : (x_below ? Y.start_bp - (X.start_bp + gx.len_bp) : X.start_bp - (Y.start_bp + y.len_bp));
                     if (gap > reach_bp) { done = true; continue; }
                     long long q1;
-                    if (!multi_sub) {   // one sub-fragment per bin: pair_mass_q_c without its slot loops (the same operations on the same values)
+                    if (!multi_sub && (sx.n == 0 || (y.flags & 4))) {
+                        q1 = 0;         // (a copy of a repeated bin: pair_mass_q_c's slot loops run over nothing; its pixels are priced by k_rep_delta)
+                    } else if (!multi_sub) {   // one sub-fragment per bin: pair_mass_q_c without its slot loops (the same operations on the same values)
                         const float norm = fa.norm_u >= 0.0f ? fa.norm_u : (float)(sx.a0 * y.st.a0) / nfpb;
                         const float sd = fabsf(y.c0 - cx.c0);
                         const float ex = (X.circ == 1 ? rippe_circ(sd, (float)X.lbp / 1000.0f, par) : rippe(sd, par)) * norm;
