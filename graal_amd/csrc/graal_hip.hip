@@ -4149,6 +4149,8 @@ void sim_free(SimBuf* b);
 
 struct JnBuf;                  // junctions.h: graal_junction_scores' buffers
 void jn_free(JnBuf* b);
+struct JbBuf;                  // junction_boot.h: graal_junction_bootstrap's buffers
+void jb_free(JbBuf* b);
 
 struct LnBuf;                  // links.h: graal_end_links' buffers and results
 void ln_free(LnBuf* b);
@@ -4378,6 +4380,7 @@ struct Ctx : CtxMem {
     float timing[4] = {0, 0, 0, 0};
     SimBuf* sim = nullptr;        // graal_simulate_contacts' buffers (simulate.h; allocated by its first call)
     JnBuf* jn = nullptr;          // graal_junction_scores' buffers (junctions.h; allocated by its first call)
+    JbBuf* jb = nullptr;          // graal_junction_bootstrap's buffers (junction_boot.h; allocated by its first call)
     LnBuf* ln = nullptr;          // graal_end_links' buffers and its last result (links.h; allocated by its first call)
     EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
     InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
@@ -4943,6 +4946,7 @@ void graal_destroy(graal_ctx* h)
         // every buffer, while the handle's device is current: the scorers' sets, then all of CtxMem at once
         sim_free(h->sim); h->sim = nullptr;
         jn_free(h->jn); h->jn = nullptr;
+        jb_free(h->jb); h->jb = nullptr;
         ln_free(h->ln); h->ln = nullptr;
         ed_free(h->ed); h->ed = nullptr;
         in_free(h->ins); h->ins = nullptr;
@@ -6378,6 +6382,7 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "score_common.h"
 #include "layout_slots.h"
 #include "junctions.h"
+#include "junction_boot.h"
 #include "rings.h"
 #include "links.h"
 #include "insert.h"

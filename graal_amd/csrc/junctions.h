@@ -28,6 +28,9 @@
 //   k_jn_quirk -- only with GRAAL_MODE_REF_TRANS_ACCU and bins of mixed RF counts: straddling pairs beyond the window, whose trans price
 //                 differs from their (v_inter) cis price by the indexing alone;
 //   two inclusive scans (D, and a count of non-finite terms laid out the same way), then k_jn_out: J and a status byte per fragment.
+// The host side is cut into the steps jn_reserve / jn_prepare / jn_add_contacts / jn_add_mass / jn_scan_d / jn_finish, and a contact's
+// term per unit count is jn_contact_unit: junction_boot.h (graal_junction_bootstrap) runs the same steps around its own kernels and
+// prices a resampled count with the same function.
 #pragma once
 
 namespace {
@@ -113,6 +116,29 @@ __device__ __forceinline__ void jn_bad(int* __restrict__ B, int i, int j)
     atomicAdd(&B[i < j ? j : i], -1);
 }
 
+// What one observed count of a contact between sub-fragments A and Bs adds to the junctions it straddles: t = ln ex_cis - ln ex_trans.
+// False when the contact has no term (another contig, a ring, one fragment, or beyond the window with the same indexing).  Shared by
+// k_jn_nnz and junction_boot.h's k_jb_nnz, which multiply it by the count and by a resampled count.
+__device__ __forceinline__ bool jn_contact_unit(const JnSub& A, const JnSub& Bs, const JnFrag* __restrict__ fr, float nfpb, const Par& par,
+                                                int quirk, double& t)
+{
+    if (!(A.slot >= 0 && Bs.slot >= 0 && A.label == Bs.label && A.slot != Bs.slot)) return false;
+    const int lo_a = A.accu & 0xffff, lo_b = Bs.accu & 0xffff;
+    const int prod = lo_a * lo_b;
+    int prod_t = prod;
+    if (quirk && ((A.accu >> 16) != lo_a || (Bs.accu >> 16) != lo_b)) {
+        const int bin_a = fr[A.slot].frag, bin_b = fr[Bs.slot].frag;
+        prod_t = bin_a < bin_b ? (A.accu >> 16) * lo_b : lo_a * (Bs.accu >> 16);
+    }
+    const float sd = fabsf(Bs.centre - A.centre);
+    // (at |d| >= d_max rippe is v_inter exactly: the cis and trans prices are the same float32 value unless the indexing differs)
+    if (sd >= par.d_max && prod_t == prod && par.v_inter >= 0.0f) return false;
+    const float ex = rippe(sd, par) * ((float)prod / nfpb);
+    const float et = par.v_inter * ((float)prod_t / nfpb);
+    t = mm_ln(ex) - mm_ln(et);
+    return true;
+}
+
 __global__ __launch_bounds__(256) void k_jn_nnz(const int* __restrict__ row, const int* __restrict__ col, const int* __restrict__ cnt,
                                                 long long nnz, const JnSub* __restrict__ sub, const JnFrag* __restrict__ fr, float nfpb, Par par,
                                                 int quirk, long long* __restrict__ D, int* __restrict__ B)
@@ -127,24 +153,12 @@ __global__ __launch_bounds__(256) void k_jn_nnz(const int* __restrict__ row, con
         if (k < nnz) {
             const JnSub A = sub[row[k]], Bs = sub[col[k]];
             ka = A.slot; kb = Bs.slot;
-            if (A.slot >= 0 && Bs.slot >= 0 && A.label == Bs.label && A.slot != Bs.slot) {
-                const int lo_a = A.accu & 0xffff, lo_b = Bs.accu & 0xffff;
-                const int prod = lo_a * lo_b;
-                int prod_t = prod;
-                if (quirk && ((A.accu >> 16) != lo_a || (Bs.accu >> 16) != lo_b)) {
-                    const int bin_a = fr[A.slot].frag, bin_b = fr[Bs.slot].frag;
-                    prod_t = bin_a < bin_b ? (A.accu >> 16) * lo_b : lo_a * (Bs.accu >> 16);
-                }
-                const float sd = fabsf(Bs.centre - A.centre);
-                // (at |d| >= d_max rippe is v_inter exactly: the cis and trans prices are the same float32 value unless the indexing differs)
-                if (!(sd >= par.d_max && prod_t == prod && par.v_inter >= 0.0f)) {
-                    const float ex = rippe(sd, par) * ((float)prod / nfpb);
-                    const float et = par.v_inter * ((float)prod_t / nfpb);
-                    const double ob = (double)__int_as_float(cnt[k]);
-                    const long long q = to_q(ob * (mm_ln(ex) - mm_ln(et)));
-                    if (q == Q_BAD) jn_bad(B, A.slot, Bs.slot);
-                    else c = A.slot < Bs.slot ? q : -q;
-                }
+            double t;
+            if (jn_contact_unit(A, Bs, fr, nfpb, par, quirk, t)) {
+                const double ob = (double)__int_as_float(cnt[k]);
+                const long long q = to_q(ob * t);
+                if (q == Q_BAD) jn_bad(B, A.slot, Bs.slot);
+                else c = A.slot < Bs.slot ? q : -q;
             }
         }
         long long vr = c, vc = -c;
@@ -272,6 +286,105 @@ __global__ void k_jn_out(SoaPtr s, int n, const int* __restrict__ slot_of, const
     st_out[f] = st;
 }
 
+// The steps of graal_junction_scores, each on the engine's stream; junction_boot.h runs the same ones around its own.
+inline int jn_quirk(const Ctx* h) { return (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0; }
+
+// The handle's JnBuf, sized to the engine's n and S; own_tmp: scratch bytes the caller's own scans need of L.tmp.
+int jn_reserve(Ctx* h, size_t own_tmp = 0)
+{
+    const int n = h->n, S = h->n_sub_total;
+    if (!h->jn) h->jn = new JnBuf();
+    JnBuf* J = h->jn;
+    size_t b2 = 0, b3 = 0;
+    CK(hipcub::DeviceScan::InclusiveSum(nullptr, b2, J->D.p, J->P.p, n, h->stream));
+    CK(hipcub::DeviceScan::InclusiveSum(nullptr, b3, J->B.p, J->PB.p, n, h->stream));
+    if (const int rc = slots_reserve(h, J->L, std::max(std::max(b2, b3), own_tmp))) return rc;
+    if (J->n != n || J->S != S) {
+        CK(group_realloc(J->n, n, J->fr, n, J->sub, std::max(S, 1), J->D, n, J->P, n, J->B, n, J->PB, n, J->q, n, J->st, n));
+        J->S = S;
+    }
+    return GRAAL_OK;
+}
+
+// D and B cleared, the slots and the records built; err: the flags of a corrupt layout (the caller leaves when they are set).
+int jn_prepare(Ctx* h, JnBuf* J, unsigned& err)
+{
+    const int n = h->n;
+    hipStream_t s = h->stream;
+    LayoutSlots& L = J->L;
+    int rc = GRAAL_OK;
+    do {
+        STEP_CK(hipMemsetAsync(J->D, 0, sizeof(long long) * (size_t)n, s));
+        STEP_CK(hipMemsetAsync(J->B, 0, sizeof(int) * (size_t)n, s));
+        STEP_CK(hipMemsetAsync(J->fr, 0, sizeof(JnFrag) * (size_t)n, s));   // (a slot no fragment claims -- a corrupt layout -- reads as empty)
+        if ((rc = slots_count(h, L))) break;
+        k_jn_prep<<<blocks_for(n, 256), 256, 0, s>>>(h->soa[h->cur], n, h->stat_frag, h->d_sub_ids, L.cnt, L.base, L.slot, J->fr, J->sub, L.err);
+        STEP_CK(hipGetLastError());
+        rc = slots_read_err(h, L, err);
+    } while (false);
+    return rc;
+}
+
+// the contacts' terms, added to D (and B)
+int jn_add_contacts(Ctx* h, JnBuf* J)
+{
+    int rc = GRAAL_OK;
+    do {
+        if (h->nnz < 1) break;
+        k_jn_nnz<<<stream_blocks(h->nnz), 256, 0, h->stream>>>(h->row, h->col, h->cnt, h->nnz, J->sub, J->fr, h->nfpb, h->par, jn_quirk(h), J->D, J->B);
+        STEP_CK(hipGetLastError());
+    } while (false);
+    return rc;
+}
+
+// the mass terms, added to D (and B)
+int jn_add_mass(Ctx* h, JnBuf* J)
+{
+    const int n = h->n, quirk = jn_quirk(h);
+    hipStream_t s = h->stream;
+    int rc = GRAAL_OK;
+    do {
+        const int lc = std::min(std::max(std::max(h->max_lcont, h->lcont_bound), 1), n);
+        const int n_tiles = (n + 63) / 64;
+        const int Sw = mass_stripes(lc);
+        k_jn_mass<<<(n_tiles * Sw + 3) / 4, 256, 0, s>>>(n, J->fr, h->nfpb, h->par, quirk, reach_bp(h), Sw, J->D, J->B);
+        STEP_CK(hipGetLastError());
+        if (quirk && h->n_ubins) {
+            k_jn_quirk<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, J->L.slot, J->fr, h->nfpb, h->par, reach_bp(h), J->D, J->B);
+            STEP_CK(hipGetLastError());
+        }
+    } while (false);
+    return rc;
+}
+
+// D's inclusive scan into P (n entries)
+int jn_scan_d(Ctx* h, JnBuf* J, long long* P)
+{
+    int rc = GRAAL_OK;
+    do {
+        size_t tb = J->L.tmp.count;
+        STEP_CK(hipcub::DeviceScan::InclusiveSum(J->L.tmp.p, tb, J->D.p, P, h->n, h->stream));
+    } while (false);
+    return rc;
+}
+
+// B's inclusive scan, then J and the status byte per fragment from it and from J->P, and their copies to the host queued behind
+int jn_finish(Ctx* h, JnBuf* J, int64_t* q_out, uint8_t* status)
+{
+    const int n = h->n;
+    hipStream_t s = h->stream;
+    int rc = GRAAL_OK;
+    do {
+        size_t tb = J->L.tmp.count;
+        STEP_CK(hipcub::DeviceScan::InclusiveSum(J->L.tmp.p, tb, J->B.p, J->PB.p, n, s));
+        k_jn_out<<<blocks_for(n, 256), 256, 0, s>>>(h->soa[h->cur], n, J->L.slot, J->P, J->PB, J->q, J->st);
+        STEP_CK(hipGetLastError());
+        STEP_CK(hipMemcpyAsync(q_out, J->q, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, s));
+        STEP_CK(hipMemcpyAsync(status, J->st, (size_t)n, hipMemcpyDeviceToHost, s));
+    } while (false);
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -280,54 +393,18 @@ int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status)
 {
     if (!h || !q_out || !status) return GRAAL_E_ARG;
     if (const int rc = score_entry(h, "graal_junction_scores")) return rc;
-    const int n = h->n, S = h->n_sub_total;
-    if (n < 1) return GRAAL_OK;
-    if (!h->jn) h->jn = new JnBuf();
+    if (h->n < 1) return GRAAL_OK;
+    if (const int rc = jn_reserve(h)) return rc;
     JnBuf* J = h->jn;
-    hipStream_t s = h->stream;
-    if (J->n != n || J->S != S) {
-        size_t b2 = 0, b3 = 0;
-        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b2, J->D.p, J->P.p, n, s));
-        CK(hipcub::DeviceScan::InclusiveSum(nullptr, b3, J->B.p, J->PB.p, n, s));
-        if (const int rc = slots_reserve(h, J->L, std::max(b2, b3))) return rc;
-        CK(group_realloc(J->n, n, J->fr, n, J->sub, std::max(S, 1), J->D, n, J->P, n, J->B, n, J->PB, n, J->q, n, J->st, n));
-        J->S = S;
-    }
-    LayoutSlots& L = J->L;
-    const SoaPtr sp = h->soa[h->cur];
-    const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     int rc = GRAAL_OK;
     unsigned err = 0;
     do {
-        STEP_CK(hipMemsetAsync(J->D, 0, sizeof(long long) * (size_t)n, s));
-        STEP_CK(hipMemsetAsync(J->B, 0, sizeof(int) * (size_t)n, s));
-        STEP_CK(hipMemsetAsync(J->fr, 0, sizeof(JnFrag) * (size_t)n, s));   // (a slot no fragment claims -- a corrupt layout -- reads as empty)
-        if ((rc = slots_count(h, L))) break;
-        k_jn_prep<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, h->stat_frag, h->d_sub_ids, L.cnt, L.base, L.slot, J->fr, J->sub, L.err);
-        STEP_CK(hipGetLastError());
-        if ((rc = slots_read_err(h, L, err)) || err) break;
-        if (h->nnz > 0) {
-            k_jn_nnz<<<stream_blocks(h->nnz), 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, J->sub, J->fr, h->nfpb, h->par, quirk, J->D, J->B);
-            STEP_CK(hipGetLastError());
-        }
-        const int lc = std::min(std::max(std::max(h->max_lcont, h->lcont_bound), 1), n);
-        const int n_tiles = (n + 63) / 64;
-        const int Sw = mass_stripes(lc);
-        k_jn_mass<<<(n_tiles * Sw + 3) / 4, 256, 0, s>>>(n, J->fr, h->nfpb, h->par, quirk, reach_bp(h), Sw, J->D, J->B);
-        STEP_CK(hipGetLastError());
-        if (quirk && h->n_ubins) {
-            k_jn_quirk<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, L.slot, J->fr, h->nfpb, h->par, reach_bp(h), J->D, J->B);
-            STEP_CK(hipGetLastError());
-        }
-        size_t tb = L.tmp.count;
-        STEP_CK(hipcub::DeviceScan::InclusiveSum(L.tmp.p, tb, J->D.p, J->P.p, n, s));
-        tb = L.tmp.count;
-        STEP_CK(hipcub::DeviceScan::InclusiveSum(L.tmp.p, tb, J->B.p, J->PB.p, n, s));
-        k_jn_out<<<blocks_for(n, 256), 256, 0, s>>>(sp, n, L.slot, J->P, J->PB, J->q, J->st);
-        STEP_CK(hipGetLastError());
-        STEP_CK(hipMemcpyAsync(q_out, J->q, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipMemcpyAsync(status, J->st, (size_t)n, hipMemcpyDeviceToHost, s));
-        STEP_CK(hipStreamSynchronize(s));
+        if ((rc = jn_prepare(h, J, err)) || err) break;
+        if ((rc = jn_add_contacts(h, J))) break;
+        if ((rc = jn_add_mass(h, J))) break;
+        if ((rc = jn_scan_d(h, J, J->P))) break;
+        if ((rc = jn_finish(h, J, q_out, status))) break;
+        STEP_CK(hipStreamSynchronize(h->stream));
     } while (false);
     return score_exit(h, "graal_junction_scores", rc, nullptr, err);
 }

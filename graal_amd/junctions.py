@@ -6,12 +6,20 @@ positive J means the data prefer the join; a join with J <= 0 is one the data wo
 
     junction_table(sampler_or_engine)   -- the junctions in contig order, as a dict of columns (see COLUMNS)
     write_junctions_tsv(path, table)    -- one tab-separated row per junction, with a header line
+
+Junction support (graal_junction_bootstrap): a Poisson bootstrap of the read pairs -- every contact's count redrawn as Poisson(count), n_rep
+times, all replicates in one GPU call -- says how sure a score's sign is: `support` is the fraction of the replicates in which the
+junction still scores above the threshold.
+
+    support_table(sampler_or_engine, seed, n_rep, threshold=0.0)   -- junction_table's columns plus SUPPORT_COLUMNS[len(COLUMNS):]
+    write_support_tsv(path, table)                                 -- the same as a TSV file
 """
 import numpy as np
 
 from .lib import Engine, JUNCTION_CIRCULAR, JUNCTION_END, JUNCTION_NONFINITE, JUNCTION_VALID
 
 COLUMNS = ("contig", "position", "left_frag", "right_frag", "left_ori", "right_ori", "join_bp", "score")
+SUPPORT_COLUMNS = COLUMNS + ("support", "boot_mean", "boot_min", "boot_max")
 STATUS_NAMES = {JUNCTION_VALID: "valid", JUNCTION_END: "contig_end", JUNCTION_CIRCULAR: "circular", JUNCTION_NONFINITE: "nonfinite"}
 
 
@@ -50,14 +58,36 @@ def junction_table(sampler_or_engine):
     return table_from(e.download_frags(), score)
 
 
-def write_junctions_tsv(path, table):
-    """Write `table` (junction_table's dict) as a TSV file with a header line; scores with 17 significant digits, NaN as 'nan'."""
+def _write_tsv(path, table, columns, n_int):
     n = len(table["score"])
     with open(path, "w") as fh:
-        fh.write("\t".join(COLUMNS) + "\n")
+        fh.write("\t".join(columns) + "\n")
         for i in range(n):
-            row = [str(int(table[c][i])) for c in COLUMNS[:-1]]
-            s = float(table["score"][i])
-            row.append("nan" if not np.isfinite(s) else repr(s))
+            row = [str(int(table[c][i])) for c in columns[:n_int]]
+            for c in columns[n_int:]:
+                s = float(table[c][i])
+                row.append("nan" if not np.isfinite(s) else repr(s))
             fh.write("\t".join(row) + "\n")
     return n
+
+
+def write_junctions_tsv(path, table):
+    """Write `table` (junction_table's dict) as a TSV file with a header line; scores with 17 significant digits, NaN as 'nan'."""
+    return _write_tsv(path, table, COLUMNS, len(COLUMNS) - 1)
+
+
+def support_table(sampler_or_engine, seed, n_rep, threshold=0.0):
+    """The junctions of the engine's current layout in contig order with their bootstrap support: table_from's columns plus `support`
+    (the fraction of the n_rep replicates scoring above `threshold`), `boot_mean`, `boot_min` and `boot_max` of the replicate scores
+    (NaN where there is no score).  A function of (layout, contacts, seed, n_rep, threshold) alone."""
+    e = _engine(sampler_or_engine)
+    b = e.junction_bootstrap(seed, n_rep, threshold)
+    t = table_from(e.download_frags(), b["J"])
+    f = t["left_frag"]
+    t.update({"support": b["support"][f], "boot_mean": b["mean"][f], "boot_min": b["min"][f], "boot_max": b["max"][f]})
+    return t
+
+
+def write_support_tsv(path, table):
+    """Write `table` (support_table's dict) as a TSV file with a header line SUPPORT_COLUMNS; floats as write_junctions_tsv writes them."""
+    return _write_tsv(path, table, SUPPORT_COLUMNS, len(COLUMNS) - 1)

@@ -51,7 +51,7 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_upload_subfrags", "graal_upload_repeats", "graal_upload_contacts", "graal_upload_contacts_f32", "graal_upload_frags", "graal_download_frags",
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_set_scan_path", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
-           "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_end_links", "graal_end_links_fetch",
+           "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_junction_bootstrap", "graal_end_links", "graal_end_links_fetch",
            "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
            "graal_block_swaps", "graal_block_excisions", "graal_ring_scores", "graal_close_rings",
            "graal_layout_maps", "graal_layout_maps_fetch", "graal_map_windows", "graal_map_windows_fetch",
@@ -139,6 +139,8 @@ def load():
         L.graal_simulate_contacts.argtypes = [ctypes.c_void_p, ctypes.c_uint64, _i64p]
         L.graal_simulate_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i32p, ctypes.c_int64]
         L.graal_junction_scores.argtypes = [ctypes.c_void_p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
+        L.graal_junction_bootstrap.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int64, _i64p,
+                                               ctypes.POINTER(ctypes.c_uint8), _i32p, _i64p, _i64p, _i64p, _i64p]
         L.graal_end_links.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i64p]
         L.graal_end_links_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
         L.graal_end_links_best.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i64p, _i64p]
@@ -419,6 +421,41 @@ class Engine:
         self._ck(self._L.graal_junction_scores(self._h, q.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
                  "graal_junction_scores")
         return q, st
+
+    def junction_bootstrap(self, seed, n_rep, threshold=0.0, replicates=False):
+        """graal_junction_bootstrap as floats: a dict of J (the data's own score), status, support (the fraction of the n_rep Poisson-
+        bootstrap replicates of the contacts in which the junction scores above `threshold`, in [0, 1]), mean, min and max of the
+        replicate scores, indexed by fragment, NaN where the status is not JUNCTION_VALID; with replicates=True also the matrix
+        `replicates` float64[n_rep, n].  Replicate r is a function of (layout, contacts, seed, r) alone.  Same preconditions and refusals
+        as junction_scores.  Leaves the step state alone."""
+        t = self.junction_bootstrap_q(seed, n_rep, int(round(float(threshold) * Q_SCALE)), replicates)
+        ok = t["status"] == JUNCTION_VALID
+        out = {"J": np.where(ok, t["q"].astype(np.float64) / Q_SCALE, np.nan), "status": t["status"],
+               "support": np.where(ok, t["support"].astype(np.float64) / float(n_rep), np.nan),
+               "mean": np.where(ok, t["q_sum"].astype(np.float64) / float(n_rep) / Q_SCALE, np.nan),
+               "min": np.where(ok, t["q_min"].astype(np.float64) / Q_SCALE, np.nan),
+               "max": np.where(ok, t["q_max"].astype(np.float64) / Q_SCALE, np.nan)}
+        if replicates:
+            out["replicates"] = np.where(ok[None, :], t["q_rep"].astype(np.float64) / Q_SCALE, np.nan)
+        return out
+
+    def junction_bootstrap_q(self, seed, n_rep, threshold_q=0, replicates=False):
+        """The same in Q: a dict of q int64[n], status uint8[n], support int32[n] (a count of replicates), q_sum, q_min, q_max int64[n]
+        and, with replicates=True, q_rep int64[n_rep, n]; zeros where the status is not JUNCTION_VALID."""
+        n, n_rep = int(self.n), int(n_rep)
+        q, q_sum, q_min, q_max = (np.zeros(n, dtype=np.int64) for _ in range(4))
+        st = np.zeros(n, dtype=np.uint8)
+        sup = np.zeros(n, dtype=np.int32)
+        rep = np.zeros((max(n_rep, 0), n), dtype=np.int64) if replicates and 1 <= n_rep <= 1024 else None
+        self._ck(self._L.graal_junction_bootstrap(self._h, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), n_rep, int(threshold_q),
+                                                  q.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                  sup.ctypes.data_as(_i32p), q_sum.ctypes.data_as(_i64p), q_min.ctypes.data_as(_i64p),
+                                                  q_max.ctypes.data_as(_i64p), rep.ctypes.data_as(_i64p) if rep is not None else None),
+                 "graal_junction_bootstrap")
+        out = {"q": q, "status": st, "support": sup, "q_sum": q_sum, "q_min": q_min, "q_max": q_max}
+        if replicates:
+            out["q_rep"] = rep
+        return out
 
     def end_links(self, min_frags=1):
         """graal_end_links: the pairs of contig ends the contacts support, as numpy columns (end_a int32, end_b int32, score float64,

@@ -52,6 +52,12 @@ def main(argv=None):
     ap.add_argument("--scaffold", action="store_true", help="after the explode and before the MCMC, join mutual-best contig ends round by "
                                                             "round (graal_amd.scaffold); writes scaffold.tsv")
     ap.add_argument("--scaffold-min-score", type=float, default=0.0, help="with --scaffold: only joins scoring above this (default 0)")
+    ap.add_argument("--junction-support", type=int, default=0, metavar="R",
+                    help="write junction_support.tsv into the output folder: junctions.tsv's columns plus the bootstrap support of every "
+                         "join of the final layout -- the fraction of R Poisson resamplings of the contacts (1 .. 1024, one GPU call) in "
+                         "which the join still scores above 0 -- and the mean, smallest and largest resampled score")
+    ap.add_argument("--junction-support-seed", type=int, default=None, help="with --junction-support: the seed of the resampling "
+                                                                            "(default: --seed, or 0 when that is unset)")
     ap.add_argument("--polish", action="store_true", help="before the outputs, cut the final layout's junctions scoring below "
                                                           "--polish-cut-below and rejoin the pieces (graal_amd.scaffold); writes polish.tsv")
     ap.add_argument("--polish-cut-below", type=float, default=0.0, help="with --polish: the junction score below which a join is cut (default 0)")
@@ -112,6 +118,8 @@ def main(argv=None):
     ap.add_argument("--maps-junction-px", type=int, default=256, help="with --maps-junctions: the windows' side in pixels (default 256)")
     ap.add_argument("--maps-junction-bin", type=int, default=1, help="with --maps-junctions: sub-fragments per pixel (default 1)")
     args = ap.parse_args(argv)
+    if not 0 <= args.junction_support <= 1024:
+        raise SystemExit("--junction-support must be in 0 .. 1024")
     if args.maps_junctions < 0 or (args.maps_junctions and not (1 <= args.maps_junction_px <= 4096 and args.maps_junction_bin >= 1)):
         raise SystemExit("--maps-junctions must be >= 0, --maps-junction-px in 1 .. 4096 and --maps-junction-bin >= 1")
     if args.maps and not 1 <= args.maps_max_px <= 4096:
@@ -210,6 +218,11 @@ def main(argv=None):
     if args.junctions:
         from . import junctions
         junctions.write_junctions_tsv(os.path.join(out, "junctions.tsv"), junctions.junction_table(smp))
+    if args.junction_support:
+        from . import junctions
+        boot_seed = args.junction_support_seed if args.junction_support_seed is not None else (args.seed if args.seed is not None else 0)
+        junctions.write_support_tsv(os.path.join(out, "junction_support.tsv"),
+                                    junctions.support_table(smp, boot_seed, args.junction_support))
     if args.links:
         from . import links
         links.write_links_tsv(os.path.join(out, "links.tsv"), links.link_table(smp, args.links_min_frags))

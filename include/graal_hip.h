@@ -297,6 +297,27 @@ int graal_simulate_fetch(graal_ctx* h, int32_t* row, int32_t* col, int32_t* coun
 #define GRAAL_JUNCTION_NONFINITE 3
 int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status);
 
+/* Junction support: a Poisson bootstrap of the read pairs behind every junction score, all replicates in one call
+ * (graal_amd/csrc/junction_boot.h).  In replicate r = 0 .. n_rep - 1 contact k with count ob_k counts ob*_{k,r} ~ Poisson(ob_k), drawn
+ * independently (ob <= 0 draws 0; a non-integer ob is the rate as it stands), and the junction behind fragment f scores
+ *   J*_r[f] = M[f] + sum over the contacts k that straddle it of  ob*_{k,r} * (ln ex_cis,k - ln ex_trans,k), rounded to Q once per
+ *             (contact, replicate),
+ * M[f] the expected-mass part of graal_junction_scores (it does not depend on the data), the prices and the window rules those of
+ * graal_junction_scores under the current mode flags.  int64 sums: bit-identical from call to call, for any grid and any batching.
+ * The draw: Philox4x32-10 keyed by the seed, counter (row_k, col_k, 2 | r << 8, draw index), then graal_simulate_contacts' Poisson
+ * sampler -- a function of the contact's sub-fragment ids, the seed and r alone: replicate r does not depend on n_rep or on the contact's
+ * place in the list, two list entries with the same (row, col) draw the same count, and the streams are disjoint from those of
+ * graal_simulate_contacts with the same seed (their tags are 0 and 1).
+ * Outputs, indexed by fragment, n entries each: q_out and status exactly as graal_junction_scores gives them (the data's own J);
+ * support[f] = the number of replicates with J*_r[f] > threshold_q; q_sum, q_min, q_max = the sum, the smallest and the largest J*_r[f]
+ * (the sum of up to 1024 scores below 2^52 in Q cannot overflow int64); q_rep, if not NULL, the matrix J*_r[f] at q_rep[r * n + f]
+ * (replicate-major, n_rep * n entries).  Every output is 0 where status is not GRAAL_JUNCTION_VALID; a replicate term that does not fit
+ * Q marks the junctions it straddles GRAAL_JUNCTION_NONFINITE in this call.
+ * 1 <= n_rep <= 1024 and no null pointer but q_rep, else GRAAL_E_ARG.  Needs, refuses and leaves alone what graal_junction_scores does:
+ * GRAAL_E_UNSUPPORTED with repeated bins, GRAAL_E_STATE with an exchange or RCCL attached; no relabel, the step state untouched. */
+int graal_junction_bootstrap(graal_ctx* h, uint64_t seed, int32_t n_rep, int64_t threshold_q, int64_t* q_out, uint8_t* status, int32_t* support,
+                             int64_t* q_sum, int64_t* q_min, int64_t* q_max, int64_t* q_rep);
+
 /* End links: the likelihood each join between two contig ends would add, for every pair of ends the contacts support, in one pass
  * (graal_amd/csrc/links.h).  An end is end = 2*f + side of a LINEAR contig: side 0 its head (position 0), side 1 its tail (position
  * l_cont - 1), f the fragment there (a single-fragment contig has the ends 2f and 2f+1).  For ends eA < eB of DIFFERENT contigs A, B the
