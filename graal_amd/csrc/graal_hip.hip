@@ -4151,6 +4151,8 @@ struct JnBuf;                  // junctions.h: graal_junction_scores' buffers
 void jn_free(JnBuf* b);
 struct JbBuf;                  // junction_boot.h: graal_junction_bootstrap's buffers
 void jb_free(JbBuf* b);
+struct JgBuf;                  // junction_gaps.h: graal_junction_gaps' buffers
+void jg_free(JgBuf* b);
 
 struct LnBuf;                  // links.h: graal_end_links' buffers and results
 void ln_free(LnBuf* b);
@@ -4381,6 +4383,7 @@ struct Ctx : CtxMem {
     SimBuf* sim = nullptr;        // graal_simulate_contacts' buffers (simulate.h; allocated by its first call)
     JnBuf* jn = nullptr;          // graal_junction_scores' buffers (junctions.h; allocated by its first call)
     JbBuf* jb = nullptr;          // graal_junction_bootstrap's buffers (junction_boot.h; allocated by its first call)
+    JgBuf* jg = nullptr;          // graal_junction_gaps' buffers (junction_gaps.h; allocated by its first call)
     LnBuf* ln = nullptr;          // graal_end_links' buffers and its last result (links.h; allocated by its first call)
     EdBuf* ed = nullptr;          // graal_edit_layout's buffers (edit.h; allocated by its first call)
     InBuf* ins = nullptr;         // graal_insertions' buffers and its last result (insert.h; allocated by its first call)
@@ -4947,6 +4950,7 @@ void graal_destroy(graal_ctx* h)
         sim_free(h->sim); h->sim = nullptr;
         jn_free(h->jn); h->jn = nullptr;
         jb_free(h->jb); h->jb = nullptr;
+        jg_free(h->jg); h->jg = nullptr;
         ln_free(h->ln); h->ln = nullptr;
         ed_free(h->ed); h->ed = nullptr;
         in_free(h->ins); h->ins = nullptr;
@@ -6383,6 +6387,7 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "layout_slots.h"
 #include "junctions.h"
 #include "junction_boot.h"
+#include "junction_gaps.h"
 #include "rings.h"
 #include "links.h"
 #include "insert.h"

@@ -51,7 +51,7 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_upload_subfrags", "graal_upload_repeats", "graal_upload_contacts", "graal_upload_contacts_f32", "graal_upload_frags", "graal_download_frags",
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_set_scan_path", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
-           "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_junction_bootstrap", "graal_end_links", "graal_end_links_fetch",
+           "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_junction_bootstrap", "graal_junction_gaps", "graal_end_links", "graal_end_links_fetch",
            "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
            "graal_block_swaps", "graal_block_excisions", "graal_ring_scores", "graal_close_rings",
            "graal_layout_maps", "graal_layout_maps_fetch", "graal_map_windows", "graal_map_windows_fetch",
@@ -141,6 +141,8 @@ def load():
         L.graal_junction_scores.argtypes = [ctypes.c_void_p, _i64p, ctypes.POINTER(ctypes.c_uint8)]
         L.graal_junction_bootstrap.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int64, _i64p,
                                                ctypes.POINTER(ctypes.c_uint8), _i32p, _i64p, _i64p, _i64p, _i64p]
+        L.graal_junction_gaps.argtypes = [ctypes.c_void_p, _f32p, ctypes.c_int32, ctypes.c_int64, _i64p, ctypes.POINTER(ctypes.c_uint8),
+                                          _i32p, _i64p, _i32p, _i32p, _i64p]
         L.graal_end_links.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i64p]
         L.graal_end_links_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
         L.graal_end_links_best.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i64p, _i64p]
@@ -455,6 +457,45 @@ class Engine:
         out = {"q": q, "status": st, "support": sup, "q_sum": q_sum, "q_min": q_min, "q_max": q_max}
         if replicates:
             out["q_rep"] = rep
+        return out
+
+    def junction_gaps(self, gap_kb, drop=1.92, profile=False):
+        """graal_junction_gaps as floats: the likelihood profile of the gap at every junction over the grid gap_kb (kb; ascending, first
+        value >= 0, at most 64 values).  A dict of J (graal_junction_scores' score), status, gap_kb (the grid value with the largest
+        G = logL(the layout with that gap behind the fragment) - logL(layout)), gap_score (that G), gap_lo_kb / gap_hi_kb (the smallest
+        and largest grid value with G within `drop` log-likelihood units of the largest; 1.92 = chi2_1(0.95) / 2) and the grid indices
+        best / lo / hi (int32), indexed by fragment; floats are NaN where the status is not JUNCTION_VALID.  With profile=True also
+        `profile` float64[n_gaps, n].  Same preconditions and refusals as junction_scores.  Leaves the step state alone."""
+        grid = np.ascontiguousarray(gap_kb, dtype=np.float32).reshape(-1)
+        t = self.junction_gaps_q(grid, int(round(float(drop) * Q_SCALE)), profile)
+        ok = t["status"] == JUNCTION_VALID
+        g64 = grid.astype(np.float64)
+        out = {"J": np.where(ok, t["q"].astype(np.float64) / Q_SCALE, np.nan), "status": t["status"],
+               "gap_kb": np.where(ok, g64[t["best"]], np.nan), "gap_score": np.where(ok, t["q_best"].astype(np.float64) / Q_SCALE, np.nan),
+               "gap_lo_kb": np.where(ok, g64[t["lo"]], np.nan), "gap_hi_kb": np.where(ok, g64[t["hi"]], np.nan),
+               "best": t["best"], "lo": t["lo"], "hi": t["hi"]}
+        if profile:
+            out["profile"] = np.where(ok[None, :], t["q_gap"].astype(np.float64) / Q_SCALE, np.nan)
+        return out
+
+    def junction_gaps_q(self, gap_kb, drop_q, profile=False):
+        """The same in Q: a dict of q int64[n], status uint8[n], best int32[n] (a grid index), q_best int64[n], lo / hi int32[n] (grid
+        indices: the interval with G >= q_best - drop_q) and, with profile=True, q_gap int64[n_gaps, n]; zeros where the status is not
+        JUNCTION_VALID."""
+        grid = np.ascontiguousarray(gap_kb, dtype=np.float32).reshape(-1)
+        n, m = int(self.n), len(grid)
+        q, q_best = (np.zeros(n, dtype=np.int64) for _ in range(2))
+        st = np.zeros(n, dtype=np.uint8)
+        best, lo, hi = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        prof = np.zeros((m, n), dtype=np.int64) if profile else None
+        self._ck(self._L.graal_junction_gaps(self._h, grid.ctypes.data_as(_f32p), m, int(drop_q), q.ctypes.data_as(_i64p),
+                                             st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), best.ctypes.data_as(_i32p),
+                                             q_best.ctypes.data_as(_i64p), lo.ctypes.data_as(_i32p), hi.ctypes.data_as(_i32p),
+                                             prof.ctypes.data_as(_i64p) if prof is not None else None),
+                 "graal_junction_gaps")
+        out = {"q": q, "status": st, "best": best, "q_best": q_best, "lo": lo, "hi": hi}
+        if profile:
+            out["q_gap"] = prof
         return out
 
     def end_links(self, min_frags=1):

@@ -58,6 +58,15 @@ def main(argv=None):
                          "which the join still scores above 0 -- and the mean, smallest and largest resampled score")
     ap.add_argument("--junction-support-seed", type=int, default=None, help="with --junction-support: the seed of the resampling "
                                                                             "(default: --seed, or 0 when that is unset)")
+    ap.add_argument("--junction-gaps", action="store_true",
+                    help="write junction_gaps.tsv into the output folder: junctions.tsv's columns plus the gap the data estimate at every "
+                         "join of the final layout -- the likelihood profile of the gap over a grid, one GPU call: its maximum, the "
+                         "interval within --junction-gaps-drop of it, and whether that interval is open towards a cut")
+    ap.add_argument("--junction-gaps-points", type=int, default=32, help="with --junction-gaps: grid points, 0 included (2 .. 64, default 32)")
+    ap.add_argument("--junction-gaps-max-kb", type=float, default=None, help="with --junction-gaps: the largest gap of the grid in kb "
+                                                                             "(default: the model's d_max)")
+    ap.add_argument("--junction-gaps-drop", type=float, default=1.92, help="with --junction-gaps: the interval's drop in log-likelihood "
+                                                                           "units (default 1.92)")
     ap.add_argument("--polish", action="store_true", help="before the outputs, cut the final layout's junctions scoring below "
                                                           "--polish-cut-below and rejoin the pieces (graal_amd.scaffold); writes polish.tsv")
     ap.add_argument("--polish-cut-below", type=float, default=0.0, help="with --polish: the junction score below which a join is cut (default 0)")
@@ -120,6 +129,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not 0 <= args.junction_support <= 1024:
         raise SystemExit("--junction-support must be in 0 .. 1024")
+    if args.junction_gaps and (not 2 <= args.junction_gaps_points <= 64 or args.junction_gaps_drop < 0
+                               or (args.junction_gaps_max_kb is not None and not args.junction_gaps_max_kb > 0)):
+        raise SystemExit("--junction-gaps-points must be in 2 .. 64, --junction-gaps-drop >= 0 and --junction-gaps-max-kb > 0")
     if args.maps_junctions < 0 or (args.maps_junctions and not (1 <= args.maps_junction_px <= 4096 and args.maps_junction_bin >= 1)):
         raise SystemExit("--maps-junctions must be >= 0, --maps-junction-px in 1 .. 4096 and --maps-junction-bin >= 1")
     if args.maps and not 1 <= args.maps_max_px <= 4096:
@@ -223,6 +235,10 @@ def main(argv=None):
         boot_seed = args.junction_support_seed if args.junction_support_seed is not None else (args.seed if args.seed is not None else 0)
         junctions.write_support_tsv(os.path.join(out, "junction_support.tsv"),
                                     junctions.support_table(smp, boot_seed, args.junction_support))
+    if args.junction_gaps:
+        from . import junctions
+        junctions.write_gaps_tsv(os.path.join(out, "junction_gaps.tsv"),
+                                 junctions.gap_table(smp, None, args.junction_gaps_drop, args.junction_gaps_points, args.junction_gaps_max_kb))
     if args.links:
         from . import links
         links.write_links_tsv(os.path.join(out, "links.tsv"), links.link_table(smp, args.links_min_frags))

@@ -318,6 +318,29 @@ int graal_junction_scores(graal_ctx* h, int64_t* q_out, uint8_t* status);
 int graal_junction_bootstrap(graal_ctx* h, uint64_t seed, int32_t n_rep, int64_t threshold_q, int64_t* q_out, uint8_t* status, int32_t* support,
                              int64_t* q_sum, int64_t* q_min, int64_t* q_max, int64_t* q_rep);
 
+/* Junction gaps: the likelihood profile of the gap at every junction, a grid of gap values in one call (graal_amd/csrc/junction_gaps.h).
+ * The layout model lets contigs abut (0 bp between a fragment and its successor); for a fragment f that graal_junction_scores scores and
+ * gap value g:   G[g][f] = logL(the layout with everything behind f in its contig moved gap_kb[g] kb further) - logL(layout),
+ * in the exact arithmetic with graal_junction_scores' roundings.  Only the sub-fragment pairs that straddle the junction change: with
+ * sd = |centre_b - centre_a| (the float32 centres as priced) and sd_g = sd + gap_kb[g] (one float32 addition), ex_0 = rippe(sd) * norm
+ * and ex_g = rippe(sd_g) * norm, norm = (float)(accu_a * accu_b) / nfpb in the plain indexing (the pair stays cis: the result does not
+ * depend on GRAAL_MODE_REF_TRANS_ACCU),
+ *   per contact:     ob * (ln ex_g - ln ex_0),  rounded to Q once per (contact, gap);
+ *   expected mass:   -(ex_g - ex_0), summed over the sub-fragment pairs of a fragment pair, rounded to Q once per (fragment pair, gap).
+ * int64 sums: bit-identical from call to call, for any launch grid and any batching of the gap values; a row depends on its own gap
+ * value alone.  At gap 0 every term is exactly 0; at a gap >= d_max every straddling pair of the window is priced v_inter * norm, so
+ * G = -J of the plain indexing: a gap as wide as the window is a cut.
+ * gap_kb: n_gaps finite values, strictly ascending, gap_kb[0] >= 0, 1 <= n_gaps <= 64; drop_q >= 0; no null pointer but q_gap: else
+ * GRAAL_E_ARG.  Outputs, indexed by fragment, n entries each: q_out and status exactly as graal_junction_scores gives them; best[f] = the
+ * grid index of the largest G[.][f] (ties: the smallest gap), q_best[f] that G in Q; lo[f] / hi[f] = the smallest and the largest grid
+ * index with G >= q_best - drop_q (the interval "within drop of the maximum"); q_gap, if not NULL, the whole profile at
+ * q_gap[g * n + f] (gap-major, n_gaps * n entries).  Every output is 0 where status is not GRAAL_JUNCTION_VALID; a term that does not
+ * fit Q at any gap marks the junctions it straddles GRAAL_JUNCTION_NONFINITE in this call.
+ * Needs, refuses and leaves alone what graal_junction_scores does: GRAAL_E_UNSUPPORTED with repeated bins, GRAAL_E_STATE with an exchange
+ * or RCCL attached; reads the layout fields only, no relabel, the step state untouched. */
+int graal_junction_gaps(graal_ctx* h, const float* gap_kb, int32_t n_gaps, int64_t drop_q, int64_t* q_out, uint8_t* status, int32_t* best,
+                        int64_t* q_best, int32_t* lo, int32_t* hi, int64_t* q_gap);
+
 /* End links: the likelihood each join between two contig ends would add, for every pair of ends the contacts support, in one pass
  * (graal_amd/csrc/links.h).  An end is end = 2*f + side of a LINEAR contig: side 0 its head (position 0), side 1 its tail (position
  * l_cont - 1), f the fragment there (a single-fragment contig has the ends 2f and 2f+1).  For ends eA < eB of DIFFERENT contigs A, B the
