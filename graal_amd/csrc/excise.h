@@ -39,7 +39,7 @@
 //   k_ex_nnz    -- streams the contact list once, 64 consecutive contacts per wave.  X x rest: a contact of one contig whose sides differ
 //                 in span feeds each side's span (cis -> trans, the count inside the window).  L x R: the lane walks the scored spans
 //                 strictly between its two slots and prices the contact with the right side moved lx down.  Sums per run of equal span
-//                 inside the wave (ln_run_sum) before the atomics; every loop bound around them is a wave ballot;
+//                 inside the wave (sp_add's run_sums) before the atomics; every loop bound around them is a wave ballot;
 //   k_ex_edges / scan / k_ex_mass -- work units from a prefix sum, a wave per unit: (span, a fragment of X within reach of an end of X),
 //                 which walks both flanks outwards from the boundaries 64 partners at a time, and (span, a fragment of L within reach of
 //                 s0), which walks R outwards from e1 with what its own gap leaves of reach_bp; a walk stops when a whole step is out of

@@ -6383,6 +6383,7 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 } // extern "C"
 
 #include "simulate.h"
+#include "wave_runs.h"
 #include "score_common.h"
 #include "layout_slots.h"
 #include "junctions.h"

@@ -1,6 +1,6 @@
 // insert.h -- the likelihood every insertion of a small contig into a junction would add, for every (piece, junction, orientation) the
 // contacts support (graal_insertions).  Included by graal_hip.hip after links.h (it uses LayoutRecs with recs_reserve / recs_build, the
-// records LnSub / LnFrag / LnCtg, ln_slot, ln_run_sum, ln_pair_mass, ln_quirk_pair, ln_mirror_q, k_ln_mirror, k_ln_flag and k_ln_keys, and
+// records LnSub / LnFrag / LnCtg, ln_slot, ln_pair_mass, ln_quirk_pair, ln_mirror_q, k_ln_mirror, k_ln_flag and k_ln_keys, wave_runs.h's run_sums, and
 // score_common.h's score_entry, score_exit, STEP_CK, stream_blocks and CandTable).
 //
 // A PIECE is a linear contig P of 1 .. max_piece_frags fragments; a TARGET junction is a fragment f with next[f] = g != -1 of a linear
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void k_in_nnz(const int* __restrict__ row, con
                 if (__ballot(mk != LN_EMPTY) != 0ull) {
                     long long v0 = m_term, v1 = m_bad ? 1 : 0, v2 = 0;
                     bool tail;
-                    ln_run_sum(mk, v0, v1, v2, tail);
+                    run_sums(mk, tail, v0, v1, v2);
                     if (tail && mk != LN_EMPTY) {
                         if (v0 != 0) atomicAdd((unsigned long long*)&mir[mk], (unsigned long long)v0);
                         if (v1 != 0) atomicAdd(&mirbad[mk], (int)v1);
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void k_in_nnz(const int* __restrict__ row, con
                     ? ((unsigned long long)(unsigned)(d ? Y.label : X.label) << 32) | (unsigned)(d ? X.label : Y.label) : LN_EMPTY;
                 if (__ballot(key != LN_EMPTY) == 0ull) continue;
                 bool tail;
-                ln_run_sum(key, v0, v1, v2, tail);
+                run_sums(key, tail, v0, v1, v2);
                 const bool rec = tail && key != LN_EMPTY;
                 if (COUNT) {
                     n_wave2 += (unsigned long long)__popcll(__ballot(rec));
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void k_in_nnz(const int* __restrict__ row, con
                 }
                 if (__ballot(key != LN_EMPTY) == 0ull) continue;
                 bool tail;
-                ln_run_sum(key, q, n_in, fl, tail);
+                run_sums(key, tail, q, n_in, fl);
                 const bool rec = tail && key != LN_EMPTY;
                 if (COUNT) {
                     n_wave += (unsigned long long)__popcll(__ballot(rec));

@@ -1,6 +1,6 @@
 // junction_gaps.h -- the likelihood profile of the gap at every junction of the current layout, a grid of gap values in one call
-// (graal_junction_gaps).  Included by graal_hip.hip after junction_boot.h (it uses JnBuf, JnFrag / JnSub, jn_bad and the steps of
-// graal_junction_scores, and junction_boot.h's jb_run_head / jb_run_sum and its batch rule).
+// (graal_junction_gaps).  Included by graal_hip.hip after junction_boot.h (it uses junctions.h's JnBuf with its batch pair, JnFrag /
+// JnSub, the steps of graal_junction_scores, jn_contact_stream, jn_bad, jn_blank and jn_mass_grid).
 //
 // G[g][f] = logL(the layout with everything behind f in its contig moved gap[g] kb further) - logL(layout), for the fragments f that
 // graal_junction_scores scores.  Pairs on one side of the junction are exactly unchanged; a straddling sub-fragment pair at distance
@@ -17,16 +17,15 @@
 //
 // Kernels, on the engine's stream:
 //   graal_junction_scores' own (slots, records, k_jn_nnz, k_jn_mass / k_jn_quirk) for the data's own J;
-//   k_jg_nnz  -- per batch of gap values: streams the row-sorted list, 64 consecutive contacts per wave; the slots, sd, norm and ln ex_0
-//                once per contact; a wave without a straddling contact inside the window moves on; else the run heads and tails once, then
-//                per gap value one rippe, one mm_ln, two segmented sums and one 64-bit atomic per run tail into D[g * n + slot];
+//   k_jg_nnz  -- per batch of gap values: junctions.h's contact stream (jn_contact_stream); the slots, sd, norm and ln ex_0 once per
+//                contact inside the window, then per gap value one rippe, one mm_ln and the stream's sums into D[g * n + slot];
 //   k_jg_mass -- k_jn_mass's tiling and rotated visiting order, JG_GB gap values per launch: ex_0 once per sub-fragment pair, then the
 //                JG_GB evaluations; a tile's column sums in LDS (4 * 64 * JG_GB int64), the row sums in registers;
 //   one hipcub InclusiveSum over the batch's rb * n entries (every gap's D sums to zero over each contig);
 //   k_jg_fold -- one thread per slot: the batch's rows of the scan into the profile G (fragment-indexed, kept on the device for the whole
 //                call: n_gaps * n int64), and behind the last batch two walks over the fragment's profile in grid order: best / q_best,
 //                then lo / hi.  No atomics: the order is fixed.
-// Batches follow junction_boot.h's byte rule (D and its scan, JB_BATCH_BYTES each).
+// Batches: jn_rows_batch(n) gap values, in JnBuf's batch pair.
 #pragma once
 
 namespace {
@@ -35,61 +34,41 @@ constexpr int JG_MAX_GAPS = 64;
 constexpr int JG_GB = 8;                               // gap values per k_jg_mass launch
 
 struct JgBuf {
-    int n = 0; size_t cells = 0, gcells = 0;
+    int n = 0; size_t gcells = 0;
     DevBuf<float> gap;                                 // the grid, JG_MAX_GAPS entries
     DevBuf<int> best, lo, hi; DevBuf<long long> qb;    // per fragment
-    DevBuf<long long> D, P;                            // a batch: rb * n each
     DevBuf<long long> G;                               // the profile: n_gaps * n, fragment-indexed
 };
 
 void jg_free(JgBuf* b) { delete b; }
 
+// the observed count times ln ex_g - ln ex_0, gap value g in row g; the plain indexing, inside the window only
+struct JgGap {
+    float nfpb; const Par& par; const float* __restrict__ gap;
+    float sd = 0.0f, norm = 0.0f;
+    double ln0 = 0.0, ob = 0.0;
+    __device__ __forceinline__ bool setup(const JnSub& A, const JnSub& Bs, int, int, const int& cnt)
+    {
+        if (!(A.slot >= 0 && Bs.slot >= 0 && A.label == Bs.label && A.slot != Bs.slot)) return false;
+        sd = fabsf(Bs.centre - A.centre);
+        if (!(sd < par.d_max)) return false;                  // (beyond the window: v_inter * norm at every gap, no term)
+        norm = (float)((A.accu & 0xffff) * (Bs.accu & 0xffff)) / nfpb;
+        ln0 = mm_ln(rippe(sd, par) * norm);
+        ob = (double)__int_as_float(cnt);
+        return true;
+    }
+    __device__ __forceinline__ long long q(int g) const
+    {
+        const float sdg = sd + gap[g];
+        return to_q(ob * (mm_ln(rippe(sdg, par) * norm) - ln0));
+    }
+};
+
 __global__ __launch_bounds__(256) void k_jg_nnz(const int* __restrict__ row, const int* __restrict__ col, const int* __restrict__ cnt,
                                                 long long nnz, const JnSub* __restrict__ sub, float nfpb, Par par,
                                                 const float* __restrict__ gap, int gb, int n, long long* __restrict__ D, int* __restrict__ B)
 {
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
-    for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: the run sums need the whole wave)
-        const long long k = k0 + lane;
-        int ka = -1, kb = -1;
-        float sd = 0.0f, norm = 0.0f;
-        double ln0 = 0.0, ob = 0.0;
-        bool has = false;
-        if (k < nnz) {
-            const JnSub A = sub[row[k]], Bs = sub[col[k]];
-            ka = A.slot; kb = Bs.slot;
-            if (ka >= 0 && kb >= 0 && A.label == Bs.label && ka != kb) {
-                sd = fabsf(Bs.centre - A.centre);
-                has = sd < par.d_max;                         // (beyond the window: v_inter * norm at every gap, no term)
-            }
-            if (has) {
-                norm = (float)((A.accu & 0xffff) * (Bs.accu & 0xffff)) / nfpb;
-                ln0 = mm_ln(rippe(sd, par) * norm);
-                ob = (double)__int_as_float(cnt[k]);
-            }
-        }
-        if (__ballot(has) == 0ull) continue;
-        const int ha = jb_run_head(ka), hb = jb_run_head(kb);
-        const int na = __shfl_down(ka, 1, 64), nb = __shfl_down(kb, 1, 64);   // (by every lane: a shuffle reads nothing from a lane that skips it)
-        const bool ta = (lane == 63 || na != ka) && ka >= 0;
-        const bool tb = (lane == 63 || nb != kb) && kb >= 0;
-        const bool fwd = ka < kb;
-        for (int g = 0; g < gb; g++) {
-            long long c = 0;
-            if (has) {
-                const float sdg = sd + gap[g];
-                const long long q = to_q(ob * (mm_ln(rippe(sdg, par) * norm) - ln0));
-                if (q == Q_BAD) jn_bad(B, ka, kb);
-                else c = fwd ? q : -q;
-            }
-            const long long vr = jb_run_sum(c, ha), vc = jb_run_sum(-c, hb);
-            long long* const Dg = D + (size_t)g * (size_t)n;
-            if (ta && vr != 0) atomicAdd((unsigned long long*)&Dg[ka], (unsigned long long)vr);
-            if (tb && vc != 0) atomicAdd((unsigned long long*)&Dg[kb], (unsigned long long)vc);
-        }
-    }
+    jn_contact_stream(row, col, cnt, nnz, sub, JgGap{nfpb, par, gap}, gb, n, D, B);
 }
 
 // What the sub-fragment pairs of fragments x (the lower slot) and y add to the expected mass at the gb gap values: acc[g] = the sum of
@@ -126,8 +105,7 @@ __global__ __launch_bounds__(256) void k_jg_mass(int n, const JnFrag* __restrict
 #pragma unroll
     for (int g = 0; g < JG_GB; g++) { gap[g] = g < gb ? gap_in[g] : 0.0f; row[g] = 0; tc[g][lane] = 0; }
     const int i = tile * 64 + lane;
-    JnFrag x;
-    x.frag = 0; x.start_bp = 0; x.len_bp = 0; x.flags = 0; x.n = 0; x.a0 = x.a1 = x.a2 = 0; x.c0 = x.c1 = x.c2 = 0.0f; x.last = -1;
+    JnFrag x = jn_blank();
     if (i < n) { x = fr[i]; x.last = min(x.last, n - 1); }
     const int x_end = x.start_bp + x.len_bp;
     bool live = i < n && !(x.flags & 2) && x.last > i;
@@ -213,20 +191,15 @@ int graal_junction_gaps(graal_ctx* h, const float* gap_kb, int32_t n_gaps, int64
     if (const int rc = score_entry(h, "graal_junction_gaps")) return rc;
     const int n = h->n;
     if (n < 1) return GRAAL_OK;
-    // the batch: junction_boot.h's rule -- as many gap values as fit the bound, whatever n_gaps is (a row does not depend on it)
-    const int RB = (int)std::max<size_t>(1, std::min<size_t>(JG_MAX_GAPS, JB_BATCH_BYTES / (sizeof(long long) * (size_t)n)));
-    const int rb_max = std::min(RB, (int)n_gaps);
+    const int RB = jn_rows_batch(n);
     if (!h->jg) h->jg = new JgBuf();
     JgBuf* X = h->jg;
     hipStream_t s = h->stream;
-    const size_t cells = (size_t)rb_max * (size_t)n, gcells = (size_t)n_gaps * (size_t)n;
-    size_t br = 0;
-    CK(hipcub::DeviceScan::InclusiveSum(nullptr, br, (long long*)nullptr, (long long*)nullptr, (int)((size_t)RB * (size_t)n), s));
-    if (const int rc = jn_reserve(h, br)) return rc;
+    const size_t gcells = (size_t)n_gaps * (size_t)n;
+    if (const int rc = jn_reserve(h, n_gaps)) return rc;
     JnBuf* J = h->jn;
     CK(group_exact(X->n, (size_t)n, X->best, n, X->lo, n, X->hi, n, X->qb, n));
     CK(X->gap.reserve_exact(JG_MAX_GAPS));
-    CK(group_grow(X->cells, cells, X->D, cells, X->P, cells));
     CK(group_grow(X->gcells, gcells, X->G, gcells));
     int rc = GRAAL_OK;
     unsigned err = 0;
@@ -236,26 +209,24 @@ int graal_junction_gaps(graal_ctx* h, const float* gap_kb, int32_t n_gaps, int64
         if ((rc = jn_add_mass(h, J))) break;
         if ((rc = jn_scan_d(h, J, J->P))) break;                  // the data's own J
         STEP_CK(hipMemcpyAsync(X->gap, gap_kb, sizeof(float) * (size_t)n_gaps, hipMemcpyHostToDevice, s));
-        const int lc = std::min(std::max(std::max(h->max_lcont, h->lcont_bound), 1), n);
-        const int n_tiles = (n + 63) / 64, Sw = mass_stripes(lc);
+        const JnMassGrid mg = jn_mass_grid(h);
         for (int g0 = 0; g0 < n_gaps && !rc; g0 += RB) {
             const int rb = std::min(RB, (int)n_gaps - g0);
             const size_t m = (size_t)rb * (size_t)n;
-            STEP_CK(hipMemsetAsync(X->D, 0, sizeof(long long) * m, s));
+            STEP_CK(hipMemsetAsync(J->Db, 0, sizeof(long long) * m, s));
             if (h->nnz > 0) {
                 k_jg_nnz<<<stream_blocks(h->nnz), 256, 0, s>>>(h->row, h->col, h->cnt, h->nnz, J->sub, h->nfpb, h->par, X->gap.p + g0, rb, n,
-                                                               X->D, J->B);
+                                                               J->Db, J->B);
                 STEP_CK(hipGetLastError());
             }
             for (int g1 = 0; g1 < rb && !rc; g1 += JG_GB) {
-                k_jg_mass<<<(n_tiles * Sw + 3) / 4, 256, 0, s>>>(n, J->fr, h->nfpb, h->par, reach_bp(h), Sw, X->gap.p + g0 + g1,
-                                                                 std::min(JG_GB, rb - g1), X->D.p + (size_t)g1 * (size_t)n, J->B);
+                k_jg_mass<<<mg.blocks, 256, 0, s>>>(n, J->fr, h->nfpb, h->par, reach_bp(h), mg.Sw, X->gap.p + g0 + g1, std::min(JG_GB, rb - g1),
+                                                    J->Db.p + (size_t)g1 * (size_t)n, J->B);
                 STEP_CK(hipGetLastError());
             }
             if (rc) break;
-            size_t tb = J->L.tmp.count;
-            STEP_CK(hipcub::DeviceScan::InclusiveSum(J->L.tmp.p, tb, X->D.p, X->P.p, (int)m, s));
-            k_jg_fold<<<blocks_for(n, 256), 256, 0, s>>>(n, J->fr, X->P, g0, rb, n_gaps, g0 + rb >= n_gaps ? 1 : 0, (long long)drop_q, X->G,
+            if ((rc = jn_rows_scan(h, J, rb))) break;
+            k_jg_fold<<<blocks_for(n, 256), 256, 0, s>>>(n, J->fr, J->Pb, g0, rb, n_gaps, g0 + rb >= n_gaps ? 1 : 0, (long long)drop_q, X->G,
                                                          X->best, X->qb, X->lo, X->hi);
             STEP_CK(hipGetLastError());
         }
@@ -267,12 +238,7 @@ int graal_junction_gaps(graal_ctx* h, const float* gap_kb, int32_t n_gaps, int64
         STEP_CK(hipMemcpyAsync(hi, X->hi, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
         if (q_gap) STEP_CK(hipMemcpyAsync(q_gap, X->G, sizeof(long long) * gcells, hipMemcpyDeviceToHost, s));
         STEP_CK(hipStreamSynchronize(s));
-        // a junction that met an unrepresentable term (in the data or at a gap) has no profile: zeros, as at ends and in rings
-        for (int f = 0; f < n; f++) {
-            if (status[f] != GRAAL_JUNCTION_NONFINITE) continue;
-            best[f] = 0; q_best[f] = 0; lo[f] = 0; hi[f] = 0;
-            if (q_gap) for (int g = 0; g < n_gaps; g++) q_gap[(size_t)g * (size_t)n + f] = 0;
-        }
+        jn_zero_nonfinite(n, status, q_gap, n_gaps, best, q_best, lo, hi);
     } while (false);
     return score_exit(h, "graal_junction_gaps", rc, nullptr, err);
 }

@@ -1,7 +1,7 @@
 // junctions.h -- the likelihood each join of the current layout carries, for every junction in one pass (graal_junction_scores).
 // Included by graal_hip.hip after layout_slots.h (it uses Ctx, Stat, centre_kb, rippe, to_q, WAVE_LDS_SYNC, model_math.h,
-// score_common.h's score_entry, score_exit, STEP_CK, stream_blocks and mass_stripes, and layout_slots.h's LayoutSlots and
-// slot_claim).
+// wave_runs.h's run_head / run_tail / run_sum, score_common.h's score_entry, score_exit, STEP_CK, stream_blocks and mass_stripes, and
+// layout_slots.h's LayoutSlots and slot_claim).
 //
 // J[f] = logL(layout) - logL(layout cut between f and next[f]), for f in a LINEAR contig with next[f] != -1, in the engine's exact
 // arithmetic: pairs on one side of the cut are exactly unchanged, so only the pairs that STRADDLE the cut contribute -- they go from their cis
@@ -18,9 +18,10 @@
 // (behind any commit or relabel the host has launched):
 //   slots_count (k_jn_count / scan) / k_jn_prep  -- slots, a 48-byte record per slot and a 16-byte record per sub-fragment (centre as the
 //                 pricing has it);
-//   k_jn_nnz   -- streams the row-sorted COO list, 64 consecutive contacts per wave; terms are summed per run of equal slots inside the wave
-//                 (a segmented shuffle scan) and only a run's last lane touches D: a row's contacts share its slot, so the row side costs
-//                 about one atomic per row and wave; the column side one per run of equal column slots;
+//   k_jn_nnz   -- streams the row-sorted COO list, 64 consecutive contacts per wave; a wave without a term moves on; else terms are summed
+//                 per run of equal slots inside the wave (a segmented shuffle scan) and only a run's last lane touches D: a row's contacts
+//                 share its slot, so the row side costs about one atomic per row and wave; the column side one per run of equal column
+//                 slots;
 //   k_jn_mass  -- k_full_mass_t's tiling: a wave's lanes are 64 consecutive slots x, the slots y behind them staged in LDS 64 at a time, S waves
 //                 per x tile.  Lane l visits the staged y's in the order l, l+1, ... (mod 64), so at every step the 64 lanes hold 64 different
 //                 columns: the column sums of a tile are kept in LDS without atomics, then one device atomic per tile column, and one per
@@ -28,9 +29,12 @@
 //   k_jn_quirk -- only with GRAAL_MODE_REF_TRANS_ACCU and bins of mixed RF counts: straddling pairs beyond the window, whose trans price
 //                 differs from their (v_inter) cis price by the indexing alone;
 //   two inclusive scans (D, and a count of non-finite terms laid out the same way), then k_jn_out: J and a status byte per fragment.
-// The host side is cut into the steps jn_reserve / jn_prepare / jn_add_contacts / jn_add_mass / jn_scan_d / jn_finish, and a contact's
-// term per unit count is jn_contact_unit: junction_boot.h (graal_junction_bootstrap) runs the same steps around its own kernels and
-// prices a resampled count with the same function.
+//
+// The family.  junction_boot.h and junction_gaps.h fill one D per replicate or per gap value -- a ROW -- by the same decomposition, and
+// share with this file jn_contact_stream (k_jn_nnz's body over a term type), the host steps jn_reserve ... jn_finish, and for the rows
+// jn_rows_batch, JnBuf's batch pair Db / Pb (one allocation: the two calls are never live together), jn_rows_scan and
+// jn_zero_nonfinite.  k_jg_mass repeats k_jn_mass's walk with JG_GB values per fragment pair: one body over the number of values puts
+// k_jn_mass over 72 VGPRs, an occupancy of 6 for 7 (profiles/junction_family.md), so only jn_blank and jn_mass_grid are shared there.
 #pragma once
 
 namespace {
@@ -45,10 +49,15 @@ struct JnBuf {
     DevBuf<JnSub> sub;
     DevBuf<long long> D, P;
     DevBuf<int> B, PB;
+    size_t cells = 0;
+    DevBuf<long long> Db, Pb;                              // a batch of rows (jn_rows_batch): rb * n each, D's and P's of the family's calls
     DevBuf<long long> q; DevBuf<unsigned char> st;         // the results, fragment-indexed
 };
 
 void jn_free(JnBuf* b) { delete b; }
+
+// the record of a lane without a slot: no sub-fragment, no partner
+__device__ __forceinline__ JnFrag jn_blank() { JnFrag x{}; x.last = -1; return x; }
 
 // What k_jn_prep and k_rg_prep read of fragment f: its bp interval, orientation and topology, its Stat, and the centres of its (up to
 // three) sub-fragments as the pricing has them.
@@ -95,21 +104,6 @@ __global__ __launch_bounds__(256) void k_jn_prep(SoaPtr s, int n, const Stat* __
     }
 }
 
-// Segmented sum over the wave's runs of equal keys: on return `v` of a run's LAST lane (`tail`) holds the run's sum.  Whole wave.
-__device__ __forceinline__ void jn_run_sum(int key, long long& v, bool& tail)
-{
-    const int lane = threadIdx.x & 63;
-    const int kp = __shfl_up(key, 1, 64), kn = __shfl_down(key, 1, 64);
-    int f = (lane == 0 || kp != key) ? 1 : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long vu = __shfl_up(v, o, 64);
-        const int fu = __shfl_up(f, o, 64);
-        if (lane >= o && !f) { v += vu; f |= fu; }
-    }
-    tail = lane == 63 || kn != key;
-}
-
 __device__ __forceinline__ void jn_bad(int* __restrict__ B, int i, int j)
 {
     atomicAdd(&B[i < j ? i : j], 1);
@@ -117,8 +111,7 @@ __device__ __forceinline__ void jn_bad(int* __restrict__ B, int i, int j)
 }
 
 // What one observed count of a contact between sub-fragments A and Bs adds to the junctions it straddles: t = ln ex_cis - ln ex_trans.
-// False when the contact has no term (another contig, a ring, one fragment, or beyond the window with the same indexing).  Shared by
-// k_jn_nnz and junction_boot.h's k_jb_nnz, which multiply it by the count and by a resampled count.
+// False when the contact has no term (another contig, a ring, one fragment, or beyond the window with the same indexing).
 __device__ __forceinline__ bool jn_contact_unit(const JnSub& A, const JnSub& Bs, const JnFrag* __restrict__ fr, float nfpb, const Par& par,
                                                 int quirk, double& t)
 {
@@ -139,35 +132,64 @@ __device__ __forceinline__ bool jn_contact_unit(const JnSub& A, const JnSub& Bs,
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_jn_nnz(const int* __restrict__ row, const int* __restrict__ col, const int* __restrict__ cnt,
-                                                long long nnz, const JnSub* __restrict__ sub, const JnFrag* __restrict__ fr, float nfpb, Par par,
-                                                int quirk, long long* __restrict__ D, int* __restrict__ B)
+// The family's contact stream: 64 consecutive contacts per wave; per contact the two records and term.setup(A, Bs, row id, column id,
+// count): has it a term; a wave without one moves on; else the runs of equal row and of equal column slots once, then per row r < rows
+// term.q(r) (Q_BAD: marked in B), two segmented sums and one 64-bit atomic per run tail into D[r * n + slot].
+template <class Term>
+__device__ __forceinline__ void jn_contact_stream(const int* __restrict__ row, const int* __restrict__ col, const int* __restrict__ cnt,
+                                                  long long nnz, const JnSub* __restrict__ sub, Term term, int rows, int n,
+                                                  long long* __restrict__ D, int* __restrict__ B)
 {
     const int lane = threadIdx.x & 63;
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
-    for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: jn_run_sum needs the whole wave)
+    for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: the run sums need the whole wave)
         const long long k = k0 + lane;
         int ka = -1, kb = -1;
-        long long c = 0;
+        bool has = false;
         if (k < nnz) {
-            const JnSub A = sub[row[k]], Bs = sub[col[k]];
+            const int ra = row[k], cb = col[k];
+            const JnSub A = sub[ra], Bs = sub[cb];
             ka = A.slot; kb = Bs.slot;
-            double t;
-            if (jn_contact_unit(A, Bs, fr, nfpb, par, quirk, t)) {
-                const double ob = (double)__int_as_float(cnt[k]);
-                const long long q = to_q(ob * t);
-                if (q == Q_BAD) jn_bad(B, A.slot, Bs.slot);
-                else c = A.slot < Bs.slot ? q : -q;
-            }
+            has = term.setup(A, Bs, ra, cb, cnt[k]);
         }
-        long long vr = c, vc = -c;
-        bool tr, tc;
-        jn_run_sum(ka, vr, tr);
-        jn_run_sum(kb, vc, tc);
-        if (tr && ka >= 0 && vr != 0) atomicAdd((unsigned long long*)&D[ka], (unsigned long long)vr);
-        if (tc && kb >= 0 && vc != 0) atomicAdd((unsigned long long*)&D[kb], (unsigned long long)vc);
+        if (__ballot(has) == 0ull) continue;
+        const int ha = run_head(ka), hb = run_head(kb);
+        const bool ta = run_tail(ka) && ka >= 0, tb = run_tail(kb) && kb >= 0;
+        const bool fwd = ka < kb;
+        for (int r = 0; r < rows; r++) {
+            long long c = 0;
+            if (has) {
+                const long long q = term.q(r);
+                if (q == Q_BAD) jn_bad(B, ka, kb);
+                else c = fwd ? q : -q;
+            }
+            const long long vr = run_sum(c, ha), vc = run_sum(-c, hb);
+            long long* const Dr = D + (size_t)r * (size_t)n;
+            if (ta && vr != 0) atomicAdd((unsigned long long*)&Dr[ka], (unsigned long long)vr);
+            if (tb && vc != 0) atomicAdd((unsigned long long*)&Dr[kb], (unsigned long long)vc);
+        }
     }
+}
+
+// the observed count times the unit term, one row
+struct JnPlain {
+    const JnFrag* __restrict__ fr; float nfpb; const Par& par; int quirk;
+    double t = 0.0, ob = 0.0;
+    __device__ __forceinline__ bool setup(const JnSub& A, const JnSub& Bs, int, int, const int& cnt)
+    {
+        if (!jn_contact_unit(A, Bs, fr, nfpb, par, quirk, t)) return false;
+        ob = (double)__int_as_float(cnt);
+        return true;
+    }
+    __device__ __forceinline__ long long q(int) const { return to_q(ob * t); }
+};
+
+__global__ __launch_bounds__(256) void k_jn_nnz(const int* __restrict__ row, const int* __restrict__ col, const int* __restrict__ cnt,
+                                                long long nnz, const JnSub* __restrict__ sub, const JnFrag* __restrict__ fr, float nfpb, Par par,
+                                                int quirk, long long* __restrict__ D, int* __restrict__ B)
+{
+    jn_contact_stream(row, col, cnt, nnz, sub, JnPlain{fr, nfpb, par, quirk}, 1, 0, D, B);
 }
 
 // trans price of sub-fragment pair (a, b) of fragments x, y: v_inter * norm, with the reference's indexing when `quirk` (ex_pair_ref)
@@ -202,8 +224,7 @@ __global__ __launch_bounds__(256) void k_jn_mass(int n, const JnFrag* __restrict
     JnFrag* const ty = s_y[wib];
     long long* const tc = s_col[wib];
     const int i = tile * 64 + lane;
-    JnFrag x;
-    x.frag = 0; x.start_bp = 0; x.len_bp = 0; x.flags = 0; x.n = 0; x.a0 = x.a1 = x.a2 = 0; x.c0 = x.c1 = x.c2 = 0.0f; x.last = -1;
+    JnFrag x = jn_blank();
     if (i < n) { x = fr[i]; x.last = min(x.last, n - 1); }
     const int x_end = x.start_bp + x.len_bp;
     long long row = 0;
@@ -286,23 +307,33 @@ __global__ void k_jn_out(SoaPtr s, int n, const int* __restrict__ slot_of, const
     st_out[f] = st;
 }
 
-// The steps of graal_junction_scores, each on the engine's stream; junction_boot.h runs the same ones around its own.
+// The steps of graal_junction_scores, each on the engine's stream; junction_boot.h and junction_gaps.h run the same ones around their own.
 inline int jn_quirk(const Ctx* h) { return (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0; }
 
-// The handle's JnBuf, sized to the engine's n and S; own_tmp: scratch bytes the caller's own scans need of L.tmp.
-int jn_reserve(Ctx* h, size_t own_tmp = 0)
+constexpr size_t JB_BATCH_BYTES = 256u << 20;      // rows * n * 8 bytes <= 256 MB (twice: Db and its scan Pb)
+constexpr int JB_BATCH_MAX = 64;
+
+// the rows (replicates, gap values) of one batch: as many as fit the bound, however many the call wants (a row does not depend on it)
+inline int jn_rows_batch(int n) { return (int)std::max<size_t>(1, std::min<size_t>(JB_BATCH_MAX, JB_BATCH_BYTES / (sizeof(long long) * (size_t)n))); }
+
+// The handle's JnBuf, sized to the engine's n and S; rows: how many rows the call will fill (the batch pair for min(batch, rows) of them,
+// and scratch for the scan of a whole batch).
+int jn_reserve(Ctx* h, int rows = 0)
 {
     const int n = h->n, S = h->n_sub_total;
     if (!h->jn) h->jn = new JnBuf();
     JnBuf* J = h->jn;
-    size_t b2 = 0, b3 = 0;
+    size_t b2 = 0, b3 = 0, br = 0;
     CK(hipcub::DeviceScan::InclusiveSum(nullptr, b2, J->D.p, J->P.p, n, h->stream));
     CK(hipcub::DeviceScan::InclusiveSum(nullptr, b3, J->B.p, J->PB.p, n, h->stream));
-    if (const int rc = slots_reserve(h, J->L, std::max(std::max(b2, b3), own_tmp))) return rc;
+    if (rows > 0) CK(hipcub::DeviceScan::InclusiveSum(nullptr, br, J->Db.p, J->Pb.p, (int)((size_t)jn_rows_batch(n) * (size_t)n), h->stream));
+    if (const int rc = slots_reserve(h, J->L, std::max(std::max(b2, b3), br))) return rc;
     if (J->n != n || J->S != S) {
         CK(group_realloc(J->n, n, J->fr, n, J->sub, std::max(S, 1), J->D, n, J->P, n, J->B, n, J->PB, n, J->q, n, J->st, n));
         J->S = S;
     }
+    const size_t cells = (size_t)std::min(jn_rows_batch(n), rows) * (size_t)n;
+    CK(group_grow(J->cells, cells, J->Db, cells, J->Pb, cells));
     return GRAAL_OK;
 }
 
@@ -337,6 +368,14 @@ int jn_add_contacts(Ctx* h, JnBuf* J)
     return rc;
 }
 
+// the launch of a mass walk (k_jn_mass, k_jg_mass): Sw waves per tile of 64 slots, four waves per block
+struct JnMassGrid { int Sw, blocks; };
+inline JnMassGrid jn_mass_grid(const Ctx* h)
+{
+    const int Sw = mass_stripes(std::min(std::max(std::max(h->max_lcont, h->lcont_bound), 1), h->n));
+    return {Sw, ((h->n + 63) / 64 * Sw + 3) / 4};
+}
+
 // the mass terms, added to D (and B)
 int jn_add_mass(Ctx* h, JnBuf* J)
 {
@@ -344,10 +383,8 @@ int jn_add_mass(Ctx* h, JnBuf* J)
     hipStream_t s = h->stream;
     int rc = GRAAL_OK;
     do {
-        const int lc = std::min(std::max(std::max(h->max_lcont, h->lcont_bound), 1), n);
-        const int n_tiles = (n + 63) / 64;
-        const int Sw = mass_stripes(lc);
-        k_jn_mass<<<(n_tiles * Sw + 3) / 4, 256, 0, s>>>(n, J->fr, h->nfpb, h->par, quirk, reach_bp(h), Sw, J->D, J->B);
+        const JnMassGrid g = jn_mass_grid(h);
+        k_jn_mass<<<g.blocks, 256, 0, s>>>(n, J->fr, h->nfpb, h->par, quirk, reach_bp(h), g.Sw, J->D, J->B);
         STEP_CK(hipGetLastError());
         if (quirk && h->n_ubins) {
             k_jn_quirk<<<h->n_ubins, 256, 0, s>>>(n, h->d_ubins, J->L.slot, J->fr, h->nfpb, h->par, reach_bp(h), J->D, J->B);
@@ -357,15 +394,30 @@ int jn_add_mass(Ctx* h, JnBuf* J)
     return rc;
 }
 
-// D's inclusive scan into P (n entries)
-int jn_scan_d(Ctx* h, JnBuf* J, long long* P)
+// D's inclusive scan into P, `rows` rows of n: every row's D sums to zero over each contig, so one scan of the concatenation is each
+// row's own scan
+int jn_scan(Ctx* h, JnBuf* J, const long long* D, long long* P, int rows)
 {
     int rc = GRAAL_OK;
     do {
         size_t tb = J->L.tmp.count;
-        STEP_CK(hipcub::DeviceScan::InclusiveSum(J->L.tmp.p, tb, J->D.p, P, h->n, h->stream));
+        STEP_CK(hipcub::DeviceScan::InclusiveSum(J->L.tmp.p, tb, D, P, (int)((size_t)rows * (size_t)h->n), h->stream));
     } while (false);
     return rc;
+}
+int jn_scan_d(Ctx* h, JnBuf* J, long long* P) { return jn_scan(h, J, J->D, P, 1); }             // the call's own D
+int jn_rows_scan(Ctx* h, JnBuf* J, int rb) { return jn_scan(h, J, J->Db, J->Pb, rb); }           // a batch of rb rows, Db into Pb
+
+// On the host, behind the copies: a junction that met an unrepresentable term (in the data or in a row) has no result -- zeros, as at
+// ends and in rings, in every per-fragment column `cols` and in its column of the rows x n matrix `mat` (null: none).
+template <class... C>
+void jn_zero_nonfinite(int n, const uint8_t* status, int64_t* mat, int rows, C*... cols)
+{
+    for (int f = 0; f < n; f++) {
+        if (status[f] != GRAAL_JUNCTION_NONFINITE) continue;
+        ((cols[f] = 0), ...);
+        if (mat) for (int r = 0; r < rows; r++) mat[(size_t)r * (size_t)n + f] = 0;
+    }
 }
 
 // B's inclusive scan, then J and the status byte per fragment from it and from J->P, and their copies to the host queued behind

@@ -1,6 +1,6 @@
 // links.h -- the likelihood every join between two contig ends would add, for every pair of ends the contacts support (graal_end_links).
 // Included by graal_hip.hip after rings.h (it uses Ctx, Stat, centre_kb, rippe, to_q, jn_trans, model_math.h, score_common.h's
-// score_entry, score_exit, STEP_CK, stream_blocks and CandTable, and layout_slots.h's LayoutSlots and slot_claim).
+// score_entry, score_exit, STEP_CK, stream_blocks and CandTable, layout_slots.h's LayoutSlots and slot_claim, and wave_runs.h's run_sums).
 // LayoutRecs, below, is shared with insert.h, span_moves.h and excise.h.
 //
 // Ends.  end = 2 * f + side of a LINEAR contig: side 0 its head (position 0), side 1 its tail (position l_cont - 1), f the fragment there.
@@ -177,21 +177,6 @@ __device__ __forceinline__ long long ln_slot(unsigned long long* __restrict__ ke
     return -1;
 }
 
-// Segmented sums over the wave's runs of equal 64-bit keys: on return a run's LAST lane (`tail`) holds the run's sums.  Whole wave.
-__device__ __forceinline__ void ln_run_sum(unsigned long long key, long long& v0, long long& v1, long long& v2, bool& tail)
-{
-    const int lane = threadIdx.x & 63;
-    const unsigned long long kp = __shfl_up(key, 1, 64), kn = __shfl_down(key, 1, 64);
-    int f = (lane == 0 || kp != key) ? 1 : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long u0 = __shfl_up(v0, o, 64), u1 = __shfl_up(v1, o, 64), u2 = __shfl_up(v2, o, 64);
-        const int fu = __shfl_up(f, o, 64);
-        if (lane >= o && !f) { v0 += u0; v1 += u1; v2 += u2; f |= fu; }
-    }
-    tail = lane == 63 || kn != key;
-}
-
 // The contact pass.  COUNT: count the records a wave would insert (after its run sums).  Otherwise insert them, and sum the contact part
 // of mirror[C] (the quirk) per contig.
 template <bool COUNT>
@@ -241,7 +226,7 @@ __global__ __launch_bounds__(256) void k_ln_nnz(const int* __restrict__ row, con
             if (__ballot(mk != LN_EMPTY) != 0ull) {
                 long long v0 = m_term, v1 = m_bad ? 1 : 0, v2 = 0;
                 bool tail;
-                ln_run_sum(mk, v0, v1, v2, tail);
+                run_sums(mk, tail, v0, v1, v2);
                 if (tail && mk != LN_EMPTY) {
                     if (v0 != 0) atomicAdd((unsigned long long*)&mir[mk], (unsigned long long)v0);
                     if (v1 != 0) atomicAdd(&mirbad[mk], (int)v1);
@@ -287,7 +272,7 @@ __global__ __launch_bounds__(256) void k_ln_nnz(const int* __restrict__ row, con
             }
             if (__ballot(key != LN_EMPTY) == 0ull) continue;
             bool tail;
-            ln_run_sum(key, q, n_in, fl, tail);
+            run_sums(key, tail, q, n_in, fl);
             const bool rec = tail && key != LN_EMPTY;
             if (COUNT) {
                 n_wave += (unsigned long long)__popcll(__ballot(rec));

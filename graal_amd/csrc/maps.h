@@ -1,7 +1,7 @@
 // maps.h -- the observed contacts, the contacts the model expects and their residual as images in the current genome order
 // (graal_layout_maps / graal_layout_maps_fetch; semantics in include/graal_hip.h).
-// Included by graal_hip.hip after edit.h (it uses score_common.h, map_shape.h, layout_slots.h's LayoutSlots, and junctions.h's
-// records of the slots: k_jn_prep, JnFrag, jn_run_sum).
+// Included by graal_hip.hip after edit.h (it uses score_common.h, map_shape.h, layout_slots.h's LayoutSlots, wave_runs.h's
+// run_sums, and junctions.h's records of the slots: k_jn_prep, JnFrag, jn_blank).
 //
 // Order.  Slots as for the junction scores (contig label -> member count -> exclusive scan -> offset + position: contigs by ascending label,
 // fragments by position), built from the layout fields, not from the engine's position index: the call does not relabel.  One more
@@ -12,7 +12,7 @@
 //   slots_count (k_jn_count / scan) / k_jn_prep / k_mp_slots / scan / k_mp_rank -- slots, ranks, pixel_of_sub, and per pixel the sum of the RF counts and of
 //                their squares (int64, exact);
 //   k_mp_obs  -- streams the contact list, 64 consecutive contacts per wave; count * 2^24 rounded once, summed per run of equal pixels inside
-//                the wave (jn_run_sum), one int64 atomic per run into the upper triangle;
+//                the wave (run_sums), one int64 atomic per run into the upper triangle;
 //   k_mp_cis  -- k_full_mass_t's windowed tiling over the slots: for every cis sub-fragment pair inside the window of a linear contig, and
 //                every pair of a circular one, max(cis, 0) - max(trans, 0) of the two float32 prices in Q30, rounded once per pair; beyond
 //                the window the two prices are the same float32 value and the pair is skipped.  With bin > 1 neighbouring lanes hit the same
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void k_mp_obs(const int* __restrict__ row, con
     const int lane = threadIdx.x & 63;
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
-    for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: jn_run_sum needs the whole wave)
+    for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: run_sums needs the whole wave)
         const long long k = k0 + lane;
         int key = -1;
         long long v = 0;
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void k_mp_obs(const int* __restrict__ row, con
             }
         }
         bool tail;
-        jn_run_sum(key, v, tail);
+        run_sums(key, tail, v);
         if (tail && key >= 0 && v != 0) atomicAdd((unsigned long long*)&O[key], (unsigned long long)v);
     }
 }
@@ -117,7 +117,7 @@ __device__ __forceinline__ void mp_add(bool merge, int key, long long q, long lo
     if (key < 0) q = 0;
     if (merge) {
         bool tail;
-        jn_run_sum(key, q, tail);
+        run_sums(key, tail, q);
         if (!tail) key = -1;
     }
     if (key >= 0 && q != 0) atomicAdd((unsigned long long*)&E[key], (unsigned long long)q);
@@ -149,8 +149,7 @@ __global__ __launch_bounds__(256) void k_mp_cis(int n, const JnFrag* __restrict_
     MpTile* const ty = s_y[wib];
     const bool merge = bin > 1;
     const int i = tile * 64 + lane;
-    JnFrag x;
-    x.frag = 0; x.start_bp = 0; x.len_bp = 0; x.flags = 0; x.n = 0; x.a0 = x.a1 = x.a2 = 0; x.c0 = x.c1 = x.c2 = 0.0f; x.last = -1;
+    JnFrag x = jn_blank();
     int xr0 = 0;
     float s_tot = 1.0f;
     if (i < n) { x = fr[i]; x.last = min(x.last, n - 1); xr0 = rank0[i]; s_tot = (float)lbp_of[i] / 1000.0f; }

@@ -2,7 +2,7 @@
 // pass (graal_ring_scores); and the commit that closes contigs (graal_close_rings).
 // Included by graal_hip.hip after junctions.h (it uses Ctx, Stat, rippe, to_q, WAVE_LDS_SYNC, model_math.h, score_common.h's score_entry,
 // layout_refusal, score_exit, STEP_CK, stream_blocks, mass_stripes and layout_replaced, layout_slots.h's LayoutSlots and
-// slot_claim, and junctions.h's jn_load and jn_run_sum).
+// slot_claim, wave_runs.h's run_sums, and junctions.h's jn_load).
 //
 // R[c] = logL(layout with contig c in the OTHER topology, every coordinate kept) - logL(layout), in the engine's exact arithmetic.  Nothing
 // moves, so only the price of c's own pairs changes, and only where the two topologies are priced apart: rippe_circ (graal_hip.hip)
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void k_rg_nnz(const int* __restrict__ row, con
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
     const RgPre pre = rg_pre(par);
-    for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: jn_run_sum needs the whole wave)
+    for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: run_sums needs the whole wave)
         const long long k = k0 + lane;
         int key = -1;
         long long vq = 0, vc = 0, vb = 0;
@@ -144,9 +144,9 @@ __global__ __launch_bounds__(256) void k_rg_nnz(const int* __restrict__ row, con
             }
         }
         bool t1, t2, t3;
-        jn_run_sum(key, vq, t1);
-        jn_run_sum(key, vc, t2);
-        jn_run_sum(key, vb, t3);
+        run_sums(key, t1, vq);
+        run_sums(key, t2, vc);
+        run_sums(key, t3, vb);
         if (t1 && key >= 0) {
             if (vq != 0) atomicAdd((unsigned long long*)&sum[key], (unsigned long long)vq);
             if (vc != 0) atomicAdd((unsigned long long*)&con[key], (unsigned long long)vc);
@@ -209,8 +209,8 @@ __global__ __launch_bounds__(256) void k_rg_mass(int n, const RgFrag* __restrict
     }
     const int key = i < n ? x.last : -1;
     bool t1, t2;
-    jn_run_sum(key, row, t1);
-    jn_run_sum(key, nb, t2);
+    run_sums(key, t1, row);
+    run_sums(key, t2, nb);
     if (t1 && key >= 0) {
         if (row != 0) atomicAdd((unsigned long long*)&sum[key], (unsigned long long)row);
         if (nb != 0) atomicAdd((unsigned long long*)&bad[key], (unsigned long long)nb);

@@ -1,8 +1,8 @@
 // span_moves.h -- the likelihood each move of a span of fragments would add, for a caller's set of disjoint spans in one pass: in-place
 // reversals (graal_block_flips) and swaps of two adjacent runs (graal_block_swaps); and the frame of every call that scores spans
 // (span_moves: these two and excise.h's graal_block_excisions).  Included by graal_hip.hip after insert.h (it uses LayoutRecs with
-// recs_reserve / recs_build, slots_read_err, the records LnFrag / LnCtg, ln_run_sum, ln_block_add, ln_mirror_q, span_check.h and
-// score_common.h's score_entry, score_exit, STEP_CK and stream_blocks).
+// recs_reserve / recs_build, slots_read_err, the records LnFrag / LnCtg, ln_block_add, ln_mirror_q, span_check.h, wave_runs.h's run_sums
+// and score_common.h's score_entry, score_exit, STEP_CK and stream_blocks).
 //
 // Span k = the fragments of one linear contig at slots first .. last, bp interval [s0, e1).  The breakpoint sm behind slot mid splits it
 // into the runs X = first .. mid and Y = mid + 1 .. last (lx = sm - s0, ly = e1 - sm).  The moved layout puts Y in front of X:
@@ -41,7 +41,7 @@
 //                 current and its moved centre (well defined: a fragment belongs to at most one span);
 //   k_sp_nnz    -- streams the contact list once, 64 consecutive contacts per wave.  A contact of one contig is priced when its sides
 //                 differ in (span, run): once for the span with both sides moved when they are its X and its Y, else once per side that
-//                 has a span, with that side moved alone.  Sums per run of equal span inside the wave (ln_run_sum) before the atomics;
+//                 has a span, with that side moved alone.  Sums per run of equal span inside the wave (run_sums) before the atomics;
 //                 the mirror's contact part rides along;
 //   k_sp_edges / scan / k_sp_mass -- work units (span, one fragment of X or Y within reach of an end of its run) from a prefix sum, a wave
 //                 per unit; its lanes walk the partner ranges outwards from the boundaries 64 fragments at a time (each partner record is
@@ -160,7 +160,7 @@ __device__ __forceinline__ void sp_add(unsigned long long key, long long q, long
                                        long long* __restrict__ cb, int* __restrict__ badb)
 {
     bool tail;
-    ln_run_sum(key, q, c, bad, tail);
+    run_sums(key, tail, q, c, bad);
     if (tail && key != LN_EMPTY) {
         if (q != 0) atomicAdd((unsigned long long*)&qb[key], (unsigned long long)q);
         if (c != 0) atomicAdd((unsigned long long*)&cb[key], (unsigned long long)c);
