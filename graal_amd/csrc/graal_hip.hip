@@ -6391,6 +6391,7 @@ int graal_run_counters(graal_ctx* h, int64_t out[12])
 #include "junction_gaps.h"
 #include "rings.h"
 #include "links.h"
+#include "links_boot.h"
 #include "insert.h"
 #include "span_moves.h"
 #include "excise.h"

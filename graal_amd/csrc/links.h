@@ -33,6 +33,9 @@
 //                 and the A x B pairs with a mixed bin (beyond the window, and the mirror's part on the partner): a wave per (link, group
 //                 of 8 fragments of A) as k_ln_mass, over all of B -- the only work that grows with contig length outside the window;
 //   k_ln_out   -- q = direct + mirrors of the reversed contigs, and a status byte.
+// What a contact contributes per end combination is formed by the contact unit (ln_contact, ln_comb, ln_mirror_term, ln_comb_term),
+// which takes the count as an argument: links_boot.h's k_lkb_nnz calls it with a replicate's count.  ln_links is graal_end_links between
+// score_entry and score_exit; graal_end_links_bootstrap (links_boot.h) runs it too.
 #pragma once
 
 namespace {
@@ -140,6 +143,16 @@ struct LnBuf {
     DevBuf<long long> bq; DevBuf<int> be; DevBuf<unsigned char> bflag; DevBuf<int> bsel, mea, meb;
     DevBuf<long long> mq; size_t bcap = 0;
     long long n_mutual = -1;                                         // -1: no result to fetch
+    // graal_end_links_bootstrap (links_boot.h).  Per table slot the link's index (-1: not listed); per contig label the contact part of
+    // mirror[C] under the data's counts (kc_mir) and a flag for a replicate term of it that does not fit Q (kc_bad); per link the fixed
+    // part M, the statistics, a flag for an unrepresentable replicate term and the call's status; per batch of replicates the contact
+    // sums C[r * m + link] (then L*_r in place), mirc[r * (n + 3) + label] and the per-end best Q / partner [r * 2n + end].
+    DevBuf<int> k_s2l; DevBuf<long long> kc_mir; DevBuf<int> kc_bad;
+    DevBuf<long long> k_fix, k_sum, k_mn, k_mx; DevBuf<int> k_sup, k_mut, k_lbad; DevBuf<unsigned char> k_st; size_t kcap = 0;
+    DevBuf<long long> kb_c, kb_mir, kb_bq; DevBuf<int> kb_be;
+    std::vector<long long> k_rep;                                    // the replicate matrix of the last call that wanted it (host)
+    long long boot_links = -1;                                       // -1: no result to fetch
+    int boot_rep = 0; bool boot_want = false;
 };
 
 void ln_free(LnBuf* b) { delete b; }
@@ -177,6 +190,111 @@ __device__ __forceinline__ long long ln_slot(unsigned long long* __restrict__ ke
     return -1;
 }
 
+// The find-only probe of the same table: the slot that holds `key`, or -1 (links_boot.h: a replicate never inserts).
+__device__ __forceinline__ long long ln_find(const unsigned long long* __restrict__ keys, unsigned long long cap, unsigned long long key)
+{
+    unsigned long long i = __umul64hi(ln_mix(key), cap);
+    for (unsigned long long t = 0; t < cap; t++) {
+        const unsigned long long old = keys[i];
+        if (old == key) return (long long)i;
+        if (old == LN_EMPTY) return -1;
+        if (++i == cap) i = 0;
+    }
+    return -1;
+}
+
+// ---- The contact unit: what a contact (X, Y) contributes per end combination, with the count left out.  k_ln_nnz multiplies by the
+// data's count, links_boot.h's k_lkb_nnz by a replicate's: both round count * unit to Q once, so a replicate that draws the count itself
+// gives k_ln_nnz's words.
+// Per contact: pair (both contigs eligible: the contact yields link records), mq (the mirror's contact part: the lower-id bin is mixed
+// and its contig eligible), the RF-count products in the plain indexing (prod) and in the current trans indexing (prod_t), and the
+// mirror's unit m_t = ln ex_trans(lower bin flipped) - ln ex_trans(now), used when m_on.
+struct LnContact { bool pair, mq, x_low, m_on; int prod, prod_t, mlabel; double m_t; };
+
+__device__ __forceinline__ void ln_contact(const LnSub& X, const LnSub& Y, int quirk, float nfpb, const Par& par, LnContact& U)
+{
+    const bool diff = X.label != Y.label;                            // (lanes past the list hold label -1 twice: no contact)
+    U.pair = diff && ln_elig(X.meta) && ln_elig(Y.meta);
+    // the quirk: the lower-id bin's orientation picks the trans price's indexing
+    U.x_low = X.frag < Y.frag;
+    const LnSub& lo = U.x_low ? X : Y;
+    U.mq = quirk && diff && ln_mixed(lo.meta) && ln_elig(lo.meta);
+    U.mlabel = lo.label;
+    const int own_x = X.acc & 0xffff, own_y = Y.acc & 0xffff;
+    U.prod = own_x * own_y;
+    U.prod_t = U.prod;
+    int prod_f = U.prod;                                             // the current trans indexing, and with the lower bin flipped
+    if (quirk && diff) {
+        const int own_l = lo.acc & 0xffff, last_l = lo.acc >> 16, other = U.x_low ? own_y : own_x;
+        U.prod_t = (ln_fwd(lo.meta) ? own_l : last_l) * other;
+        prod_f = (ln_fwd(lo.meta) ? last_l : own_l) * other;
+    }
+    U.m_on = U.mq && prod_f != U.prod_t;
+    U.m_t = 0.0;
+    if (U.m_on) {
+        const float et = par.v_inter * ((float)U.prod_t / nfpb), ef = par.v_inter * ((float)prod_f / nfpb);
+        U.m_t = mm_ln(ef) - mm_ln(et);
+    }
+}
+
+// the mirror's contact term of a contact that counts ob
+__device__ __forceinline__ void ln_mirror_term(const LnContact& U, double ob, long long& m_term, bool& m_bad)
+{
+    m_term = 0; m_bad = false;
+    if (U.m_on) {
+        m_term = to_q(ob * U.m_t);
+        if (m_term == Q_BAD) { m_bad = true; m_term = 0; }
+    }
+}
+
+// ln of the contact's current trans price
+__device__ __forceinline__ double ln_contact_trans(const LnContact& U, float nfpb, const Par& par)
+{
+    return mm_ln(par.v_inter * ((float)U.prod_t / nfpb));
+}
+
+// Per (contact of a pair, end combination c = side of X's contig << 1 | side of Y's): the link's key, whether the joined distance is
+// inside the window, the unit t = ln ex_joined - ln ex_trans (has_t: it is not exactly 0), and whether the mirror's contact term comes
+// off (the lower bin's contig is reversed by this link).
+struct LnComb { unsigned long long key; double t; bool has_t, in_win, sub_m; };
+
+__device__ __forceinline__ void ln_comb(const LnContact& U, const LnSub& X, const LnSub& Y, const LnCtg& CX, const LnCtg& CY, const Stat& SX,
+                                        const Stat& SY, int c, double ln_et, float nfpb, const Par& par, LnComb& G)
+{
+    const int sx = c >> 1, sy = c & 1;
+    const int ex = 2 * (sx ? CX.tail : CX.head) + sx, ey = 2 * (sy ? CY.tail : CY.head) + sy;
+    const bool x_first = ex < ey;
+    // A (first) is reversed iff its end is a head; B (second) iff its end is a tail
+    const bool rev_x = x_first ? sx == 0 : sx == 1, rev_y = x_first ? sy == 1 : sy == 0;
+    const int lbp_first = x_first ? X.lbp : Y.lbp;
+    const int nsx = ln_new_start(X.start, X.len, X.lbp, lbp_first, x_first, rev_x);
+    const int nsy = ln_new_start(Y.start, Y.len, Y.lbp, lbp_first, !x_first, rev_y);
+    const float cx = centre_kb(nsx, ln_fwd(X.meta) != rev_x, SX, ln_k(X.meta));
+    const float cy = centre_kb(nsy, ln_fwd(Y.meta) != rev_y, SY, ln_k(Y.meta));
+    const float sd = fabsf(cy - cx);
+    G.in_win = sd < par.d_max;
+    G.t = 0.0;
+    // (at |d| >= d_max rippe is v_inter exactly: the joined and the trans prices are the same float32 value unless the indexing differs)
+    G.has_t = !(sd >= par.d_max && U.prod_t == U.prod && par.v_inter >= 0.0f);
+    if (G.has_t) {
+        const float exn = rippe(sd, par) * ((float)U.prod / nfpb);
+        G.t = mm_ln(exn) - ln_et;
+    }
+    G.sub_m = U.mq && (U.x_low ? rev_x : rev_y);                     // the mirror's part on the partner: priced above
+    G.key = x_first ? ((unsigned long long)ex << 32) | (unsigned)ey : ((unsigned long long)ey << 32) | (unsigned)ex;
+}
+
+// the record term of a combination for a contact that counts ob (m_term, m_bad: ln_mirror_term's for the same count)
+__device__ __forceinline__ void ln_comb_term(const LnComb& G, double ob, long long m_term, bool m_bad, long long& q, bool& bad)
+{
+    q = 0; bad = false;
+    if (G.has_t) {
+        const long long t = to_q(ob * G.t);
+        if (t == Q_BAD) bad = true; else q = t;
+    }
+    if (G.sub_m) { q -= m_term; bad = bad || m_bad; }
+}
+
 // The contact pass.  COUNT: count the records a wave would insert (after its run sums).  Otherwise insert them, and sum the contact part
 // of mirror[C] (the quirk) per contig.
 template <bool COUNT>
@@ -194,35 +312,17 @@ __global__ __launch_bounds__(256) void k_ln_nnz(const int* __restrict__ row, con
     for (long long k0 = wave * 64; k0 < nnz; k0 += n_waves * 64) {   // (wave-uniform bounds: the run sums need the whole wave)
         const long long k = k0 + lane;
         LnSub X = {-1, -1, 0, 0, 0, 0, 0, 0}, Y = X;                   // (lanes past the list: no contig, no bin, no flags)
-        bool diff = false;
-        if (k < nnz) {
-            X = sub[row[k]]; Y = sub[col[k]];
-            diff = X.label != Y.label;
-        }
-        const bool pair = diff && ln_elig(X.meta) && ln_elig(Y.meta);
-        // the quirk: the lower-id bin's orientation picks the trans price's indexing
-        const bool x_low = X.frag < Y.frag;
-        const LnSub& lo = x_low ? X : Y;
-        const bool mq = quirk && diff && ln_mixed(lo.meta) && ln_elig(lo.meta);
+        if (k < nnz) { X = sub[row[k]]; Y = sub[col[k]]; }
+        LnContact U;
+        ln_contact(X, Y, quirk, nfpb, par, U);
+        const bool pair = U.pair, mq = U.mq;
         if (__ballot(pair || mq) == 0ull) continue;
         const double ob = k < nnz ? (double)__int_as_float(cnt[k]) : 0.0;
-        const int own_x = X.acc & 0xffff, own_y = Y.acc & 0xffff;
-        const int prod = own_x * own_y;
-        int prod_t = prod, prod_f = prod;                            // the current trans indexing, and with the lower bin flipped
-        if (quirk && diff) {
-            const int own_l = lo.acc & 0xffff, last_l = lo.acc >> 16, other = x_low ? own_y : own_x;
-            prod_t = (ln_fwd(lo.meta) ? own_l : last_l) * other;
-            prod_f = (ln_fwd(lo.meta) ? last_l : own_l) * other;
-        }
-        long long m_term = 0;
-        bool m_bad = false;
-        if (mq && prod_f != prod_t) {
-            const float et = par.v_inter * ((float)prod_t / nfpb), ef = par.v_inter * ((float)prod_f / nfpb);
-            m_term = to_q(ob * (mm_ln(ef) - mm_ln(et)));
-            if (m_term == Q_BAD) { m_bad = true; m_term = 0; }
-        }
+        long long m_term;
+        bool m_bad;
+        ln_mirror_term(U, ob, m_term, m_bad);
         if (!COUNT) {                                                // mirror[C]'s contacts, summed per run of the lower bin's contig
-            const unsigned long long mk = (mq && (m_term != 0 || m_bad)) ? (unsigned long long)lo.label : LN_EMPTY;
+            const unsigned long long mk = (mq && (m_term != 0 || m_bad)) ? (unsigned long long)U.mlabel : LN_EMPTY;
             if (__ballot(mk != LN_EMPTY) != 0ull) {
                 long long v0 = m_term, v1 = m_bad ? 1 : 0, v2 = 0;
                 bool tail;
@@ -237,37 +337,20 @@ __global__ __launch_bounds__(256) void k_ln_nnz(const int* __restrict__ row, con
         LnCtg CX, CY;
         Stat SX, SY;
         if (pair) { CX = ctg[X.label]; CY = ctg[Y.label]; SX = stat[X.frag]; SY = stat[Y.frag]; }
-        const float et = par.v_inter * ((float)prod_t / nfpb);
-        const double ln_et = mm_ln(et);
+        const double ln_et = ln_contact_trans(U, nfpb, par);
 #pragma unroll 1
         for (int c = 0; c < 4; c++) {
             unsigned long long key = LN_EMPTY;
             long long q = 0, n_in = 0, fl = 0;
             if (pair) {
-                const int sx = c >> 1, sy = c & 1;
-                const int ex = 2 * (sx ? CX.tail : CX.head) + sx, ey = 2 * (sy ? CY.tail : CY.head) + sy;
-                const bool x_first = ex < ey;
-                // A (first) is reversed iff its end is a head; B (second) iff its end is a tail
-                const bool rev_x = x_first ? sx == 0 : sx == 1, rev_y = x_first ? sy == 1 : sy == 0;
-                const int lbp_first = x_first ? X.lbp : Y.lbp;
-                const int nsx = ln_new_start(X.start, X.len, X.lbp, lbp_first, x_first, rev_x);
-                const int nsy = ln_new_start(Y.start, Y.len, Y.lbp, lbp_first, !x_first, rev_y);
-                const float cx = centre_kb(nsx, ln_fwd(X.meta) != rev_x, SX, ln_k(X.meta));
-                const float cy = centre_kb(nsy, ln_fwd(Y.meta) != rev_y, SY, ln_k(Y.meta));
-                const float sd = fabsf(cy - cx);
-                const bool in_win = sd < par.d_max;
-                bool bad = false;
-                // (at |d| >= d_max rippe is v_inter exactly: the joined and the trans prices are the same float32 value unless the indexing differs)
-                if (!(sd >= par.d_max && prod_t == prod && par.v_inter >= 0.0f)) {
-                    const float exn = rippe(sd, par) * ((float)prod / nfpb);
-                    const long long t = to_q(ob * (mm_ln(exn) - ln_et));
-                    if (t == Q_BAD) bad = true; else q = t;
-                }
-                if (mq && (x_low ? rev_x : rev_y)) { q -= m_term; bad = bad || m_bad; }   // the mirror's part on the partner: priced above
-                if (in_win || q != 0 || bad) {
-                    key = x_first ? ((unsigned long long)ex << 32) | (unsigned)ey : ((unsigned long long)ey << 32) | (unsigned)ex;
-                    n_in = in_win ? (long long)llrint(ob) : 0;
-                    fl = (bad ? 1 : 0) + (in_win ? (1ll << 32) : 0);
+                LnComb G;
+                ln_comb(U, X, Y, CX, CY, SX, SY, c, ln_et, nfpb, par, G);
+                bool bad;
+                ln_comb_term(G, ob, m_term, m_bad, q, bad);
+                if (G.in_win || q != 0 || bad) {
+                    key = G.key;
+                    n_in = G.in_win ? (long long)llrint(ob) : 0;
+                    fl = (bad ? 1 : 0) + (G.in_win ? (1ll << 32) : 0);
                 }
             }
             if (__ballot(key != LN_EMPTY) == 0ull) continue;
@@ -700,38 +783,28 @@ int ln_count(Ctx* h, LayoutRecs& R, int min_frags, int quirk, LnCount& C)
     return rc;
 }
 
-} // namespace
-
-extern "C" {
-
-int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
+// graal_end_links between score_entry and score_exit: the scored, sorted link table in Lb (m links).  fn names the caller in the
+// refusals (why, written into msg); need: the device bytes counted against the budget; mirc_keep, if not null, receives the contact part
+// of mirror[C] (n + 3 words) as the insert pass leaves it, before k_ln_mirror adds the mass part into the same array -- int64 sums are
+// exact, so the split changes no word of the total (links_boot.h re-forms the contact part per replicate).
+int ln_links(Ctx* h, LnBuf* Lb, int min_frags, const char* fn, long long* mirc_keep, LnCount& C, long long& m, const char*& why, char* msg,
+             size_t msg_len, unsigned long long& need)
 {
-    if (!h || !n_links) return GRAAL_E_ARG;
-    if (min_frags < 1) return fail(h, GRAAL_E_ARG, "graal_end_links: min_frags must be >= 1");
-    if (const int rc = score_entry(h, "graal_end_links")) return rc;
-    *n_links = 0;
-    const int n = h->n;
-    if (!h->ln) h->ln = new LnBuf();
-    LnBuf* Lb = h->ln;
     LayoutRecs& R = Lb->R;
     CandTable& T = Lb->T;
-    Lb->n_links = -1;
-    if (n < 1) { Lb->n_links = 0; return GRAAL_OK; }
+    const int n = h->n;
     hipStream_t s = h->stream;
     if (const int rc = recs_reserve(h, R)) return rc;
     const int quirk = (h->mode & GRAAL_MODE_REF_TRANS_ACCU) ? 1 : 0;
     const int mq = quirk && h->n_ubins > 0;
     int rc = GRAAL_OK;
-    LnCount C;
-    long long m = 0;
-    const char* why = nullptr;
-    char msg[320];
+    m = 0;
     do {
         if ((rc = ln_count(h, R, min_frags, quirk, C)) || C.err) break;
         const unsigned long long cap = C.cap, L = C.bound + 1;
         // device memory: the table (key, q, contacts, flags, selection byte per slot), the per-link arrays sized to the bound (keys x2,
         // indices x2, q, contacts, groups x2, bad, ends x2, status) and the hipCUB temp storage of the selection, the sort and the scan
-        unsigned long long need = cap * TABLE_SLOT_BYTES + L * (unsigned long long)(8 * 2 + 4 * 2 + 8 + 8 + 8 * 2 + 4 + 4 * 2 + 1);
+        need = cap * TABLE_SLOT_BYTES + L * (unsigned long long)(8 * 2 + 4 * 2 + 8 + 8 + 8 * 2 + 4 + 4 * 2 + 1);
         size_t b_sel = 0, b_sort = 0, b_scan = 0;
         if (cap < (unsigned long long)INT_MAX) {
             STEP_CK(hipcub::DeviceSelect::Flagged(nullptr, b_sel, hipcub::CountingInputIterator<int>(0), (const unsigned char*)nullptr, (int*)nullptr,
@@ -743,8 +816,8 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
         const size_t tneed = std::max(b_sel, std::max(b_sort, b_scan));
         need += tneed;
         if (cap >= (unsigned long long)INT_MAX || need > (unsigned long long)GRAAL_LINKS_MAX_BYTES) {
-            snprintf(msg, sizeof msg, "graal_end_links: the candidate table needs %llu bytes (%llu records counted), over the budget of %llu bytes "
-                     "(GRAAL_LINKS_MAX_BYTES): use a larger min_frags", need, C.ctr[0], (unsigned long long)GRAAL_LINKS_MAX_BYTES);
+            snprintf(msg, msg_len, "%s: the candidate table needs %llu bytes (%llu records counted), over the budget of %llu bytes "
+                     "(GRAAL_LINKS_MAX_BYTES): use a larger min_frags", fn, need, C.ctr[0], (unsigned long long)GRAAL_LINKS_MAX_BYTES);
             why = msg;
             break;
         }
@@ -759,6 +832,7 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
                                                  T.tq, T.tc, T.tf, R.mir, R.mirbad, &R.ctr[0], R.L.err);
             STEP_CK(hipGetLastError());
         }
+        if (mirc_keep) STEP_CK(hipMemcpyAsync(mirc_keep, R.mir, sizeof(long long) * (size_t)(n + 3), hipMemcpyDeviceToDevice, s));
         k_ln_flag<<<blocks_for((long long)cap, 256), 256, 0, s>>>(T.keys, T.tf, (long long)cap, T.tsel);
         STEP_CK(hipGetLastError());
         size_t tb = T.stmp.count;
@@ -783,7 +857,7 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
         STEP_CK(hipStreamSynchronize(s));
         const long long groups = last[0] + last[1];
         if ((groups + 3) / 4 > (long long)INT_MAX) {
-            snprintf(msg, sizeof msg, "graal_end_links: %lld wave groups exceed one launch: use a larger min_frags", groups);
+            snprintf(msg, msg_len, "%s: %lld wave groups exceed one launch: use a larger min_frags", fn, groups);
             why = msg;
             break;
         }
@@ -805,6 +879,30 @@ int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
         STEP_CK(hipGetLastError());
         STEP_CK(hipStreamSynchronize(s));
     } while (false);
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int graal_end_links(graal_ctx* h, int32_t min_frags, int64_t* n_links)
+{
+    if (!h || !n_links) return GRAAL_E_ARG;
+    if (min_frags < 1) return fail(h, GRAAL_E_ARG, "graal_end_links: min_frags must be >= 1");
+    if (const int rc = score_entry(h, "graal_end_links")) return rc;
+    *n_links = 0;
+    if (!h->ln) h->ln = new LnBuf();
+    LnBuf* Lb = h->ln;
+    Lb->n_links = -1;
+    Lb->boot_links = -1;                                             // (a bootstrap's columns describe the table this call replaces)
+    if (h->n < 1) { Lb->n_links = 0; return GRAAL_OK; }
+    LnCount C;
+    long long m = 0;
+    const char* why = nullptr;
+    char msg[320];
+    unsigned long long need = 0;
+    const int rc = ln_links(h, Lb, min_frags, "graal_end_links", nullptr, C, m, why, msg, sizeof msg, need);
     if (const int r = score_exit(h, "graal_end_links", rc, why, C.err)) return r;
     Lb->n_links = m;
     *n_links = m;

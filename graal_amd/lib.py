@@ -52,7 +52,7 @@ SYMBOLS = ("graal_abi_version", "graal_create", "graal_destroy", "graal_last_err
            "graal_relabel_contigs", "graal_begin_step", "graal_begin_step_launch", "graal_layout_stats", "graal_eval_full_q", "graal_eval_full_params", "graal_eval_candidates_q",
            "graal_eval_candidates", "graal_exchange_bytes", "graal_attach_exchange", "graal_eval_candidates_x", "graal_exchange_selftest", "graal_detach_exchange", "graal_rccl_unique_id", "graal_attach_rccl", "graal_detach_rccl", "graal_upload_distance_ref", "graal_genome_distance", "graal_apply_move", "graal_set_finisher", "graal_set_mode", "graal_set_timing", "graal_set_scan_path", "graal_last_timing", "graal_scan_times", "graal_strict_times", "graal_time_scan", "graal_last_counters", "graal_take_carry_correction", "graal_upload_own_obs", "graal_explode", "graal_run_counters",
            "graal_simulate_contacts", "graal_simulate_fetch", "graal_junction_scores", "graal_junction_bootstrap", "graal_junction_gaps", "graal_end_links", "graal_end_links_fetch",
-           "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
+           "graal_end_links_best", "graal_end_links_mutual_fetch", "graal_end_links_bootstrap", "graal_end_links_bootstrap_fetch", "graal_edit_layout", "graal_insertions", "graal_insertions_fetch", "graal_block_flips",
            "graal_block_swaps", "graal_block_excisions", "graal_ring_scores", "graal_close_rings",
            "graal_layout_maps", "graal_layout_maps_fetch", "graal_map_windows", "graal_map_windows_fetch",
            "graal_upload_proposal_tables", "graal_step", "graal_step_finish", "graal_steps", "graal_host_np_sum", "graal_host_select_move", "graal_host_neighbours", "graal_host_max_dist_intra")
@@ -147,6 +147,10 @@ def load():
         L.graal_end_links_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
         L.graal_end_links_best.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, _i64p, _i64p]
         L.graal_end_links_mutual_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i64p, ctypes.c_int64]
+        L.graal_end_links_bootstrap.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                _i64p]
+        L.graal_end_links_bootstrap_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint8), _i32p, _i32p,
+                                                      _i64p, _i64p, _i64p, _i64p, ctypes.c_int64]
         L.graal_edit_layout.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i32p, ctypes.c_int32, _i32p, _i32p, _i32p]
         L.graal_insertions.argtypes = [ctypes.c_void_p, ctypes.c_int32, _i64p]
         L.graal_insertions_fetch.argtypes = [ctypes.c_void_p, _i32p, _i32p, ctypes.POINTER(ctypes.c_uint8), _i64p, _i64p,
@@ -540,6 +544,49 @@ class Engine:
         self._ck(self._L.graal_end_links_mutual_fetch(self._h, a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p), q.ctypes.data_as(_i64p), m),
                  "graal_end_links_mutual_fetch")
         return be, bq, (a, b, q)
+
+    def end_links_bootstrap(self, seed, n_rep, min_frags=1, threshold=0.0, replicates=False):
+        """graal_end_links_bootstrap as floats: a dict of end_a, end_b, contacts and status (end_links' columns, word for word), score
+        (the data's own), support (the fraction of the n_rep Poisson-bootstrap replicates of the contacts in which the link scores above
+        `threshold`), mutual (the fraction in which it also is the join both of its ends choose: each the other's best partner, ties to
+        the lower partner end), mean, min and max of the replicate scores; floats are NaN where the status is not LINK_VALID.  With
+        replicates=True also `replicates` float64[n_rep, n_links].  Replicate r is a function of (layout, contacts, seed, r) alone, and
+        the same resampled dataset as junction_bootstrap's replicate r under the same seed.  Same preconditions and refusals as
+        end_links.  Leaves the step state alone."""
+        t = self.end_links_bootstrap_q(seed, n_rep, min_frags, int(round(float(threshold) * Q_SCALE)), replicates)
+        ok = t["status"] == LINK_VALID
+        f = lambda x, d=1.0: np.where(ok, x.astype(np.float64) / d, np.nan)
+        out = {"end_a": t["end_a"], "end_b": t["end_b"], "contacts": t["contacts"], "status": t["status"], "score": f(t["q"], Q_SCALE),
+               "support": f(t["support"], float(n_rep)), "mutual": f(t["mutual"], float(n_rep)),
+               "mean": f(t["q_sum"], float(n_rep) * Q_SCALE), "min": f(t["q_min"], Q_SCALE), "max": f(t["q_max"], Q_SCALE)}
+        if replicates:
+            out["replicates"] = np.where(ok[None, :], t["q_rep"].astype(np.float64) / Q_SCALE, np.nan)
+        return out
+
+    def end_links_bootstrap_q(self, seed, n_rep, min_frags=1, threshold_q=0, replicates=False):
+        """The same in Q: a dict of end_a, end_b int32, q, contacts int64, status uint8, support, mutual int32 (counts of replicates),
+        q_sum, q_min, q_max int64 and, with replicates=True, q_rep int64[n_rep, n_links]; replicate columns are 0 where the status is
+        not LINK_VALID."""
+        m = ctypes.c_int64(0)
+        n_rep = int(n_rep)
+        self._ck(self._L.graal_end_links_bootstrap(self._h, int(min_frags), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), n_rep,
+                                                   int(threshold_q), 1 if replicates else 0, ctypes.byref(m)), "graal_end_links_bootstrap")
+        m = int(m.value)
+        a, b, sup, mut = (np.zeros(m, dtype=np.int32) for _ in range(4))
+        q, c, q_sum, q_min, q_max = (np.zeros(m, dtype=np.int64) for _ in range(5))
+        st = np.zeros(m, dtype=np.uint8)
+        rep = np.zeros((n_rep, m), dtype=np.int64) if replicates else None
+        self._ck(self._L.graal_end_links_bootstrap_fetch(self._h, a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p), q.ctypes.data_as(_i64p),
+                                                         c.ctypes.data_as(_i64p), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                         sup.ctypes.data_as(_i32p), mut.ctypes.data_as(_i32p), q_sum.ctypes.data_as(_i64p),
+                                                         q_min.ctypes.data_as(_i64p), q_max.ctypes.data_as(_i64p),
+                                                         rep.ctypes.data_as(_i64p) if rep is not None else None, m),
+                 "graal_end_links_bootstrap_fetch")
+        out = {"end_a": a, "end_b": b, "q": q, "contacts": c, "status": st, "support": sup, "mutual": mut, "q_sum": q_sum, "q_min": q_min,
+               "q_max": q_max}
+        if replicates:
+            out["q_rep"] = rep
+        return out
 
     def insertions(self, max_piece_frags=1):
         """graal_insertions: every insertion of a piece (a linear contig of 1 .. max_piece_frags fragments) into a junction of another

@@ -10,6 +10,14 @@ other pair would score only its negative expected mass.
     best_links(table, k)                         -- the k best partners of every end (a dict of columns, see BEST_COLUMNS)
     mutual_best(table)                           -- the links whose two ends are each other's best partner with a positive score
     write_links_tsv(path, table)                 -- one tab-separated row per link, with a header line
+
+Link support (graal_end_links_bootstrap): a Poisson bootstrap of the read pairs -- every contact's count redrawn as Poisson(count), n_rep
+times, in one GPU call.  Per listed link: support, the fraction of the resampled datasets in which the join still scores above 0, and
+mutual, the fraction in which it also is the join both of its ends choose (each the other's best partner) -- the number a phylogeny
+program prints beside a branch.  Under one seed replicate r is the same resampled dataset as graal_amd.junctions' support replicate r.
+
+    support_table(sampler_or_engine, seed, n_rep, min_frags=1, threshold=0.0)   -- COLUMNS plus SUPPORT_COLUMNS' last five
+    write_support_tsv(path, table)                                              -- one row per link, with a header line
 """
 import numpy as np
 
@@ -17,6 +25,7 @@ from .lib import Engine, LINK_NONFINITE, LINK_VALID
 
 COLUMNS = ("contig_a", "frag_a", "side_a", "contig_b", "frag_b", "side_b", "contacts", "score")
 BEST_COLUMNS = ("contig", "frag", "side", "rank", "partner_contig", "partner_frag", "partner_side", "contacts", "score")
+SUPPORT_COLUMNS = COLUMNS + ("support", "mutual", "boot_mean", "boot_min", "boot_max")
 STATUS_NAMES = {LINK_VALID: "valid", LINK_NONFINITE: "nonfinite"}
 
 
@@ -96,5 +105,30 @@ def write_links_tsv(path, table):
             row = [str(int(table[c][i])) for c in COLUMNS[:-1]]
             s = float(table["score"][i])
             row.append("nan" if not np.isfinite(s) else repr(s))
+            fh.write("\t".join(row) + "\n")
+    return n
+
+
+def support_table(sampler_or_engine, seed, n_rep, min_frags=1, threshold=0.0):
+    """link_table's rows of the engine's current layout plus the bootstrap columns: a dict of numpy columns SUPPORT_COLUMNS (support and
+    mutual are fractions of the n_rep replicates; NaN where the link has no score)."""
+    e = _engine(sampler_or_engine)
+    b = e.end_links_bootstrap(seed, n_rep, min_frags, threshold)
+    t = table_from(e.download_frags(), b["end_a"], b["end_b"], b["contacts"], b["score"])
+    t.update({"support": b["support"], "mutual": b["mutual"], "boot_mean": b["mean"], "boot_min": b["min"], "boot_max": b["max"]})
+    return t
+
+
+def write_support_tsv(path, table):
+    """Write `table` (support_table's dict) as a TSV file with a header line; floats with 17 significant digits, NaN as 'nan'."""
+    n = len(table["score"])
+    ints = COLUMNS[:-1]
+    with open(path, "w") as fh:
+        fh.write("\t".join(SUPPORT_COLUMNS) + "\n")
+        for i in range(n):
+            row = [str(int(table[c][i])) for c in ints]
+            for c in SUPPORT_COLUMNS[len(ints):]:
+                v = float(table[c][i])
+                row.append("nan" if not np.isfinite(v) else repr(v))
             fh.write("\t".join(row) + "\n")
     return n

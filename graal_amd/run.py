@@ -49,6 +49,13 @@ def main(argv=None):
                                                          "layout with contacts between them, with the log-likelihood their join would add "
                                                          "(graal_amd.links)")
     ap.add_argument("--links-min-frags", type=int, default=1, help="with --links: only contigs of at least this many fragments (default 1)")
+    ap.add_argument("--link-support", type=int, default=0, metavar="R",
+                    help="write link_support.tsv into the output folder: links.tsv's columns plus the bootstrap support of every listed "
+                         "link of the final layout -- the fraction of R Poisson resamplings of the contacts (1 .. 1024, one GPU call) in "
+                         "which the join still scores above 0, the fraction in which it also is the join both ends choose (mutual), and "
+                         "the mean, smallest and largest resampled score; --links-min-frags applies")
+    ap.add_argument("--link-support-seed", type=int, default=None, help="with --link-support: the seed of the resampling "
+                                                                        "(default: --seed, or 0 when that is unset)")
     ap.add_argument("--scaffold", action="store_true", help="after the explode and before the MCMC, join mutual-best contig ends round by "
                                                             "round (graal_amd.scaffold); writes scaffold.tsv")
     ap.add_argument("--scaffold-min-score", type=float, default=0.0, help="with --scaffold: only joins scoring above this (default 0)")
@@ -129,6 +136,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not 0 <= args.junction_support <= 1024:
         raise SystemExit("--junction-support must be in 0 .. 1024")
+    if not 0 <= args.link_support <= 1024:
+        raise SystemExit("--link-support must be in 0 .. 1024")
     if args.junction_gaps and (not 2 <= args.junction_gaps_points <= 64 or args.junction_gaps_drop < 0
                                or (args.junction_gaps_max_kb is not None and not args.junction_gaps_max_kb > 0)):
         raise SystemExit("--junction-gaps-points must be in 2 .. 64, --junction-gaps-drop >= 0 and --junction-gaps-max-kb > 0")
@@ -242,6 +251,11 @@ def main(argv=None):
     if args.links:
         from . import links
         links.write_links_tsv(os.path.join(out, "links.tsv"), links.link_table(smp, args.links_min_frags))
+    if args.link_support:
+        from . import links
+        boot_seed = args.link_support_seed if args.link_support_seed is not None else (args.seed if args.seed is not None else 0)
+        links.write_support_tsv(os.path.join(out, "link_support.tsv"),
+                                links.support_table(smp, boot_seed, args.link_support, args.links_min_frags))
     if args.insertions:
         from . import insert
         table, _ = insert.fitting_insertion_table(smp, args.insert_max_frags)   # (a smaller piece size when over the device budget)

@@ -381,6 +381,50 @@ int graal_end_links_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, int64_t*
 int graal_end_links_best(graal_ctx* h, int32_t min_frags, int32_t* best_end, int64_t* best_q, int64_t* n_mutual);
 int graal_end_links_mutual_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, int64_t* q, int64_t cap);
 
+/* Link support: a Poisson bootstrap of the read pairs behind every listed link, all replicates in one call
+ * (graal_amd/csrc/links_boot.h).
+ * Replicate counts.  Replicate r = 0 .. n_rep - 1 of contact k counts
+ *   ob*_{k,r} = sim_poisson(ob_k, SimStream(row_k, col_k, 2 | r << 8, seed))
+ * -- Philox4x32-10 keyed by the seed, counter (row_k, col_k, 2 | r << 8, draw index), then graal_simulate_contacts' Poisson sampler: the
+ * same stream, tag and sampler as graal_junction_bootstrap, so under one seed replicate r of the link support and replicate r of the
+ * junction support are the same resampled dataset.  A permutation of the list changes nothing, and replicate r does not depend on n_rep.
+ * ob <= 0 draws 0; a non-integer count is the rate as it stands.
+ * The listed set is the data's: exactly the links graal_end_links(min_frags) lists, in its (end_a, end_b) order, with its q, contacts and
+ * status word for word.
+ * A link's replicate score L*_r(link) is what graal_end_links returns for that link on the same layout with every count replaced by
+ * ob*_{k,r}; contacts that drew 0 stay in the list with count 0.  Spelled out: everything that does not multiply a count is computed once
+ * for all replicates (the expected mass of the fragment pairs, the pairs with a mixed bin beyond the window, the mass part of the mirror
+ * term of a reversed contig); every term that does multiply a count is re-formed with ob* (the record terms
+ * ob* . (ln ex_joined - ln ex_trans), the mirror's contact term, and its subtraction on the partner), each rounded to Q once per
+ * (contact, end combination, replicate) and summed in int64.  A replicate record whose key is not in the data's table is dropped: it
+ * cannot belong to a listed link.  A replicate term that does not fit Q marks the link GRAAL_LINK_NONFINITE in this call's status (q = 0),
+ * as an unrepresentable term of the data does.
+ * Per-link outputs (graal_end_links_bootstrap_fetch, n_links entries each, cap < n_links: GRAAL_E_ARG): end_a, end_b, q, contacts, status
+ * as above; support = the number of replicates with L*_r > threshold_q; q_sum, q_min, q_max = the sum, the smallest and the largest L*_r
+ * (the sum of up to 1024 scores below 2^52 in Q cannot overflow int64); mutual = the number of replicates in which the link is MUTUAL:
+ * L*_r > threshold_q and each of its two ends is the other's best partner among the valid listed links under replicate r's scores, ties
+ * towards the lower partner end -- graal_end_links_best's rule applied to replicate r (threshold_q = 0 is its Q > 0); q_rep, if not NULL,
+ * the matrix L*_r at q_rep[r * n_links + link] (replicate-major; kept in host memory between the call and the fetch).  q_rep must be NULL
+ * unless the call set want_rep (GRAAL_E_ARG).  All replicate outputs are 0 where status is not GRAAL_LINK_VALID.
+ * "Valid" in the mutual rule is the DATA's status: a link that only a replicate term marks non-finite (a count times its unit beyond Q)
+ * reports zeros itself but still competed, with that term taken as 0, for its ends' best partner in every replicate.  The matrix of a
+ * want_rep call may hold at most GRAAL_LINKS_MAX_BYTES (n_rep * n_links * 8 bytes of host memory): beyond that, or when the host cannot
+ * provide it, GRAAL_E_UNSUPPORTED with the bytes in the message.
+ * 1 <= n_rep <= 1024, min_frags >= 1, no null pointer but q_rep: else GRAAL_E_ARG.  Results are bit-identical from call to call, for any
+ * grid and any batching of the replicates (batches of up to 64, as many as fit 256 MB of per-replicate arrays).
+ * Needs, refuses and leaves alone what graal_end_links does: GRAAL_E_UNSUPPORTED with repeated bins, and when the link table plus the
+ * bootstrap's arrays (per link, per table slot, and one batch of replicates) would need more than GRAAL_LINKS_MAX_BYTES.  The check is in
+ * two steps: graal_end_links' own, before the link table is allocated, and the bootstrap's once the number of links is known -- by then
+ * the link table and two arrays of n + 3 words per contig label exist; the per-slot, per-link and per-batch arrays, which are the bulk,
+ * are allocated only behind it.  The message gives the bytes needed;
+ * GRAAL_E_STATE with an exchange or RCCL attached; no relabel, the step state untouched.  The call leaves graal_end_links' table in
+ * place (graal_end_links_fetch may follow); a later graal_end_links call ends the bootstrap's result. */
+int graal_end_links_bootstrap(graal_ctx* h, int32_t min_frags, uint64_t seed, int32_t n_rep, int64_t threshold_q, int32_t want_rep,
+                              int64_t* n_links);
+int graal_end_links_bootstrap_fetch(graal_ctx* h, int32_t* end_a, int32_t* end_b, int64_t* q, int64_t* contacts, uint8_t* status,
+                                    int32_t* support, int32_t* mutual, int64_t* q_sum, int64_t* q_min, int64_t* q_max, int64_t* q_rep,
+                                    int64_t cap);
+
 /* A batch of cuts and joins applied to the CURRENT layout in one call (graal_amd/csrc/edit.h).  Labels must be < 2n + 4 and positions a
  * permutation of 0 .. count - 1 per label, as graal_upload_frags accepts them.
  * CUTS first: for every fragment f of cut_after[0 .. n_cuts), the junction after f is cut.  In a linear contig f must not be its last
